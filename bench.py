@@ -73,6 +73,10 @@ def parse_args(argv=None):
                     help="print the torch.distributed.run command and backend this call would start its ranks with, as JSON, "
                          "and exit (no GPU call)")
     ap.add_argument("--side-json", default="", help="also write the side measurements (the earlier stdout line) to this file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the headline step returned in its last step (X, tonality and "
+                         "threshold of encode(), the PCM of decode(); rank 0's clips) as DIR/<name>.npy, float32: in full "
+                         "when small, else a fixed seeded sample of the flattened output (dump_indices()), < 64 MB in all")
     return ap.parse_args(argv)
 
 
@@ -103,7 +107,14 @@ def launch_ranks(args):
     relay their output.  Never an exec: the ranks are child processes, this process exits with their status."""
     import torch
     have = torch.cuda.device_count()          # (counting devices does not initialise the GPU on this image)
-    plan = plan_launch(args.gpus, have, args.dist, os.environ, [a for a in sys.argv[1:] if a != "--dry-run-launch"], free_port())
+    argv = [a for a in sys.argv[1:] if a != "--dry-run-launch"]
+    for i, a in enumerate(argv):   # the ranks run from ROOT: they get --dump-outputs as this process resolved it
+        if a.startswith("--du"):   # (argparse takes any unambiguous prefix of --dump-outputs)
+            if "=" in a:
+                argv[i] = "--dump-outputs=" + args.dump_outputs
+            elif i + 1 < len(argv):
+                argv[i + 1] = args.dump_outputs
+    plan = plan_launch(args.gpus, have, args.dist, os.environ, argv, free_port())
     if args.dry_run_launch:
         print(json.dumps(plan))
         return 0
@@ -415,6 +426,39 @@ def timed_loop_api(torch, codec, x, steps, warmup, barrier=None, settle_ms=0.0):
     return el, enc, dec, w0, w1, n_settle, out
 
 
+# ---- --dump-outputs: the results of the timed path, for comparing two builds output for output ------------------------
+DUMP_BUDGET_BYTES = 48 << 20     # all files together (< 64 MB), split evenly over the outputs
+DUMP_SEED = 1234
+
+
+def dump_indices(np, numel, keep, seed=DUMP_SEED):
+    """Flat indices of the fixed sample of an output of `numel` elements: None (all of it) when numel <= keep, else one
+    element drawn uniformly from each of `keep` equal strata of the flat range -- sorted, distinct, every region of the
+    tensor covered.  Depends on (numel, keep, seed) only: every run and every build samples the same elements."""
+    if numel <= keep:
+        return None
+    edges = np.arange(keep + 1, dtype=np.int64) * numel // keep
+    return edges[:-1] + np.random.default_rng(seed).integers(0, edges[1:] - edges[:-1])
+
+
+def dump_outputs(np, torch, outdir, arrays):
+    """Writes each output (name -> device tensor) as outdir/<name>.npy in float32 (float64 stays float64), in full or as
+    the dump_indices() sample of the flattened tensor; returns what was written."""
+    os.makedirs(outdir, exist_ok=True)
+    files = {}
+    for name, a in arrays.items():
+        dt = torch.float64 if a.dtype == torch.float64 else torch.float32
+        keep = DUMP_BUDGET_BYTES // (len(arrays) * (8 if dt == torch.float64 else 4))
+        flat = a.detach().reshape(-1)
+        idx = dump_indices(np, flat.numel(), keep)
+        if idx is not None:
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+        host = flat.to(dt).cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), host if idx is not None else host.reshape(tuple(a.shape)))
+        files[name] = {"shape": list(a.shape), "written": int(host.size), "sampled": idx is not None}
+    return {"dir": outdir, "sample_seed": DUMP_SEED, "files": files}
+
+
 def other_configs(torch, np, audiocodec_amd, dev, steps, warmup, settle_ms):
     """Side measurements beside the headline (rank 0, N = 1 only, outside the timed region): the all-float32 spreading
     product on the headline workload, the cache-resident K = 46 length of SURVEY 8(d), BASELINE configs[3] and
@@ -623,6 +667,10 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         sys.exit("--gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("--steps must be >= 1")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     in_torchrun = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     force_dist = args.dist in ("nccl", "gloo") or os.environ.get("AC_BENCH_FORCE_DIST", "") not in ("", "0")
     if not in_torchrun and (args.gpus > 1 or force_dist or args.dry_run_launch):
@@ -708,6 +756,10 @@ def main():
     err_max, = acd.reduce_scalars([err], "max", device=dev)
     if err_max > 1.0 / 32768.0:
         sys.exit("bench.py: round trip error %g exceeds 1 LSB of int16" % err_max)
+    dumped = None
+    if rank == 0 and args.dump_outputs:      # outside the timed region; before the side measurements free these tensors
+        dumped = dump_outputs(np, torch, args.dump_outputs,
+                              {"encode_X": X, "encode_tonality": t, "encode_threshold": thr, "decode_pcm": xh})
     ranks_seen = torch.distributed.get_world_size() if use_dist else world
     backend_seen = torch.distributed.get_backend() if use_dist else None
     enc_ms, dec_ms = float(np.mean(enc_all)), float(np.mean(dec_all))
@@ -737,6 +789,8 @@ def main():
         }
         if cold is not None:
             side["cold_start"] = cold
+        if dumped is not None:
+            side["dump_outputs"] = dumped
         if smi is not None:
             pr = torch.cuda.get_device_properties(dev)
             side["gpu_state"] = smi.finish(w0, w1, "%04x:%02x:%02x" % (pr.pci_domain_id, pr.pci_bus_id, pr.pci_device_id))

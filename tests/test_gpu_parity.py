@@ -2372,6 +2372,57 @@ def test_bench_contract_line_on_a_small_workload():
     assert d["reduced_over_ranks"]["frames_per_step"] == 16 * 2 * 32
 
 
+DUMP_NAMES = ("encode_X", "encode_tonality", "encode_threshold", "decode_pcm")
+
+
+def test_bench_dump_outputs_in_full_on_a_small_workload(tmp_path):
+    """--dump-outputs on a workload small enough to be written in full: the four results of the last timed step as float32
+    arrays of their shapes, summing to the checksums of the line, and the same bytes from a second process."""
+    common = ("--clips", 16, "--blocks", 32, "--steps", 3, "--warmup", 1, "--settle-ms", 5, "--no-cpu-baseline",
+              "--no-other-configs", "--no-workspace", "--no-smi")
+    got = []
+    for run in ("a", "b"):
+        d = _run_bench(*common, "--dump-outputs", tmp_path / run)
+        assert d["steps"] == 3 and not any(f["sampled"] for f in d["_side"]["dump_outputs"]["files"].values())
+        got.append({k: np.load(tmp_path / run / (k + ".npy")) for k in DUMP_NAMES})
+    o, N, K = got[0], 1024, 32
+    assert o["encode_X"].shape == o["encode_threshold"].shape == (16, K + 1, N, 2)
+    assert o["encode_tonality"].shape == (16, K + 1, 1, 2) and o["decode_pcm"].shape == (16, (K + 2) * N, 2)
+    assert all(a.dtype == np.float32 for a in o.values())
+    s = d["reduced_over_ranks"]
+    for k, c in (("encode_X", "checksum_X"), ("encode_tonality", "checksum_tonality"), ("encode_threshold", "checksum_thr"),
+                 ("decode_pcm", "checksum_pcm")):
+        assert abs(float(o[k].sum(dtype=np.float64)) - s[c]) <= 1e-9 * max(1.0, abs(s[c])), (k, s[c])
+        assert np.array_equal(o[k], got[1][k]), k
+
+
+def test_bench_dump_outputs_sample_the_headline_workload(tmp_path):
+    """At the headline size (~1 GB per output) --dump-outputs writes the fixed sample of bench.dump_indices(), under 64 MB
+    in all, and the sampled values are what codec.encode() / decode() return on the bench's own inputs."""
+    import importlib.util
+    import os
+    from conftest import ROOT
+    d = _run_bench("--steps", 2, "--warmup", 1, "--settle-ms", 5, "--no-cpu-baseline", "--no-other-configs", "--no-workspace",
+                   "--no-smi", "--dump-outputs", tmp_path)
+    assert d["config"]["clips_per_gpu"] == 256 and d["config"]["blocks"] == 468
+    assert sum(os.path.getsize(tmp_path / (k + ".npy")) for k in DUMP_NAMES) < 64e6
+    spec = importlib.util.spec_from_file_location("ac_bench_under_test", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    x = b.make_clips(torch, torch.device("cuda"), 0, 256, 468)
+    codec = audiocodec_amd.AudioCodec(48000, 1024)
+    X, t, thr = codec.encode(x)
+    del x
+    want = dict(zip(DUMP_NAMES, (X, t, thr, codec.decode(X))))
+    files = d["_side"]["dump_outputs"]["files"]
+    assert files["encode_X"]["sampled"] and not files["encode_tonality"]["sampled"]
+    for k in DUMP_NAMES:
+        a = want[k].reshape(-1)
+        idx = b.dump_indices(np, a.numel(), b.DUMP_BUDGET_BYTES // (4 * len(DUMP_NAMES)))
+        a = (a if idx is None else a[torch.from_numpy(idx).cuda()]).cpu().numpy()
+        assert np.array_equal(np.load(tmp_path / (k + ".npy")).reshape(-1), a), k
+
+
 def test_bench_two_ranks_on_one_gpu_equal_one_rank():
     """`python bench.py --gpus 2` starts its own two ranks (gloo when the box has fewer devices than ranks; both run the
     HIP kernels on the one GPU), prints n_gpus = 2, and the frame count / checksums of X, thr, PCM, tonality reduced over

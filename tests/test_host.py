@@ -260,7 +260,7 @@ def test_bench_launch_plan_backend_by_device_count():
     assert b.plan_launch(2, 8, "auto", {"AC_BENCH_BACKEND": "gloo"}, [], 1)["backend"] == "gloo"
 
 
-def test_bench_dry_run_launch_prints_the_plan():
+def test_bench_dry_run_launch_prints_the_plan(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run-launch"],
                          capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stdout + out.stderr
@@ -268,6 +268,41 @@ def test_bench_dry_run_launch_prints_the_plan():
     plan = json.loads(out.stdout.strip().splitlines()[-1])
     assert plan["ranks"] == 2 and plan["backend"] == ("nccl" if plan["devices"] >= 2 else "gloo")
     assert "--dry-run-launch" not in plan["cmd"]
+    # a relative --dump-outputs reaches the ranks (which run from the repository root) once, as this process resolved it
+    for form, want in ((["--dump-outputs", "outs", "--steps", "3"], ["--dump-outputs", str(tmp_path / "outs"), "--steps", "3"]),
+                       (["--dump-outputs=outs"], ["--dump-outputs=" + str(tmp_path / "outs")])):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run-launch"] + form,
+                             capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+        assert out.returncode == 0, out.stdout + out.stderr
+        cmd = json.loads(out.stdout.strip().splitlines()[-1])["cmd"]
+        assert cmd[-len(want):] == want and sum(a.startswith("--dump-outputs") for a in cmd) == 1, cmd
+
+
+def test_bench_refuses_zero_steps():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--no-cpu-baseline", "--no-smi"],
+                         capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode != 0 and "--steps" in out.stderr
+
+
+def test_bench_dump_sample_is_fixed_and_within_budget(tmp_path):
+    """--dump-outputs: an output larger than its share of the budget is written as one element of each of `keep` equal strata
+    of its flat range (sorted, distinct, the same in every run); smaller ones in full; the four files stay under 64 MB."""
+    b = _bench_module()
+    keep = b.DUMP_BUDGET_BYTES // (4 * 4)
+    assert 4 * keep * 4 < 64e6
+    assert b.dump_indices(np, keep, keep) is None
+    n = 256 * 469 * 1024 * 2                                      # X of the headline workload
+    i = b.dump_indices(np, n, keep)
+    assert i.dtype == np.int64 and len(i) == keep and i[0] >= 0 and i[-1] < n and np.all(np.diff(i) > 0)
+    assert np.array_equal(i, b.dump_indices(np, n, keep))
+    edges = np.arange(keep + 1, dtype=np.int64) * n // keep
+    assert np.all(edges[:-1] <= i) and np.all(i < edges[1:])                 # one element in each stratum
+    big, small = torch.randn(keep + 1000), torch.randn(3, 5, 2)
+    info = b.dump_outputs(np, torch, str(tmp_path), {"a": big, "b": small, "c": small.double(), "d": small})
+    assert info["files"]["a"]["sampled"] and not info["files"]["b"]["sampled"]
+    a = np.load(tmp_path / "a.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, big.numpy()[b.dump_indices(np, big.numel(), keep)])
+    assert np.array_equal(np.load(tmp_path / "b.npy"), small.numpy()) and np.load(tmp_path / "c.npy").dtype == np.float64
 
 
 def test_bench_rank_without_a_device_refuses_nccl():
