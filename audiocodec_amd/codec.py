@@ -180,6 +180,42 @@ class AudioCodec:
         self.decode_into(X, x)
         return x
 
+    # ---- quantised spectra (extension) ------------------------------------------------
+    def encode_quantized(self, x, drown=0.0):
+        """:meth:`encode`, then :meth:`PsychoacousticModel.quantize` on its X and threshold: x [B, K*N, C] (float or
+        ``torch.int16`` PCM) -> (codes int16 [B, K+1, N, C], sf int8 [B, K+1, M, C]).  Two launches; X, tonality and
+        threshold are temporaries.  float32 only, not differentiable."""
+        _host.require_float32(self.compute_dtype, "encode_quantized")
+        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+            raise ValueError("x requires a gradient: quantisation is not differentiable -- use encode() and "
+                             "psy.add_noise(), its differentiable stand-in")
+        X, _, thr = self.encode(x, drown)
+        return self.psy.quantize(X, thr)
+
+    def decode_quantized_launches(self, channels_n=2, device=None):
+        """Launches :meth:`decode_quantized` takes for ``channels_n`` channels (``ac_decode_quantized_launches``): 1 = the
+        synthesis dequantises in its loads (filters_n 1024 / 2048, mono / stereo), 2 = dequantise, then :meth:`decode`."""
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return int(self._lib.ac_decode_quantized_launches(self.mdct._plan(dev), self.psy._plan(dev), int(channels_n)))
+
+    def decode_quantized(self, codes, sf, pcm16=False):
+        """codes int16 [B, K', N, C], sf int8 [B, K', M, C] -> x [B, (K'+1)*N, C] (``torch.int16`` with ``pcm16=True``):
+        bit-equal to ``decode(psy.dequantize(codes, sf), pcm16)``.  float32 only."""
+        _host.require_float32(self.compute_dtype, "decode_quantized")
+        codes, sf = self.psy._check_codes(codes, sf)
+        B, Kp, N, C = codes.shape
+        dev = codes.device
+        x = torch.empty((B, (Kp + 1) * N, C), dtype=torch.int16 if pcm16 else torch.float32, device=dev)
+        mdct, psy = self.mdct._plan(dev), self.psy._plan(dev)
+        scratch = None
+        if self._lib.ac_decode_quantized_launches(mdct, psy, C) != 1:
+            scratch = torch.empty((B, Kp, N, C), dtype=torch.float32, device=dev)
+        with _host.on_device(dev):
+            _lib.check(self._lib.ac_decode_quantized(
+                mdct, psy, _host.ptr(codes), _host.ptr(sf), None if pcm16 else _host.ptr(x), _host.ptr(x) if pcm16 else None,
+                _host.ptr(scratch) if scratch is not None else None, B, Kp, C, _host.stream_ptr(dev)))
+        return x
+
     def decode_into(self, X, x):
         """:meth:`decode` into a caller-owned PCM tensor ``x [B, (K'+1)*N, C]`` (``torch.int16`` selects 16-bit PCM);
         same exactness rules as :meth:`encode_into`."""

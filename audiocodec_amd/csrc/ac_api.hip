@@ -185,6 +185,17 @@ int ac_psy_tables_host_pre(int N, int M, double sample_rate, double alpha, int p
   return AC_OK;
 }
 
+int ac_psy_scale_bands_host(double sample_rate, int filter_bands_n, int bark_bands_n, int32_t* offsets) {
+  AC_REQUIRE(filter_bands_n >= 1 && bark_bands_n >= 1, "filter_bands_n (%d) and bark_bands_n (%d) must be positive",
+             filter_bands_n, bark_bands_n);
+  AC_REQUIRE(sample_rate > 0, "sample_rate must be positive");
+  AC_REQUIRE(offsets != nullptr, "offsets is NULL");
+  std::vector<int32_t> off;
+  scale_bands(sample_rate, filter_bands_n, bark_bands_n, off);
+  std::copy(off.begin(), off.end(), offsets);
+  return AC_OK;
+}
+
 // ---- plans --------------------------------------------------------------------------------------
 
 int ac_mdct_plan_create(int N, int window, int device, ac_mdct_plan** out) {
@@ -408,6 +419,16 @@ static int psy_plan_build(int N, int M, double sample_rate, double alpha, int de
     if (!st) st = upload(p->host.quiet, &p->d_quiet64);
     if (!st) st = upload(beta64, &p->d_beta64);
   }
+  {
+    // quantiser: scale-factor band offsets and the band of every bin (ac_quant.hip)
+    std::vector<int32_t> qoff;
+    scale_bands(sample_rate, N, M, qoff);
+    std::vector<uint16_t> qband(N);
+    for (int j = 0; j < M; ++j)
+      for (int i = qoff[j]; i < qoff[j + 1]; ++i) qband[i] = (uint16_t)j;
+    if (!st) st = upload(qoff, &p->d_qoff);
+    if (!st) st = upload(qband, &p->d_qband);
+  }
   if (!st && fast_psy_supported(p)) {
     st = fast_psy_plan_init(p);
     if (!st) p->fast = 1;
@@ -462,6 +483,8 @@ int ac_psy_plan_destroy(ac_psy_plan* p) {
   (void)hipFree(p->d_fast);
   (void)hipFree(p->d_mid);
   (void)hipFree(p->d_runs);
+  (void)hipFree(p->d_qoff);
+  (void)hipFree(p->d_qband);
   delete p;
   return AC_OK;
 }
@@ -944,6 +967,72 @@ int ac_amplitude_to_db_backward(const float* a, const float* grad_out, float* gr
 int ac_add_noise(const float* X, const float* thr, float* out, size_t n, uint64_t seed, void* stream) {
   AC_REQUIRE(n == 0 || (thr != nullptr && out != nullptr), "NULL tensor pointer");   // X == NULL: zeros
   return launch_add_noise(X, thr, out, n, seed, (hipStream_t)stream);
+}
+
+// ---- quantiser (ac_quant.hip) -----------------------------------------------
+
+static int check_quant(const ac_psy_plan* psy, int B, int F, int C) {
+  AC_REQUIRE(psy != nullptr, "plan is NULL");
+  AC_REQUIRE(B >= 0 && F >= 0 && C >= 0, "negative dimension (B=%d, frames=%d, C=%d)", B, F, C);
+  AC_REQUIRE(psy->N % 2 == 0, "the quantiser needs an even filter_bands_n (got %d)", psy->N);
+  AC_REQUIRE(psy->d_qoff != nullptr && psy->d_qband != nullptr, "plan has no quantiser tables");
+  return AC_OK;
+}
+
+int ac_quantize(const ac_psy_plan* psy, const float* X, const float* thr, int16_t* codes, int8_t* sf, int B, int F, int C,
+                void* stream) {
+  int st = check_quant(psy, B, F, C);
+  if (st) return st;
+  if (B == 0 || F == 0 || C == 0) return AC_OK;
+  AC_REQUIRE(X != nullptr && thr != nullptr && codes != nullptr && sf != nullptr, "NULL tensor pointer");
+  AC_REQUIRE_ALIGNED(X, thr, codes, sf);
+  DeviceGuard guard(psy->device);
+  return launch_quantize(psy, X, thr, codes, sf, B, F, C, (hipStream_t)stream);
+}
+
+int ac_dequantize(const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, float* X, int B, int F, int C, void* stream) {
+  int st = check_quant(psy, B, F, C);
+  if (st) return st;
+  if (B == 0 || F == 0 || C == 0) return AC_OK;
+  AC_REQUIRE(X != nullptr && codes != nullptr && sf != nullptr, "NULL tensor pointer");
+  AC_REQUIRE_ALIGNED(X, codes, sf);
+  DeviceGuard guard(psy->device);
+  return launch_dequantize(psy, codes, sf, X, B, F, C, (hipStream_t)stream);
+}
+
+static bool decode_quantized_fuses(const ac_mdct_plan* mdct, int C) {
+  return !g_force_generic && wave_level(mdct, C, 0, 1) && fast_inv_quant_serves(mdct, C);
+}
+
+int ac_decode_quantized_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C) {
+  if (!mdct || !psy || mdct->N != psy->N || mdct->device != psy->device || C < 1) return 0;
+  return decode_quantized_fuses(mdct, C) ? 1 : 2;
+}
+
+int ac_decode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, float* x,
+                        int16_t* pcm16, float* scratch, int B, int Kp, int C, void* stream) {
+  AC_REQUIRE(mdct != nullptr && psy != nullptr, "plan is NULL");
+  AC_REQUIRE(mdct->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", mdct->N, psy->N);
+  AC_REQUIRE(mdct->device == psy->device, "plans live on different devices");
+  int st = check_quant(psy, B, Kp, C);
+  if (st) return st;
+  AC_REQUIRE((x != nullptr) != (pcm16 != nullptr), "exactly one of x (float32) and pcm16 must be given");
+  if (B == 0 || C == 0) return AC_OK;
+  AC_REQUIRE(Kp == 0 || (codes != nullptr && sf != nullptr), "NULL tensor pointer");
+  void* out = x ? static_cast<void*>(x) : static_cast<void*>(pcm16);
+  AC_REQUIRE_ALIGNED(codes, sf, out);
+  DeviceGuard guard(mdct->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (Kp >= 1 && decode_quantized_fuses(mdct, C))
+    return launch_inv_fast_quant(mdct, psy, codes, sf, out, pcm16 != nullptr, B, Kp, C, s);
+  AC_REQUIRE(Kp == 0 || scratch != nullptr,
+             "scratch [B, Kp, N, C] float32 is required where ac_decode_quantized_launches() returns 2");
+  AC_REQUIRE_ALIGNED(scratch);
+  if (Kp >= 1) {
+    st = launch_dequantize(psy, codes, sf, scratch, B, Kp, C, s);
+    if (st) return st;
+  }
+  return mdct_inverse(mdct, scratch, out, pcm16 != nullptr, B, Kp, C, stream);
 }
 
 // ---- buffer placement probe ---------------------------------------------------------------------

@@ -32,6 +32,7 @@
 
 #include "ac_internal.h"
 #include "ac_psy_mid_dev.h"
+#include "ac_quant_dev.h"
 #include "ac_psy_runs_dev.h"
 
 namespace ac {
@@ -545,6 +546,54 @@ __device__ __forceinline__ void store_row_h(int16_t* __restrict__ r0, int16_t* _
     }
   }
 }
+// ---- a row of quantised spectra (ac_quant.hip): int16 codes and int8 scale factors, dequantised where the frame is used
+// -- X^ = fp32(code * step(sf)), the product ac_dequantize forms (ac_quant_dev.h).  A granule holds the raw codes and
+// scale factors of (2q, s0), (2q, s1), (2q+1, s0), (2q+1, s1) -- the element order of load_row -- so a prefetch of the next
+// frame only issues loads.  bw[i] packs the bands of bins 2q (low half) and 2q+1, q = 64 i + lane: frame-invariant, held in
+// registers for the whole strip.  sf0 / sf1 address the frame's scale-factor row [M, C] at the signal's channel.
+struct QGran {
+  s4 code;
+  uint32_t sfw;   // four scale-factor bytes, same order
+};
+template <int CMODE, int R>
+__device__ __forceinline__ void load_row_q(const int16_t* __restrict__ r0, const int16_t* __restrict__ r1,
+                                           const int8_t* __restrict__ sf0, const int8_t* __restrict__ sf1,
+                                           const uint32_t (&bw)[R], bool has1, int lane, QGran (&g)[R]) {
+  static_assert(CMODE == 0 || CMODE == 2, "quantised spectra: mono / stereo");
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const int q = 64 * i + lane;
+    const int j0 = (int)(bw[i] & 0xffffu), j1 = (int)(bw[i] >> 16);
+    if (CMODE == 0) {   // [M][2]: the two channels' scale factors of a band are one 16-bit word
+      g[i].code = reinterpret_cast<const s4*>(r0)[q];
+      g[i].sfw = (uint32_t)*reinterpret_cast<const uint16_t*>(sf0 + 2 * j0) |
+                 ((uint32_t)*reinterpret_cast<const uint16_t*>(sf0 + 2 * j1) << 16);
+    } else {
+      const s2 u = reinterpret_cast<const s2*>(r0)[q];
+      g[i].code = s4{u.x, 0, u.y, 0};
+      g[i].sfw = (uint32_t)(uint8_t)sf0[j0] | ((uint32_t)(uint8_t)sf0[j1] << 16);
+    }
+  }
+  if (CMODE == 2 && has1) {
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const s2 w = reinterpret_cast<const s2*>(r1)[64 * i + lane];
+      g[i].code.y = w.x;
+      g[i].code.w = w.y;
+      g[i].sfw |= ((uint32_t)(uint8_t)sf1[bw[i] & 0xffffu] << 8) | ((uint32_t)(uint8_t)sf1[bw[i] >> 16] << 24);
+    }
+  }
+}
+template <int R>
+__device__ __forceinline__ void dequant_frame(const QGran (&g)[R], v4f (&v)[R]) {
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const uint32_t w = g[i].sfw;
+    v[i] = v4f{dequant(g[i].code.x, (int8_t)(w & 0xff)), dequant(g[i].code.y, (int8_t)((w >> 8) & 0xff)),
+               dequant(g[i].code.z, (int8_t)((w >> 16) & 0xff)), dequant(g[i].code.w, (int8_t)(w >> 24))};
+  }
+}
+
 // IOF: 0 = float32 tensors; 1 = 16-bit PCM on the PCM side (spectra float32); 2 = bfloat16 tensors throughout
 template <int IOF> struct RowFmt { using type = Pcm16Fmt; };
 template <> struct RowFmt<2> { using type = Bf16Fmt; };
@@ -1251,9 +1300,19 @@ __device__ __forceinline__ void idct_frame(const v4f (&frm)[R], char* buf, gtab_
   }
 }
 
+// synthesis from quantised spectra (IOF 3: float32 PCM out, 4: 16-bit PCM out): InvArgs::X addresses the int16 codes
+struct QuantRows {
+  const int8_t* sf;        // [B, Kp, M, C]
+  const uint32_t* band32;  // [N/2]: bands of bins 2q | 2q+1 << 16
+  int M;
+};
+
 template <int R, int CMODE, int NW, int IOF = 0>
-__device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const int bid, const int nblocks) {
+__device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const int bid, const int nblocks,
+                                              const QuantRows* qr = nullptr) {
   using G = Geo<R>;
+  constexpr bool QUANT = IOF >= 3;
+  constexpr int OIOF = QUANT ? IOF - 3 : IOF;   // format of the PCM side
   constexpr int FH = G::FH;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   load_tables<NW, WAVE_LDS, G::I_LDS, 0>(lds, a.tab + G::I_TOTAL, nullptr);
@@ -1277,11 +1336,33 @@ __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const
   const bool has1 = pq.has1;
   const int n0 = sgm * a.seglen;
   const int n1 = min(a.nblk, n0 + a.seglen);
-  using spec_t = typename std::conditional<IOF == 2, int16_t, float>::type;   // storage of the spectrum
+  using spec_t = typename std::conditional<IOF == 2 || QUANT, int16_t, float>::type;   // storage of the spectrum
   const spec_t* X0 = reinterpret_cast<const spec_t*>(a.X) + row_off(pq.b0, a.Kp, 0, blk, pq.c0);   // frame 0 of the two signals
   const spec_t* X1 = reinterpret_cast<const spec_t*>(a.X) + row_off(pq.b1, a.Kp, 0, blk, pq.c1);
-  auto load_frame = [&](const spec_t* r0, const spec_t* r1, v4f (&dst)[R]) {
-    if constexpr (IOF == 2) load_row_h<Bf16Fmt, CMODE, R>(r0, r1, C, has1, lane, dst);
+  // what a loaded frame is held as until it is transformed: float32 rows, or the raw codes and scale factors (QUANT)
+  using hold_t = typename std::conditional<QUANT, QGran, v4f>::type;
+  // (QUANT) the bands of the lane's bin pairs, the same in every frame: held in registers by the 1024-filter kernel; the
+  // 2048-filter one (no registers to spare, and no frame in flight ahead) reads them with the frame
+  constexpr bool BW_REGS = QUANT && R == 8;
+  uint32_t bw[BW_REGS ? R : 1];
+  if constexpr (BW_REGS) {
+#pragma unroll
+    for (int i = 0; i < R; ++i) bw[i] = qr->band32[64 * i + lane];
+  }
+  auto load_frame = [&](int n, const spec_t* r0, const spec_t* r1, hold_t (&dst)[R]) {
+    if constexpr (QUANT) {
+      const size_t mc = (size_t)qr->M * C;
+      const int8_t* sf0 = qr->sf + row_off(pq.b0, a.Kp, n, mc, pq.c0);
+      const int8_t* sf1 = qr->sf + row_off(pq.b1, a.Kp, n, mc, pq.c1);
+      if constexpr (BW_REGS) {
+        load_row_q<CMODE, R>(r0, r1, sf0, sf1, bw, has1, lane, dst);
+      } else {
+        uint32_t bl[R];
+#pragma unroll
+        for (int i = 0; i < R; ++i) bl[i] = qr->band32[64 * i + lane];
+        load_row_q<CMODE, R>(r0, r1, sf0, sf1, bl, has1, lane, dst);
+      }
+    } else if constexpr (IOF == 2) load_row_h<Bf16Fmt, CMODE, R>(r0, r1, C, has1, lane, dst);
     else load_row<CMODE, (AC_NT_LOAD & 4) != 0, R>(r0, r1, C, has1, lane, dst);
   };
   const size_t ts0 = ((size_t)pq.b0 * C + pq.c0) * FH, ts1 = ((size_t)pq.b1 * C + pq.c1) * FH;   // stream state rows
@@ -1308,8 +1389,8 @@ __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const
 #pragma unroll
     for (int i = 0; i < R; ++i) row[i] = v4f{xe[i].x, xe[i].y, xo[i].x, xo[i].y};
     const size_t o0 = row_off(pq.b0, a.nblk, n, blk, pq.c0), o1 = row_off(pq.b1, a.nblk, n, blk, pq.c1);
-    if constexpr (IOF != 0)
-      store_row_h<typename RowFmt<IOF>::type, CMODE, R>(static_cast<int16_t*>(a.x) + o0, static_cast<int16_t*>(a.x) + o1, C, has1, lane, row);
+    if constexpr (OIOF != 0)
+      store_row_h<typename RowFmt<OIOF>::type, CMODE, R>(static_cast<int16_t*>(a.x) + o0, static_cast<int16_t*>(a.x) + o1, C, has1, lane, row);
     else store_row<CMODE, R>(static_cast<float*>(a.x) + o0, static_cast<float*>(a.x) + o1, C, has1, lane, row);
   };
 
@@ -1320,16 +1401,22 @@ __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const
     now0[r] = v2f{0.f, 0.f};
   }
   if (valid) {
-    v4f ahead[R];
+    hold_t ahead[R];
     if (left && !deferred) {
       // aliased half of frame n0-1 (always an existing frame: n0-1 < Kp)
-      v4f row[R];
-      load_frame(X0 + (size_t)(n0 - 1) * blk, X1 + (size_t)(n0 - 1) * blk, row);
-      if (AHEAD && n0 < a.Kp) load_frame(X0 + (size_t)n0 * blk, X1 + (size_t)n0 * blk, ahead);
+      hold_t row[R];
+      load_frame(n0 - 1, X0 + (size_t)(n0 - 1) * blk, X1 + (size_t)(n0 - 1) * blk, row);
+      if (AHEAD && n0 < a.Kp) load_frame(n0, X0 + (size_t)n0 * blk, X1 + (size_t)n0 * blk, ahead);
       v2f dummy[R];
-      idct_frame<R>(row, buf, tab, p1, lane, dummy, carry);
+      if constexpr (QUANT) {
+        v4f frm[R];
+        dequant_frame<R>(row, frm);
+        idct_frame<R>(frm, buf, tab, p1, lane, dummy, carry);
+      } else {
+        idct_frame<R>(row, buf, tab, p1, lane, dummy, carry);
+      }
     } else {
-      if (AHEAD && n0 < a.Kp) load_frame(X0 + (size_t)n0 * blk, X1 + (size_t)n0 * blk, ahead);
+      if (AHEAD && n0 < a.Kp) load_frame(n0, X0 + (size_t)n0 * blk, X1 + (size_t)n0 * blk, ahead);
       if (!left && a.tail_in) {
 #pragma unroll
         for (int j2 = 0; j2 < R; ++j2) {
@@ -1344,10 +1431,16 @@ __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const
     for (int n = n0; n < n1; ++n) {
       v2f now[R], nxt[R];
       if (n < a.Kp) {
-        if (!AHEAD) load_frame(X0 + (size_t)n * blk, X1 + (size_t)n * blk, ahead);
-        idct_frame<R>(ahead, buf, tab, p1, lane, now, nxt);
+        if (!AHEAD) load_frame(n, X0 + (size_t)n * blk, X1 + (size_t)n * blk, ahead);
+        if constexpr (QUANT) {   // (the frame's loads were issued one frame earlier: the waits land here)
+          v4f frm[R];
+          dequant_frame<R>(ahead, frm);
+          idct_frame<R>(frm, buf, tab, p1, lane, now, nxt);
+        } else {
+          idct_frame<R>(ahead, buf, tab, p1, lane, now, nxt);
+        }
         if (AHEAD && n + 1 < n1 && n + 1 < a.Kp)
-          load_frame(X0 + (size_t)(n + 1) * blk, X1 + (size_t)(n + 1) * blk, ahead);
+          load_frame(n + 1, X0 + (size_t)(n + 1) * blk, X1 + (size_t)(n + 1) * blk, ahead);
       } else {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -1398,6 +1491,15 @@ template <int R, int CMODE, int NW, int IOF = 0>
 __global__ __launch_bounds__(NW * 64, ((IOF == 2 || (IOF == 1 && !(R == 8 && CMODE != 1))) ? 2 : wpe<R, CMODE>())) void k_inv_fast(InvArgs a) {
   __shared__ __attribute__((aligned(16))) char lds[NW * WAVE_LDS + Geo<R>::TAB_LDS];
   inv_fast_body<R, CMODE, NW, IOF>(a, lds, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// the same synthesis reading quantised spectra (IOF 3 / 4, mono / stereo); its own kernel, so the instances above keep their
+// launch bounds and arguments
+template <int R, int CMODE, int NW, int IOF>
+__global__ __launch_bounds__(NW * 64, 2) void k_inv_fast_q(InvArgs a, QuantRows qr) {
+  static_assert(IOF == 3 || IOF == 4, "quantised spectra");
+  __shared__ __attribute__((aligned(16))) char lds[NW * WAVE_LDS + Geo<R>::TAB_LDS];
+  inv_fast_body<R, CMODE, NW, IOF>(a, lds, (int)blockIdx.x, (int)gridDim.x, &qr);
 }
 
 // Streaming duplex (BASELINE configs[4]): the analysis of chunk i + 1 and the synthesis of chunk i in ONE launch -- the
@@ -3112,6 +3214,51 @@ int launch_inv_fast(const ac_mdct_plan* p, const float* X, void* x, int iof, con
   else if (iof == 2) launch_inv_R<16, 2>(a, C, grid, s);
   else if (iof == 1) launch_inv_R<16, 1>(a, C, grid, s);
   else launch_inv_R<16, 0>(a, C, grid, s);
+#endif
+  AC_HIP_CHECK(hipGetLastError());
+  return AC_OK;
+}
+
+// ---- synthesis from quantised spectra (k_inv_fast_q): filters_n 1024 / 2048, mono / stereo ----
+bool fast_inv_quant_serves(const ac_mdct_plan* p, int C) {
+  if (!p->fast || fast_mdct_frames_per_wave(p->N) != 1 || (C != 1 && C != 2)) return false;
+#ifdef AC_NO_R16
+  if (p->N != Geo<8>::FN) return false;
+#endif
+  return true;
+}
+
+template <int R, int IOF>
+static void launch_inv_q_R(const InvArgs& a, const QuantRows& qr, int C, unsigned grid, hipStream_t s) {
+  const dim3 blk(AC_WAVES * 64);
+  if (C == 2) hipLaunchKernelGGL((k_inv_fast_q<R, 0, AC_WAVES, IOF>), dim3(grid), blk, 0, s, a, qr);
+  else hipLaunchKernelGGL((k_inv_fast_q<R, 2, AC_WAVES, IOF>), dim3(grid), blk, 0, s, a, qr);
+}
+
+int launch_inv_fast_quant(const ac_mdct_plan* p, const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, void* x,
+                          bool pcm16, int B, int Kp, int C, hipStream_t s) {
+  if (B <= 0 || C <= 0 || Kp <= 0) return AC_OK;
+  if (!fast_inv_quant_serves(p, C) || psy->N != p->N) {
+    set_error("internal: no synthesis from quantised spectra for filters_n = %d, %d channels", p->N, C);
+    return AC_EUNSUPPORTED;
+  }
+  InvArgs a;
+  unsigned grid;
+  // (the spectrum pointer addresses the codes: the kernel reads it as int16)
+  const int st = prep_inv_fast(p, reinterpret_cast<const float*>(codes), x, pcm16 ? 1 : 0, nullptr, nullptr, B, Kp, Kp + 1, C,
+                               a, grid);
+  if (st) return st;
+  QuantRows qr;
+  qr.sf = sf;
+  qr.band32 = reinterpret_cast<const uint32_t*>(psy->d_qband);
+  qr.M = psy->M;
+  if (p->N == Geo<8>::FN) {
+    if (pcm16) launch_inv_q_R<8, 4>(a, qr, C, grid, s);
+    else launch_inv_q_R<8, 3>(a, qr, C, grid, s);
+  }
+#ifndef AC_NO_R16
+  else if (pcm16) launch_inv_q_R<16, 4>(a, qr, C, grid, s);
+  else launch_inv_q_R<16, 3>(a, qr, C, grid, s);
 #endif
   AC_HIP_CHECK(hipGetLastError());
   return AC_OK;

@@ -157,6 +157,10 @@ struct ac_psy_plan {
   uint32_t* d_runs = nullptr;
   ac::RunsLayout runs_lay;
   int cus = 0;                 // compute units of the device (sizes the launches)
+  // quantiser (ac_quant.hip): scale-factor band offsets [M+1] (ac::scale_bands) and the band of every bin [N] (uint16,
+  // read as one 32-bit word per bin pair by the fused synthesis from codes)
+  int32_t* d_qoff = nullptr;
+  uint16_t* d_qband = nullptr;
 };
 
 struct ac_stream {
@@ -238,6 +242,11 @@ int launch_fwd_fast(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x
 bool fast_epilogue_supported(const ac_mdct_plan* p, const ac_psy_plan* psy, int iof, int C);
 int launch_inv_fast(const ac_mdct_plan* p, const float* X, void* x, int iof, const float* tail_in, float* tail_out,
                     int B, int Kp, int nblk, int C, hipStream_t s);
+// synthesis straight from quantised spectra (codes int16 [B,Kp,N,C], sf int8 [B,Kp,M,C]; ac_quant.hip), filters_n 1024 /
+// 2048, mono / stereo: the frames are dequantised in the loads, bit-equal to launch_inv_fast on launch_dequantize's output
+bool fast_inv_quant_serves(const ac_mdct_plan* p, int C);
+int launch_inv_fast_quant(const ac_mdct_plan* p, const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, void* x,
+                          bool pcm16, int B, int Kp, int C, hipStream_t s);
 int launch_psy_fast(const ac_psy_plan* p, const float* X, const float* t_in, float* t_out, float* thr, float drown,
                     int B, int F, int C, hipStream_t s, int iof = 0);
 // streaming duplex: the analysis of a chunk of k_fwd blocks (psy: with the fused masking model) and the synthesis of a
@@ -291,5 +300,9 @@ int launch_add_noise_typed(const void* X, const void* thr, void* out, size_t n, 
 int launch_db(const float* a, float* out, size_t n, int norm, hipStream_t s);
 int launch_db_bwd(const float* a, const float* g, float* ga, size_t n, int norm, hipStream_t s);
 int launch_add_noise(const float* X, const float* thr, float* out, size_t n, uint64_t seed, hipStream_t s);
+// quantiser (ac_quant.hip): X, thr [B,F,N,C] -> codes int16 [B,F,N,C], sf int8 [B,F,M,C], and back
+int launch_quantize(const ac_psy_plan* p, const float* X, const float* thr, int16_t* codes, int8_t* sf, int B, int F, int C,
+                    hipStream_t s);
+int launch_dequantize(const ac_psy_plan* p, const int16_t* codes, const int8_t* sf, float* X, int B, int F, int C, hipStream_t s);
 
 }  // namespace ac

@@ -1,0 +1,37 @@
+// Device helpers of the quantiser shared by its kernels (ac_quant.hip) and the synthesis from codes (ac_fast.hip): one
+// definition, so that every path dequantises bit for bit alike.  DESIGN.md section 8a has the definition.
+#pragma once
+#include <cstdint>
+#include <hip/hip_runtime.h>
+
+namespace ac {
+
+constexpr float kQuantSqrt3 = 1.73205080756887729353f;   // fp32(sqrt 3)
+
+// a product that is never contracted into a multiply-add (the library builds with -ffp-contract=fast)
+__device__ __forceinline__ float qmul(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// fp32(2^(-r/4)), r = 0 .. 3
+__device__ __forceinline__ float quant_ic(int r) {
+  return r == 0 ? 1.0f : r == 1 ? 0.84089641525371454303f : r == 2 ? 0.70710678118654752440f : 0.59460355750136053336f;
+}
+// step(s) = ldexp(c[s & 3], s >> 2) (arithmetic shift), c[r] = fp32(2^(r/4)), s in [-128, 127]: c[r] lies in [1, 2), so the
+// product is c[r]'s mantissa under the exponent 127 + (s >> 2) -- assembled from bits, without branches (v_cndmask only)
+__device__ __forceinline__ uint32_t quant_step_bits(int s) {
+  const int r = s & 3;
+  const uint32_t mant = (r & 2) ? ((r & 1) ? 0x5744fdu : 0x3504f3u) : ((r & 1) ? 0x1837f0u : 0u);
+  return ((uint32_t)(127 + (s >> 2)) << 23) | mant;
+}
+__device__ __forceinline__ float quant_step(int s) { return __uint_as_float(quant_step_bits(s)); }
+// inv(s) = ldexp(ic[s & 3], -(s >> 2))
+__device__ __forceinline__ float quant_inv_step(int s) { return __builtin_ldexpf(quant_ic(s & 3), -(s >> 2)); }
+// X^ = fp32(code * step(sf)); sf = -128 (a band with NaN / Inf) dequantises to NaN
+__device__ __forceinline__ float dequant(int code, int sf) {
+  const uint32_t st = sf == -128 ? 0x7fc00000u : quant_step_bits(sf);
+  return qmul((float)code, __uint_as_float(st));
+}
+
+}  // namespace ac

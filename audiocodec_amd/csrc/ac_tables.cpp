@@ -228,4 +228,16 @@ void winv_by_band(const PsyTables& t, SparseRows& out) {
   }
 }
 
+void scale_bands(double sample_rate, int N, int M, std::vector<int32_t>& off) {
+  off.assign(M + 1, N);
+  off[0] = 0;
+  const double w = 6.0 * std::asinh(sample_rate / 2.0 / 600.0) / (double)M;
+  int j = 0;   // band of the previous bin (the rule is monotone in i)
+  for (int i = 0; i < N; ++i) {
+    const double f = ((double)i + 0.5) * (sample_rate / 2.0) / (double)N;
+    const int band = std::min(M - 1, (int)std::floor(6.0 * std::asinh(f / 600.0) / w));
+    while (j < band) off[++j] = i;
+  }
+}
+
 }  // namespace ac

@@ -50,4 +50,9 @@ void winv_by_bin(const PsyTables& t, SparseRows& out);
 void w_by_bin(const PsyTables& t, SparseRows& out);
 void winv_by_band(const PsyTables& t, SparseRows& out);
 
+// Scale-factor bands of the quantiser (no counterpart in the reference): contiguous bin ranges
+// [off[j], off[j+1]), j = 0 .. M-1.  Bin i belongs to band min(M-1, floor(bark(f_i) / w)) with f_i = (i + 1/2) (sr/2) / N,
+// bark(f) = 6 asinh(f / 600), w = bark(sr/2) / M, all in float64 whatever the precompute dtype.  off has M + 1 entries.
+void scale_bands(double sample_rate, int N, int M, std::vector<int32_t>& off);
+
 }  // namespace ac

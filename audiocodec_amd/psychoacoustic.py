@@ -301,6 +301,76 @@ class PsychoacousticModel:
                                                     thr.numel(), seed, self._dtype_id, _host.stream_ptr(thr.device)))
         return out
 
+    # ---- quantiser (extension: what add_noise stands in for) -----------------------
+    @property
+    def scale_band_offsets(self):
+        """Scale-factor bands of the quantiser: int32 offsets ``[bark_bands_n + 1]``; band j holds bins
+        ``[o[j], o[j+1])`` (``ac_psy_scale_bands_host``, computed on the host in float64, no GPU needed)."""
+        off = np.empty((self.bark_bands_n + 1,), dtype=np.int32)
+        _lib.check(self._lib.ac_psy_scale_bands_host(float(self.sample_rate), self.filter_bands_n, self.bark_bands_n,
+                                                     off.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return off
+
+    def _check_quant_tensor(self, t, name, dtype, shape=None, device=None):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+        if t.requires_grad and torch.is_grad_enabled():
+            raise ValueError("%s requires a gradient: quantisation is not differentiable -- use add_noise(), its "
+                             "differentiable stand-in" % name)
+        if t.dtype != dtype:
+            raise ValueError("%s has dtype %s, expected %s" % (name, t.dtype, dtype))
+        if t.dim() != 4:
+            raise ValueError("%s must have 4 dimensions, got shape %s" % (name, tuple(t.shape)))
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+        if not t.is_cuda:
+            raise ValueError("%s lives on %s: the quantiser runs on ROCm device tensors only" % (name, t.device))
+        if device is not None and t.device != device:
+            raise ValueError("%s lives on %s but %s" % (name, t.device, device))
+        t = t.contiguous()
+        if t.data_ptr() % 16 != 0:      # a view that starts inside an allocation: the kernels want 16-byte aligned rows
+            t = t.clone()
+        return t
+
+    def quantize(self, mdct_amplitudes, masking_threshold):
+        """Perceptual quantiser: X, thr [B, F, N, C] float32 -> (codes int16 [B, F, N, C], sf int8 [B, F, M, C]).
+
+        Per scale-factor band (:attr:`scale_band_offsets`) and (clip, frame, channel) a step 2^(sf/4) with
+        step * sqrt(3) <= the band's smallest threshold, so the error of a bin is at most thr / (2 sqrt 3), and the noise
+        RMS at most the thr / 6 of :meth:`add_noise`; sf = -128 marks a band holding NaN / Inf (its codes are 0).  Not
+        differentiable (:meth:`add_noise` is the differentiable stand-in); float32 only."""
+        _host.require_float32(self.compute_dtype, "the quantiser")
+        X = self._check_quant_tensor(mdct_amplitudes, "mdct_amplitudes", torch.float32)
+        B, F, N, C = X.shape
+        if N != self.filter_bands_n:
+            raise ValueError("axis 2 of mdct_amplitudes (%d) != filter_bands_n (%d)" % (N, self.filter_bands_n))
+        thr = self._check_quant_tensor(masking_threshold, "masking_threshold", torch.float32, X.shape, X.device)
+        codes = torch.empty((B, F, N, C), dtype=torch.int16, device=X.device)
+        sf = torch.empty((B, F, self.bark_bands_n, C), dtype=torch.int8, device=X.device)
+        with _host.on_device(X.device):
+            _lib.check(self._lib.ac_quantize(self._plans.get(X.device), _host.ptr(X), _host.ptr(thr), _host.ptr(codes),
+                                             _host.ptr(sf), B, F, C, _host.stream_ptr(X.device)))
+        return codes, sf
+
+    def _check_codes(self, codes, sf):
+        codes = self._check_quant_tensor(codes, "codes", torch.int16)
+        B, F, N, C = codes.shape
+        if N != self.filter_bands_n:
+            raise ValueError("axis 2 of codes (%d) != filter_bands_n (%d)" % (N, self.filter_bands_n))
+        sf = self._check_quant_tensor(sf, "sf", torch.int8, (B, F, self.bark_bands_n, C), codes.device)
+        return codes, sf
+
+    def dequantize(self, codes, sf):
+        """Inverse map of :meth:`quantize`: X^ = fp32(code * 2^(sf/4)) [B, F, N, C] float32 (NaN in bands with sf = -128)."""
+        _host.require_float32(self.compute_dtype, "the quantiser")
+        codes, sf = self._check_codes(codes, sf)
+        B, F, N, C = codes.shape
+        X = torch.empty((B, F, N, C), dtype=torch.float32, device=codes.device)
+        with _host.on_device(codes.device):
+            _lib.check(self._lib.ac_dequantize(self._plans.get(codes.device), _host.ptr(codes), _host.ptr(sf), _host.ptr(X),
+                                               B, F, C, _host.stream_ptr(codes.device)))
+        return X
+
     # ---- Bark scale (host precompute helpers, psychoacoustic.py:333-339) ------------------------------
     def freq2bark(self, frequencies):
         """Empirical Bark scale (``:333-335``)."""

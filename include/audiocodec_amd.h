@@ -44,7 +44,9 @@ extern "C" {
 #define AC_API __attribute__((visibility("default")))
 #endif
 
-#define AC_VERSION 171 /* 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
+#define AC_VERSION 171 /* 0.1.8 + the quantiser (int16 codes, int8 per-band scale factors: ac_quantize, ac_dequantize,
+                          * ac_decode_quantized[_launches], ac_psy_scale_bands_host; additions only, so the number stays).
+                          * 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
                           * with a 5-smooth half up to 8192, float32); masking model for general band layouts up to 4096 bins.
                           * 0.1.7: only the ac_* entry points are exported; ac_stream_settle (home buffers for the streaming state);
                           * float32 precompute (ac_*_create_pre, ac_*_host_pre); fused encode at filters_n 64 ... 512; ac_workspace_*.
@@ -107,6 +109,11 @@ AC_API int ac_mdct_fold_coefficients_host_pre(int N, int window, int precompute,
 AC_API int ac_mdct_dense_matrices_host_pre(int N, int window, int precompute, float* H, float* H_inv);
 AC_API int ac_psy_tables_host_pre(int N, int M, double sample_rate, double alpha, int precompute,
                                   double* W, double* W_inv, double* S, double* quiet, double* scalars);
+
+/* Scale-factor bands of the quantiser (extension, no counterpart in the reference): offsets[M+1] of contiguous bin ranges
+ * [offsets[j], offsets[j+1]).  Bin i belongs to band min(M-1, floor(bark(f_i) / w)), f_i = (i + 1/2) (sample_rate/2) / N,
+ * bark(f) = 6 asinh(f / 600), w = bark(sample_rate/2) / M, in float64.  Bands may be empty. */
+AC_API int ac_psy_scale_bands_host(double sample_rate, int filter_bands_n, int bark_bands_n, int32_t* offsets);
 
 /* ------------------------------------------------------------------------------------------
  * Plans (own the device copies of the constant tables).
@@ -231,6 +238,27 @@ AC_API int ac_mdct_forward_pcm16(const ac_mdct_plan* plan, const int16_t* x, flo
 AC_API int ac_mdct_inverse_pcm16(const ac_mdct_plan* plan, const float* X, int16_t* x, int B, int Kp, int C, void* stream);
 AC_API int ac_encode_fused_pcm16(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const int16_t* x, float* X, float* t,
                           float* thr, float drown, int B, int K, int C, void* stream);
+
+/* Perceptual quantiser (extension: the quantisation that add_noise, psychoacoustic.py:150-167, stands in for; float32,
+ * even filter_bands_n, any bark_bands_n and channel count).  With scale-factor bands as in ac_psy_scale_bands_host and
+ * step(s) = ldexp(fp32(2^((s&3)/4)), s>>2):
+ *   sf[b,f,j,c]   = the largest s in [-127, 127] with fp32(step(s) * fp32(sqrt 3)) <= min(thr over band j), else -127;
+ *                   0 for an empty band; -128 when an X or thr of the band is NaN / Inf;
+ *   codes[b,f,i,c] = clamp(rint(fp32(X * 2^-(s/4))), -32767, 32767) (0 in a band with sf = -128);
+ *   dequantised X = fp32(code * step(sf)) (NaN in a band with sf = -128): |error| <= thr / (2 sqrt 3) (1 + 1e-6) + 1e-6 |X|.
+ * ac_quantize: X, thr [B,F,N,C] float32 -> codes int16 [B,F,N,C], sf int8 [B,F,M,C].  ac_dequantize: the inverse map.
+ * ac_decode_quantized: the synthesis (ac_mdct_inverse, or ac_mdct_inverse_pcm16 when pcm16 is given instead of x) of the
+ *   dequantised spectra, codes [B,Kp,N,C] -> x [B,(Kp+1)*N,C]; bit-equal to ac_dequantize followed by the inverse.
+ *   scratch [B,Kp,N,C] float32 receives the dequantised spectra where ac_decode_quantized_launches returns 2 and may be
+ *   NULL where it returns 1 (filters_n 1024 / 2048 on the wave-level kernels, mono / stereo: one launch that dequantises in
+ *   its loads).  mdct and psy must share filters_n and device. */
+AC_API int ac_quantize(const ac_psy_plan* psy, const float* X, const float* thr, int16_t* codes, int8_t* sf, int B, int F,
+                       int C, void* stream);
+AC_API int ac_dequantize(const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, float* X, int B, int F, int C,
+                         void* stream);
+AC_API int ac_decode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf,
+                               float* x, int16_t* pcm16, float* scratch, int B, int Kp, int C, void* stream);
+AC_API int ac_decode_quantized_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C);
 
 /* ------------------------------------------------------------------------------------------
  * Streaming overlap-add (chunked transform with device-resident state).

@@ -1,0 +1,68 @@
+"""Quantiser at the bench workload (B = 256 clips, stereo, K = 468 blocks, filters_n 1024): quantize, the fused synthesis
+from codes (float32 and 16-bit PCM out) and decode() -- all allocating their results -- on the same process's tensors, timed
+with HIP events; decode_into() (a caller-owned output) for reference.
+python tools/quant_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5]"""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import audiocodec_amd  # noqa: E402
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--clips", type=int, default=256)
+    ap.add_argument("--blocks", type=int, default=468)
+    ap.add_argument("--filters", type=int, default=1024)
+    ap.add_argument("--channels", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    a = ap.parse_args()
+    B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    codec = audiocodec_amd.AudioCodec(48000, N)
+    M = codec.psy.bark_bands_n
+    x = (torch.rand((B, K * N, C), device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * 2 - 1)
+    X, _, thr = codec.encode(x)
+    del x
+    codes, sf = codec.psy.quantize(X, thr)
+    F = K + 1
+    nbin = B * F * N * C
+    pcm_f32, pcm_i16 = B * (F + 1) * N * C * 4, B * (F + 1) * N * C * 2
+    code_b, sf_b = nbin * 2, B * F * M * C
+    out_f = torch.empty((B, (F + 1) * N, C), dtype=torch.float32, device="cuda")
+    print("quant_bench: B=%d K=%d N=%d C=%d M=%d  decode_quantized launches=%d  %s"
+          % (B, K, N, C, M, codec.decode_quantized_launches(C), torch.cuda.get_device_name()))
+    rows = [
+        ("quantize", lambda: codec.psy.quantize(X, thr), nbin * 8 + code_b + sf_b),
+        ("decode_quantized f32", lambda: codec.decode_quantized(codes, sf), code_b + sf_b + pcm_f32),
+        ("decode_quantized pcm16", lambda: codec.decode_quantized(codes, sf, pcm16=True), code_b + sf_b + pcm_i16),
+        ("decode f32", lambda: codec.decode(X), nbin * 4 + pcm_f32),
+        ("decode_into f32", lambda: codec.decode_into(X, out_f), nbin * 4 + pcm_f32),
+        ("dequantize", lambda: codec.psy.dequantize(codes, sf), code_b + sf_b + nbin * 4),
+    ]
+    res = {}
+    for name, fn, nbytes in rows:
+        ms = timed(fn, a.steps, a.warmup)
+        res[name] = ms
+        print("%-24s %8.3f ms  %6.3f GB  %6.2f TB/s" % (name, ms, nbytes / 1e9, nbytes / ms / 1e9))
+    print("decode_quantized f32 / decode f32 = %.3f" % (res["decode_quantized f32"] / res["decode f32"]))
+
+
+if __name__ == "__main__":
+    main()
