@@ -14,6 +14,8 @@ from conftest import rel_elem, rel_l2, rel_peak, tonality_err
 import audiocodec_amd
 from audiocodec_amd import _lib
 from oracle.audiocodec_oracle import MDCTOracle, PsychoOracle, sine_wav
+from psy_torch_reference import torch_psy_reference as _torch_psy_reference
+from psy_torch_reference import torch_tonality_reference as _torch_tonality_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -1564,38 +1566,6 @@ def test_tensors_beyond_4_gib():
     xh = codec.decode(X)
     assert float((xh[-1:, N:-N] - x[-1:]).abs().max()) <= LSB
     assert torch.equal(codec.decode(X[1199:].contiguous()), xh[1199:])
-
-
-def _torch_psy_reference(p, X, t, drown):
-    """The masking model in float64 torch ops (test infrastructure: lets torch.autograd produce reference gradients)."""
-    W = p.W.double().cuda()
-    Wi = p.W_inv.double().cuda()
-    S = p.spreading_matrix.double().cuda()
-    quiet = p.quiet_threshold_intensity.double().cuda()
-    alpha, M = float(p.alpha), p.bark_bands_n
-    eps = 1e-14
-    I = X ** 2
-    P = torch.einsum("nbic,ij->nbjc", I, W)
-    Q = torch.clamp(P, min=eps) ** alpha
-    A = torch.einsum("nbic,ij->nbjc", Q, S)
-    # (the reference evaluates linspace in compute_dtype, psychoacoustic.py:187-189: float32 unless the model is float64)
-    bdt = torch.float64 if p.compute_dtype == torch.float64 else torch.float32
-    beta = torch.linspace(0.0, float(p.max_bark), M, dtype=bdt).double().cuda().reshape(1, 1, M, 1)
-    O = (1.0 - drown) * (t * beta + 9.0 * t + 5.5)
-    fac = 10.0 ** (-alpha * O / 10.0)
-    T = torch.clamp(fac * A, min=eps) ** (1.0 / alpha)
-    G = torch.maximum(T, quiet)
-    E = torch.einsum("nbjc,jf->nbfc", G, Wi)
-    return torch.sqrt(torch.clamp(E, min=eps))
-
-
-def _torch_tonality_reference(X):
-    eps = 1e-14
-    I = X ** 2
-    N = X.shape[2]
-    sfm = 10.0 * (torch.log(torch.clamp(I, min=eps)).mean(dim=2, keepdim=True)
-                  - torch.log(I.mean(dim=2, keepdim=True) + eps)) / np.log(10.0)
-    return torch.clamp(sfm / -60.0, max=1.0)
 
 
 @pytest.mark.parametrize("sr,N,M,C,drown", [(48000, 1024, 64, 2, 0.0), (44100, 256, 48, 1, 0.3), (48000, 2048, 64, 3, 0.0)])

@@ -1,0 +1,398 @@
+"""GPU (MI355X): the adjoint kernels of the masking model -- k_psy_bwd_fast (ac_fast.hip: float32, filter_bands_n 1024 /
+2048, 64 bands) and k_tonality_bwd_generic / k_threshold_bwd_generic (ac_generic.hip: every other plan and dtype) --
+against torch.autograd on the float64 restatement (tests/psy_torch_reference.py), evaluated at the very inputs the kernels
+saw, on every path the kernels take: the channel modes and row widths of the fast kernel with a half-filled last pair,
+partial and chip-filling grids, more than 64 bands, the spreading matrix from global memory, the accumulate form of the C
+ABI, the kinks of the chain, and the size limits.
+
+Bars (err = max|g - g_ref| / max|g_ref| and rel-L2 = ||g - g_ref|| / ||g_ref||, over the whole tensor).  The worst
+values measured on the MI355X over every case of this module:
+  * fast (float32, k_psy_bwd_fast):              peak 1.5e-6, rel-L2 6.7e-7
+  * generic (float32, the generic kernels):      peak 1.1e-6, rel-L2 5.0e-7
+  * float64 (the generic kernels in double):     peak 1.2e-15, rel-L2 4.0e-16
+  * bfloat16 (bfloat16 tensors, float32 inside): peak 2.9e-3, rel-L2 1.7e-3
+Each bar is about 4x the worst value of its path (never looser than the bars of test_gpu_parity.py's autograd tests).  Every
+parametrised case also shows its bar is not vacuous: it rejects the reference gradient recomputed at drown + 0.05 and the
+reference gradient with one band's column of the spreading matrix zeroed.
+"""
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import rel_elem, tonality_err
+from psy_torch_reference import torch_masking_intensity, torch_psy_reference, torch_tonality_reference
+
+import audiocodec_amd
+from audiocodec_amd import _host, _lib
+from oracle.audiocodec_oracle import PsychoOracle
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-4          # forward parity bars of test_gpu_parity.py
+# (peak, rel-L2) per path; see the module docstring for the measured worst values
+BARS = {"fast": (6e-6, 2.5e-6), "generic": (4e-6, 2e-6), "float64": (5e-15, 1.6e-15), "bfloat16": (1.2e-2, 6.7e-3)}
+WORST = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _require_gpu():
+    assert torch.cuda.is_available(), "these tests need the MI355X (run with -m gpu on the GPU box)"
+    assert _lib.load().ac_set_force_generic(0) == 0, "AC_TESTING=1 not in effect"
+    yield
+    _lib.load().ac_set_force_generic(0)
+    if WORST:
+        print("\nworst gradient errors (peak, rel-L2) per path:")
+        for k in sorted(WORST):
+            print("  %-9s %.2e  %.2e" % (k, *WORST[k]))
+
+
+class _forced_generic:
+    """ac_set_force_generic(1) for the block: the generic kernels serve every call, forward and backward."""
+
+    def __init__(self, on=True):
+        self.on = on
+
+    def __enter__(self):
+        if self.on:
+            assert _lib.load().ac_set_force_generic(1) == 0
+
+    def __exit__(self, *exc):
+        _lib.load().ac_set_force_generic(0)
+
+
+def _errs(g, ref):
+    g, ref = g.detach().double(), ref.detach().double()
+    d = g - ref
+    peak = float(d.abs().max() / ref.abs().max())
+    l2 = float(torch.linalg.vector_norm(d) / torch.linalg.vector_norm(ref))
+    return peak, l2
+
+
+def _within(g, ref, path):
+    peak, l2 = _errs(g, ref)
+    return peak <= BARS[path][0] and l2 <= BARS[path][1]
+
+
+def _check(g, ref, path, guards=()):
+    """g within the bar of `path` of ref; every gradient of `guards` (a wrong reference) outside it."""
+    ref = ref.detach().double()
+    assert bool(torch.isfinite(g).all())
+    if float(ref.abs().max()) == 0.0:
+        assert float(g.abs().max()) == 0.0
+        return
+    peak, l2 = _errs(g, ref)
+    w = WORST.get(path, (0.0, 0.0))
+    WORST[path] = (max(w[0], peak), max(w[1], l2))
+    assert peak <= BARS[path][0] and l2 <= BARS[path][1], (path, peak, l2)
+    for bad in guards:
+        assert not _within(bad, ref, path), "the bar of %s does not reject a wrong reference" % path
+
+
+def _draw(B, F, N, C, g, dtype):
+    """A spectrum with a rising envelope, every |X| >= 1e-6 (no bin near the I > eps clamp)."""
+    env = torch.logspace(-3, 0, N, device="cuda", dtype=torch.float64).reshape(1, 1, N, 1)
+    u = torch.rand(B, F, N, C, device="cuda", generator=g, dtype=torch.float64)
+    s = torch.where(torch.rand(B, F, N, C, device="cuda", generator=g) < 0.5, -1.0, 1.0).double()
+    return (s * (0.999 * u + 0.001) * env).to(dtype)
+
+
+def _ref_grads(p, X, t_kernel, w, drown, S=None, rounded_t=False):
+    """Reference gradients at the kernel's inputs: d/dX of sum(w thr(X, t(X))), and of sum(w thr(X, t)) w.r.t. X and t."""
+    Xd = X.detach().double().requires_grad_(True)
+    td = torch_tonality_reference(Xd)
+    if rounded_t:        # the threshold kernel saw the ROUNDED tonality; its gradient path is td's
+        td = td + (t_kernel.detach().double() - td).detach()
+    (torch_psy_reference(p, Xd, td, drown, S) * w.double()).sum().backward()
+    Xd2 = X.detach().double().requires_grad_(True)
+    td2 = t_kernel.detach().double().requires_grad_(True)
+    (torch_psy_reference(p, Xd2, td2, drown, S) * w.double()).sum().backward()
+    return Xd.grad, Xd2.grad, td2.grad
+
+
+def _band_column_zeroed(p, X, t, drown):
+    """The spreading matrix with the column of the band that rises furthest above its quiet threshold zeroed."""
+    T = torch_masking_intensity(p, X.detach().double(), t.detach().double(), drown)
+    j = int((T / p.quiet_threshold_intensity.double().to(T.device)).mean(dim=(0, 1, 3)).argmax())
+    S = p.spreading_matrix.clone()
+    S[:, j] = 0
+    return S
+
+
+def _check_backward(p, X, drown, path, gen, rounded_t=False):
+    """The composed chain thr(X, t(X)), the threshold alone (grad_X, grad_t) and the tonality alone, each against the
+    float64 reference, with the sensitivity guards on the first two."""
+    B, F, N, C = X.shape
+    Xa = X.detach().clone().requires_grad_(True)
+    w = (torch.rand(B, F, N, C, device="cuda", generator=gen, dtype=torch.float64) + 0.5).to(X.dtype)
+    wt = (torch.rand(B, F, 1, C, device="cuda", generator=gen, dtype=torch.float64) * 2 - 1).to(X.dtype)
+    with _forced_generic(path != "fast" and p.is_fast()):
+        t = p.tonality(Xa)
+        (p.global_masking_threshold(Xa, t, drown) * w).sum().backward()
+        X2 = X.detach().clone().requires_grad_(True)
+        t2 = t.detach().clone().requires_grad_(True)
+        (p.global_masking_threshold(X2, t2, drown) * w).sum().backward()
+        X3 = X.detach().clone().requires_grad_(True)
+        (p.tonality(X3) * wt).sum().backward()
+    assert Xa.grad.dtype == X.dtype and t2.grad.dtype == X.dtype
+    gX, gX2, gt2 = _ref_grads(p, X, t, w, drown, rounded_t=rounded_t)
+    bX, bX2, bt2 = _ref_grads(p, X, t, w, drown + 0.05, rounded_t=rounded_t)
+    zX, zX2, zt2 = _ref_grads(p, X, t, w, drown, S=_band_column_zeroed(p, X, t, drown), rounded_t=rounded_t)
+    _check(Xa.grad, gX, path, guards=(bX, zX))
+    _check(X2.grad, gX2, path, guards=(bX2, zX2))
+    if drown == 1.0:     # the offset term vanishes: no gradient reaches the tonality, exactly
+        assert float(t2.grad.abs().max()) == 0.0 and float(gt2.abs().max()) == 0.0
+    else:
+        _check(t2.grad, gt2, path, guards=(bt2, zt2))
+    Xd = X.detach().double().requires_grad_(True)
+    (torch_tonality_reference(Xd) * wt.double()).sum().backward()
+    _check(X3.grad, Xd.grad, path)
+
+
+# ---- B. the fast backward: every channel mode (CMODE 0 stereo / 1 strided pairs / 2 mono), both row widths (R 8 at
+# N 1024, R 16 at N 2048), half-filled last pairs (odd B C), grids whose last workgroup (4 waves) is partly empty ----------
+SHAPES = [(1, 3, 1), (3, 5, 1), (1, 4, 3), (3, 3, 3), (1, 2, 5), (2, 3, 2), (2, 5, 1)]
+FAST = [(N, sr, shape) for N in (1024, 2048) for sr, shapes in ((48000, SHAPES[0::2]), (44100, SHAPES[1::2]))
+        for shape in shapes]
+
+
+def _fast_id(N, sr, shape):
+    B, F, C = shape
+    cmode = 0 if C == 2 else 2 if C == 1 else 1
+    ntasks = (B if C == 2 else (B * C + 1) // 2) * F
+    return "N%d-R%d-cmode%d-B%dF%dC%d-%s-ntasks%d-sr%d" % (N, 8 if N == 1024 else 16, cmode, B, F, C,
+                                                          "odd" if B * C % 2 else "even", ntasks, sr)
+
+
+@pytest.mark.parametrize("case", range(len(FAST)), ids=[_fast_id(*c) for c in FAST])
+def test_fast_backward_every_mode_and_tail(case):
+    """k_psy_bwd_fast in each channel mode and row width, odd signal counts (the last pair holds one signal) and grids
+    with ntasks % 4 != 0, at drown 0 / 0.4 / 1 (at 1 grad_t is exactly 0); every other case also runs the generic
+    kernels (ac_set_force_generic) against the same reference."""
+    N, sr, (B, F, C) = FAST[case]
+    p = audiocodec_amd.PsychoacousticModel(sr, filter_bands_n=N, bark_bands_n=64)
+    assert p.is_fast()
+    g = torch.Generator(device="cuda").manual_seed(100 + case)
+    X = _draw(B, F, N, C, g, torch.float32)
+    for drown in (0.0, 0.4, 1.0):
+        _check_backward(p, X, drown, "fast", g)
+        if case % 2 == 0:
+            _check_backward(p, X, drown, "generic", g)
+
+
+def test_fast_backward_on_a_launch_that_fills_the_chip():
+    """B = 32, F = 48, C = 2 at N = 1024: 1536 tasks, 384 workgroups -- more than one per CU."""
+    p = audiocodec_amd.PsychoacousticModel(48000, filter_bands_n=1024, bark_bands_n=64)
+    assert p.is_fast()
+    g = torch.Generator(device="cuda").manual_seed(7)
+    X = _draw(32, 48, 1024, 2, g, torch.float32)
+    _check_backward(p, X, 0.4, "fast", g)
+
+
+# ---- C. the generic backward at general band layouts and more than 64 bands --------------------------------------------
+# (the threshold kernel's LDS holds 2N + 10M values, and the M x M spreading matrix when the sum stays within 64 KiB)
+GENERIC = [
+    (48000, 30, 8, 2, 2, 1, torch.float32), (16000, 240, 32, 2, 5, 1, torch.float32),
+    (48000, 120, 20, 2, 5, 7, torch.float32), (48000, 480, 64, 3, 3, 1, torch.float32),
+    (44100, 576, 48, 2, 3, 2, torch.float32), (48000, 960, 64, 2, 3, 3, torch.float32),
+    (48000, 1000, 64, 1, 3, 2, torch.float32), (48000, 1920, 64, 2, 3, 2, torch.float32),
+    (48000, 4096, 64, 1, 3, 2, torch.float32),
+    (48000, 1024, 100, 2, 3, 1, torch.float32),    # two band iterations, S in LDS
+    (48000, 1024, 128, 1, 3, 3, torch.float32),    # S from global memory
+    (48000, 512, 200, 2, 3, 2, torch.float32),     # S from global memory, four band iterations
+    (48000, 2048, 256, 1, 2, 1, torch.float32),
+    (48000, 2048, 64, 2, 3, 1, torch.float64),     # S from global memory in double
+    (48000, 960, 64, 2, 3, 3, torch.bfloat16),
+]
+
+
+def _generic_id(sr, N, M, B, F, C, dt):
+    return "%s-sr%d-N%d-M%d-B%dF%dC%d" % (str(dt).split(".")[-1], sr, N, M, B, F, C)
+
+
+@pytest.mark.parametrize("case", range(len(GENERIC)), ids=[_generic_id(*c) for c in GENERIC])
+def test_generic_backward_at_general_layouts(case):
+    """Forward against the float64 oracle (the first forward test above 64 bands), then the gradients of the generic
+    kernels against the reference."""
+    sr, N, M, B, F, C, dt = GENERIC[case]
+    p = audiocodec_amd.PsychoacousticModel(sr, filter_bands_n=N, bark_bands_n=M, compute_dtype=dt)
+    assert not p.is_fast() or dt != torch.float32      # (float64 / bfloat16 tensors: the generic kernels at every size)
+    g = torch.Generator(device="cuda").manual_seed(200 + case)
+    X = _draw(B, F, N, C, g, dt)
+    o = PsychoOracle(sr, N, M, compute_dtype=np.float64)
+    Xo = X.double().cpu().numpy()
+    t = p.tonality(X)
+    to = o.tonality(Xo)
+    drown = (0.0, 0.4, 1.0)[case % 3]
+    if dt == torch.bfloat16:
+        assert float((t.double().cpu() - torch.from_numpy(to)).abs().max()) <= 4e-3
+        thr = p.global_masking_threshold(X, t, drown)
+        assert rel_elem(thr.double().cpu().numpy(), o.global_masking_threshold(Xo, t.double().cpu().numpy(), drown)) <= 6e-3
+    elif dt == torch.float64:
+        assert float((t.cpu() - torch.from_numpy(to)).abs().max()) <= 1e-12
+        thr = p.global_masking_threshold(X, t, drown)
+        assert rel_elem(thr.cpu().numpy(), o.global_masking_threshold(Xo, to, drown)) <= 1e-10
+    else:
+        assert tonality_err(t, to) <= 1.0
+        thr = p.global_masking_threshold(X, torch.from_numpy(to.astype(np.float32)).cuda(), drown)
+        assert rel_elem(thr.cpu().numpy(), o.global_masking_threshold(Xo, to, drown)) <= TOL
+    path = {torch.float32: "generic", torch.float64: "float64", torch.bfloat16: "bfloat16"}[dt]
+    _check_backward(p, X, drown, path, g, rounded_t=(dt == torch.bfloat16))
+
+
+# ---- A (device half). gradcheck of the float64 kernels against finite differences ------------------------------------
+@pytest.mark.parametrize("sr,N,M", [(48000, 30, 8), (32768, 64, 64), (48000, 120, 20)])
+@pytest.mark.parametrize("C", [1, 3])
+def test_gradcheck_of_the_float64_kernels(sr, N, M, C):
+    """torch.autograd.gradcheck of tonality and of global_masking_threshold (X and t as inputs) of a float64 model: the
+    kernels against central differences, independently of the restatement.  |X| in [0.05, 1] and t in [0.1, 0.9] keep
+    every clamp of the chain far from its kink (checked below)."""
+    p = audiocodec_amd.PsychoacousticModel(sr, filter_bands_n=N, bark_bands_n=M, compute_dtype=torch.float64)
+    g = torch.Generator().manual_seed(1)
+    X = (torch.rand(1, 2, N, C, generator=g, dtype=torch.float64) * 0.95 + 0.05)
+    X = (X * torch.where(torch.rand(1, 2, N, C, generator=g) < 0.5, -1.0, 1.0).double()).cuda().requires_grad_(True)
+    t = (torch.rand(1, 2, 1, C, generator=g, dtype=torch.float64) * 0.8 + 0.1).cuda().requires_grad_(True)
+    # away from the kinks: the masking threshold is not within 10 % of the quiet threshold, tonality below 1
+    with torch.no_grad():
+        P = torch.einsum("nbic,ij->nbjc", X ** 2, p.W.cuda())
+        A = torch.einsum("nbic,ij->nbjc", P ** p.alpha, p.spreading_matrix.cuda())
+        beta = torch.linspace(0.0, float(p.max_bark), M, dtype=torch.float64, device="cuda").reshape(1, 1, M, 1)
+        T = (10.0 ** (-p.alpha * (t * beta + 9.0 * t + 5.5) / 10.0) * A) ** (1.0 / p.alpha)
+        assert float((T / p.quiet_threshold_intensity.cuda()).log().abs().min()) > 0.1
+        assert float(P.min()) > 1e-6 and float(p.tonality(X).max()) < 0.9
+    assert torch.autograd.gradcheck(lambda x: p.tonality(x), (X,))
+    for drown in (0.0, 0.4):
+        assert torch.autograd.gradcheck(lambda x, tt: p.global_masking_threshold(x, tt, drown), (X, t))
+
+
+# ---- D. the accumulate flag of ac_tonality_backward ---------------------------------------------------------------------
+@pytest.mark.parametrize("N,B,F,C,generic", [(1024, 3, 2, 1, False), (1024, 1, 3, 3, False), (1024, 3, 3, 3, True),
+                                             (960, 3, 2, 1, False), (960, 1, 3, 3, False)])
+def test_tonality_backward_accumulate(N, B, F, C, generic):
+    """ac_tonality_backward(accumulate = 1) on a prefilled grad_X equals prefill + the accumulate = 0 result within one ulp
+    of the sum (a fused multiply-add may round once less), and writes nothing past the B x F rows: a sentinel tail of the
+    buffer stays bit for bit (fast plan: k_psy_bwd_fast with odd B C; N 960 and the forced path: k_tonality_bwd_generic)."""
+    p = audiocodec_amd.PsychoacousticModel(48000, filter_bands_n=N, bark_bands_n=64)
+    assert p.is_fast() == (N == 1024)
+    lib = _lib.load()
+    g = torch.Generator(device="cuda").manual_seed(N + C)
+    X = _draw(B, F, N, C, g, torch.float32)
+    gt = torch.rand(B, F, 1, C, device="cuda", generator=g) * 2 - 1
+    n, tail = B * F * N * C, 2 * N * C
+    def run(buf, accumulate):
+        with _host.on_device(X.device), _forced_generic(generic):
+            _lib.check(lib.ac_tonality_backward(p._plan(X.device), _host.ptr(X), _host.ptr(gt), _host.ptr(buf),
+                                                accumulate, B, F, C, _host.stream_ptr(X.device)))
+        torch.cuda.synchronize()
+
+    sentinel = torch.full((tail,), 12345.678, device="cuda")
+    fresh = torch.cat([torch.full((n,), float("nan"), device="cuda"), sentinel])
+    run(fresh, 0)
+    assert bool(torch.isfinite(fresh[:n]).all()) and float(fresh[:n].abs().max()) > 0
+    # prefill values of magnitude above the fresh ones: no cancellation, so one fused rounding stays within an ulp of the sum
+    scale = 4 * float(fresh[:n].abs().max())
+    prefill = (torch.rand(n, device="cuda", generator=g) + 1) * scale * torch.where(
+        torch.rand(n, device="cuda", generator=g) < 0.5, -1.0, 1.0)
+    acc = torch.cat([prefill, sentinel])
+    run(acc, 1)
+    assert torch.equal(fresh[n:], sentinel) and torch.equal(acc[n:], sentinel)
+    s = prefill + fresh[:n]
+    ulp = torch.nextafter(s.abs(), torch.full_like(s, float("inf"))) - s.abs()
+    assert bool(((acc[:n] - s).abs() <= ulp).all())
+    # the fresh result is the Python entry point's (accumulate = 0) result
+    Xa = X.clone().requires_grad_(True)
+    with _forced_generic(generic):
+        (p.tonality(Xa) * gt).sum().backward()
+    assert torch.equal(Xa.grad.reshape(-1), fresh[:n])
+
+
+# ---- E. kinks of the chain give exact zeros ------------------------------------------------------------------------------
+@pytest.mark.parametrize("N,C,generic", [(1024, 1, False), (2048, 2, False), (1024, 3, True), (960, 1, False)])
+def test_kinks_give_exact_zeros(N, C, generic):
+    """Frame 0: one large bin over a floor near 1e-6 (tonality clamped at 1: its grad_X from tonality is 0).  Frame 1:
+    zeros (I <= eps and P <= eps everywhere).  Frame 2: amplitudes near 2.5e-7 with t = 1, so every band sits on the
+    quiet threshold (its grad_X and grad_t from the threshold are 0).  Frame 3: an ordinary frame.  Where the reference
+    gradient is exactly 0 the kernel's is exactly 0; the values stay clear of exact ties with eps or quiet."""
+    p = audiocodec_amd.PsychoacousticModel(48000, filter_bands_n=N, bark_bands_n=64)
+    path = "fast" if p.is_fast() and not generic else "generic"
+    g = torch.Generator(device="cuda").manual_seed(N + 10 * C)
+    B, F = 1, 4
+    X = _draw(B, F, N, C, g, torch.float64)
+    sgn = torch.where(torch.rand(N, C, device="cuda", generator=g) < 0.5, -1.0, 1.0).double()
+    X[0, 0] = 1e-6 * (1 + torch.rand(N, C, device="cuda", generator=g, dtype=torch.float64)) * sgn
+    X[0, 0, N // 3] = 0.9
+    X[0, 1] = 0.0
+    X[0, 2] = 2.5e-7 * (1 + 0.2 * torch.rand(N, C, device="cuda", generator=g, dtype=torch.float64)) * sgn
+    X = X.float()
+    w = torch.rand(B, F, N, C, device="cuda", generator=g) + 0.5
+    wt = torch.rand(B, F, 1, C, device="cuda", generator=g) + 0.5
+    X3 = X.clone().requires_grad_(True)
+    X2 = X.clone().requires_grad_(True)
+    with _forced_generic(generic):
+        t = p.tonality(X3)
+        (t * wt).sum().backward()
+        tin = t.detach().clone()
+        tin[0, 2] = 1.0
+        t2 = tin.clone().requires_grad_(True)
+        (p.global_masking_threshold(X2, t2, 0.2) * w).sum().backward()
+    assert float(t.detach()[0, 0].min()) == 1.0
+    Xd = X.double().requires_grad_(True)
+    (torch_tonality_reference(Xd) * wt.double()).sum().backward()
+    Xd2 = X.double().requires_grad_(True)
+    td2 = tin.double().requires_grad_(True)
+    (torch_psy_reference(p, Xd2, td2, 0.2) * w.double()).sum().backward()
+    # the construction: the reference gradients of the kink frames are exactly 0 ...
+    assert float(Xd.grad[0, :2].abs().max()) == 0.0
+    assert float(Xd2.grad[0, 1:3].abs().max()) == 0.0 and float(td2.grad[0, 1:3].abs().max()) == 0.0
+    # ... and so are the kernels', wherever the reference's are
+    for k, r in ((X3.grad, Xd.grad), (X2.grad, Xd2.grad), (t2.grad, td2.grad)):
+        assert bool(torch.isfinite(k).all()) and bool((k[r == 0] == 0).all())
+    _check(X3.grad[0, 2:], Xd.grad[0, 2:], path)
+    _check(X2.grad[0, 3], Xd2.grad[0, 3], path)
+    _check(t2.grad[0, 3], td2.grad[0, 3], path)
+
+
+# ---- F. the spreading form and the limits -------------------------------------------------------------------------------
+@pytest.mark.parametrize("N,C", [(1024, 2), (1024, 1), (2048, 3)])
+def test_threshold_backward_does_not_depend_on_the_spreading_form(N, C):
+    """The backward of the threshold alone is the exact float32 adjoint whatever form of the spreading product the plan's
+    forward runs: for the same X, t and upstream gradient, models built with spreading "bf16_mfma", "bf16x2_mfma" and "f32"
+    give the default model's grad_X and grad_t bit for bit."""
+    g = torch.Generator(device="cuda").manual_seed(N + C)
+    X = _draw(2, 3, N, C, g, torch.float32)
+    w = torch.rand(2, 3, N, C, device="cuda", generator=g) + 0.5
+    base = audiocodec_amd.PsychoacousticModel(48000, filter_bands_n=N)
+    t = base.tonality(X)
+    grads = []
+    for spreading in (None, "bf16_mfma", "bf16x2_mfma", "f32"):
+        p = audiocodec_amd.PsychoacousticModel(48000, filter_bands_n=N, spreading=spreading)
+        assert spreading is None or p.plan_spreading() == spreading
+        Xa = X.clone().requires_grad_(True)
+        ta = t.clone().requires_grad_(True)
+        (p.global_masking_threshold(Xa, ta, 0.3) * w).sum().backward()
+        grads.append((Xa.grad, ta.grad))
+    for gX, gt in grads[1:]:
+        assert torch.equal(gX, grads[0][0]) and torch.equal(gt, grads[0][1])
+
+
+@pytest.mark.parametrize("N,M,dt", [(8192, 64, torch.float32), (4096, 64, torch.float64), (1024, 4096, torch.float32)])
+def test_backward_refuses_plans_beyond_its_lds(N, M, dt):
+    """The threshold backward holds 2N + 10M values in LDS (64 KiB): float32 N = 8192, float64 N = 4096 and N 1024 with
+    4096 bands are refused with a ValueError naming both sizes; the forward works at these sizes, and a forward call right
+    after the refusal still succeeds (and matches the oracle)."""
+    p = audiocodec_amd.PsychoacousticModel(48000, filter_bands_n=N, bark_bands_n=M, compute_dtype=dt)
+    g = torch.Generator(device="cuda").manual_seed(N + M)
+    X = _draw(1, 2, N, 1, g, dt)
+    t = p.tonality(X)
+    Xa = X.clone().requires_grad_(True)
+    thr = p.global_masking_threshold(Xa, t, 0.0)
+    with pytest.raises(ValueError, match="filter_bands_n = %d / bark_bands_n = %d" % (N, M)):
+        thr.sum().backward()
+    thr2 = p.global_masking_threshold(X, t, 0.0)
+    torch.cuda.synchronize()
+    assert torch.equal(thr2, thr.detach())
+    o = PsychoOracle(48000, N, M, compute_dtype=np.float64)
+    Xo = X.double().cpu().numpy()
+    to = o.tonality(Xo)
+    assert tonality_err(t, to) <= 1.0
+    assert rel_elem(thr2.double().cpu().numpy(), o.global_masking_threshold(Xo, t.double().cpu().numpy(), 0.0)) <= TOL
