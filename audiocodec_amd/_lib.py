@@ -106,6 +106,10 @@ PROTOTYPES = {
     "ac_decode_quantized": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                     c_void_p]),
     "ac_decode_quantized_launches": (c_int, [c_void_p, c_void_p, c_int]),
+    "ac_pack_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ac_pack_index": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "ac_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "ac_unpack": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -216,6 +216,21 @@ class AudioCodec:
                 _host.ptr(scratch) if scratch is not None else None, B, Kp, C, _host.stream_ptr(dev)))
         return x
 
+    def encode_packed(self, x, drown=0.0):
+        """:meth:`encode_quantized`, then :meth:`PsychoacousticModel.pack`: x [B, K*N, C] -> (data uint8 [nbytes],
+        index int64 [B, K+1, C]) (DESIGN.md section 8b).  Synchronises with the device (``pack`` reads the byte count);
+        float32 only, not differentiable."""
+        codes, sf = self.encode_quantized(x, drown)
+        return self.psy.pack(codes, sf)
+
+    def decode_packed(self, data, index, pcm16=False):
+        """:meth:`PsychoacousticModel.unpack`, then :meth:`decode_quantized`: data uint8 [nbytes], index int64
+        [B, K', C] -> x [B, (K'+1)*N, C] (``torch.int16`` with ``pcm16=True``); bit-equal to ``decode_quantized`` on the
+        codes that were packed.  float32 only."""
+        _host.require_float32(self.compute_dtype, "decode_packed")
+        codes, sf = self.psy.unpack(data, index)
+        return self.decode_quantized(codes, sf, pcm16)
+
     def decode_into(self, X, x):
         """:meth:`decode` into a caller-owned PCM tensor ``x [B, (K'+1)*N, C]`` (``torch.int16`` selects 16-bit PCM);
         same exactness rules as :meth:`encode_into`."""

@@ -1035,6 +1035,54 @@ int ac_decode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const 
   return mdct_inverse(mdct, scratch, out, pcm16 != nullptr, B, Kp, C, stream);
 }
 
+// ---- packed bitstream (ac_pack.hip) ----------------------------------------
+
+size_t ac_pack_scratch_bytes(int B, int F, int C) {
+  if (B <= 0 || F <= 0 || C <= 0) return 0;
+  return pack_scratch_bytes((long long)B * F * C);
+}
+
+int ac_pack_index(const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, int64_t* index, int64_t* total, void* scratch,
+                  int B, int F, int C, void* stream) {
+  int st = check_quant(psy, B, F, C);
+  if (st) return st;
+  AC_REQUIRE(total != nullptr, "total is NULL");
+  DeviceGuard guard(psy->device);
+  if (B == 0 || F == 0 || C == 0) {
+    AC_HIP_CHECK(hipMemsetAsync(total, 0, sizeof(int64_t), (hipStream_t)stream));
+    return AC_OK;
+  }
+  AC_REQUIRE(codes != nullptr && sf != nullptr && index != nullptr, "NULL tensor pointer");
+  AC_REQUIRE(scratch != nullptr || ac_pack_scratch_bytes(B, F, C) == 0,
+             "scratch of ac_pack_scratch_bytes() = %zu bytes is required", ac_pack_scratch_bytes(B, F, C));
+  AC_REQUIRE_ALIGNED(codes, sf, index, total, scratch);
+  return launch_pack_index(psy, codes, sf, index, total, scratch, B, F, C, (hipStream_t)stream);
+}
+
+int ac_pack(const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, const int64_t* index, uint8_t* data, int B, int F,
+            int C, void* stream) {
+  int st = check_quant(psy, B, F, C);
+  if (st) return st;
+  if (B == 0 || F == 0 || C == 0) return AC_OK;
+  AC_REQUIRE(codes != nullptr && sf != nullptr && index != nullptr && data != nullptr, "NULL tensor pointer");
+  AC_REQUIRE_ALIGNED(codes, sf, index, data);
+  DeviceGuard guard(psy->device);
+  return launch_pack(psy, codes, sf, index, data, B, F, C, (hipStream_t)stream);
+}
+
+int ac_unpack(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes, const int64_t* index, int16_t* codes, int8_t* sf,
+              int B, int F, int C, void* stream) {
+  int st = check_quant(psy, B, F, C);
+  if (st) return st;
+  AC_REQUIRE(nbytes >= 0, "negative nbytes (%lld)", (long long)nbytes);
+  if (B == 0 || F == 0 || C == 0) return AC_OK;
+  AC_REQUIRE(index != nullptr && codes != nullptr && sf != nullptr, "NULL tensor pointer");
+  AC_REQUIRE(data != nullptr || nbytes == 0, "data is NULL");
+  AC_REQUIRE_ALIGNED(data, index, codes, sf);
+  DeviceGuard guard(psy->device);
+  return launch_unpack(psy, data, nbytes, index, codes, sf, B, F, C, (hipStream_t)stream);
+}
+
 // ---- buffer placement probe ---------------------------------------------------------------------
 int ac_probe_placement(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, float* X, float* t,
                        float* const* thr_candidates, int n_candidates, int B, int K, int C, void* stream, int* best,

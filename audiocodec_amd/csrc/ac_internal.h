@@ -304,5 +304,13 @@ int launch_add_noise(const float* X, const float* thr, float* out, size_t n, uin
 int launch_quantize(const ac_psy_plan* p, const float* X, const float* thr, int16_t* codes, int8_t* sf, int B, int F, int C,
                     hipStream_t s);
 int launch_dequantize(const ac_psy_plan* p, const int16_t* codes, const int8_t* sf, float* X, int B, int F, int C, hipStream_t s);
+// packed bitstream (ac_pack.hip): codes, sf -> index [B,F,C] (row byte offsets) + total, data; and back
+size_t pack_scratch_bytes(long long rows);
+int launch_pack_index(const ac_psy_plan* p, const int16_t* codes, const int8_t* sf, int64_t* index, int64_t* total,
+                      void* scratch, int B, int F, int C, hipStream_t s);
+int launch_pack(const ac_psy_plan* p, const int16_t* codes, const int8_t* sf, const int64_t* index, uint8_t* data, int B,
+                int F, int C, hipStream_t s);
+int launch_unpack(const ac_psy_plan* p, const uint8_t* data, int64_t nbytes, const int64_t* index, int16_t* codes, int8_t* sf,
+                  int B, int F, int C, hipStream_t s);
 
 }  // namespace ac

@@ -311,7 +311,7 @@ class PsychoacousticModel:
                                                      off.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
         return off
 
-    def _check_quant_tensor(self, t, name, dtype, shape=None, device=None):
+    def _check_quant_tensor(self, t, name, dtype, shape=None, device=None, ndim=4):
         if not isinstance(t, torch.Tensor):
             raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
         if t.requires_grad and torch.is_grad_enabled():
@@ -319,8 +319,8 @@ class PsychoacousticModel:
                              "differentiable stand-in" % name)
         if t.dtype != dtype:
             raise ValueError("%s has dtype %s, expected %s" % (name, t.dtype, dtype))
-        if t.dim() != 4:
-            raise ValueError("%s must have 4 dimensions, got shape %s" % (name, tuple(t.shape)))
+        if t.dim() != ndim:
+            raise ValueError("%s must have %d dimensions, got shape %s" % (name, ndim, tuple(t.shape)))
         if shape is not None and tuple(t.shape) != tuple(shape):
             raise ValueError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
         if not t.is_cuda:
@@ -370,6 +370,50 @@ class PsychoacousticModel:
             _lib.check(self._lib.ac_dequantize(self._plans.get(codes.device), _host.ptr(codes), _host.ptr(sf), _host.ptr(X),
                                                B, F, C, _host.stream_ptr(codes.device)))
         return X
+
+    # ---- packed bitstream of quantised spectra (extension) ------------------------
+    def pack(self, codes, sf):
+        """Packs :meth:`quantize` output into a bitstream: codes int16 [B, F, N, C], sf int8 [B, F, M, C] ->
+        (data uint8 [nbytes], index int64 [B, F, C]).
+
+        Every (clip, frame, channel) row stores each scale-factor band at the bit width its largest zigzag code needs
+        (DESIGN.md section 8b has the format); ``index`` holds each row's byte offset in ``data``.  Any int16 code and
+        int8 sf is accepted.  Three launches around one device-to-host read of the byte count: the call synchronises
+        with the device and cannot be captured in a graph.  float32 plans only."""
+        _host.require_float32(self.compute_dtype, "the quantiser")
+        codes, sf = self._check_codes(codes, sf)
+        B, F, N, C = codes.shape
+        dev = codes.device
+        index = torch.empty((B, F, C), dtype=torch.int64, device=dev)
+        total = torch.empty((1,), dtype=torch.int64, device=dev)
+        nscratch = int(self._lib.ac_pack_scratch_bytes(B, F, C))
+        scratch = torch.empty((nscratch,), dtype=torch.uint8, device=dev) if nscratch else None
+        plan = self._plans.get(dev)
+        with _host.on_device(dev):
+            _lib.check(self._lib.ac_pack_index(plan, _host.ptr(codes), _host.ptr(sf), _host.ptr(index), _host.ptr(total),
+                                               _host.ptr(scratch) if scratch is not None else None, B, F, C,
+                                               _host.stream_ptr(dev)))
+            data = torch.empty((int(total.item()),), dtype=torch.uint8, device=dev)
+            _lib.check(self._lib.ac_pack(plan, _host.ptr(codes), _host.ptr(sf), _host.ptr(index), _host.ptr(data), B, F, C,
+                                         _host.stream_ptr(dev)))
+        return data, index
+
+    def unpack(self, data, index):
+        """Inverse of :meth:`pack`: data uint8 [nbytes], index int64 [B', F', C] -> (codes int16 [B', F', N, C],
+        sf int8 [B', F', M, C]) in canonical form -- codes 0 in bands with sf = -128, sf 0 in bands whose codes are all 0
+        (:meth:`dequantize` gives the same values as on the packed input).  ``index`` may hold any row starts, e.g. a
+        slice of frames or channels in another order.  Bits past the end of ``data`` read as 0.  float32 plans only."""
+        _host.require_float32(self.compute_dtype, "the quantiser")
+        data = self._check_quant_tensor(data, "data", torch.uint8, ndim=1)
+        index = self._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
+        B, F, C = index.shape
+        dev = data.device
+        codes = torch.empty((B, F, self.filter_bands_n, C), dtype=torch.int16, device=dev)
+        sf = torch.empty((B, F, self.bark_bands_n, C), dtype=torch.int8, device=dev)
+        with _host.on_device(dev):
+            _lib.check(self._lib.ac_unpack(self._plans.get(dev), _host.ptr(data), data.numel(), _host.ptr(index),
+                                           _host.ptr(codes), _host.ptr(sf), B, F, C, _host.stream_ptr(dev)))
+        return codes, sf
 
     # ---- Bark scale (host precompute helpers, psychoacoustic.py:333-339) ------------------------------
     def freq2bark(self, frequencies):

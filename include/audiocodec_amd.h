@@ -45,7 +45,8 @@ extern "C" {
 #endif
 
 #define AC_VERSION 171 /* 0.1.8 + the quantiser (int16 codes, int8 per-band scale factors: ac_quantize, ac_dequantize,
-                          * ac_decode_quantized[_launches], ac_psy_scale_bands_host; additions only, so the number stays).
+                          * ac_decode_quantized[_launches], ac_psy_scale_bands_host) and its packed bitstream (ac_pack_index,
+                          * ac_pack, ac_unpack, ac_pack_scratch_bytes); additions only, so the number stays.
                           * 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
                           * with a 5-smooth half up to 8192, float32); masking model for general band layouts up to 4096 bins.
                           * 0.1.7: only the ac_* entry points are exported; ac_stream_settle (home buffers for the streaming state);
@@ -259,6 +260,28 @@ AC_API int ac_dequantize(const ac_psy_plan* psy, const int16_t* codes, const int
 AC_API int ac_decode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf,
                                float* x, int16_t* pcm16, float* scratch, int B, int Kp, int C, void* stream);
 AC_API int ac_decode_quantized_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C);
+
+/* Packed bitstream of quantised spectra (extension).  A row is one (b, f, c) of codes [B,F,N,C] and
+ * sf [B,F,M,C]; bit p of a row is bit p % 32 of its little-endian 32-bit word p / 32; fields are written LSB first:
+ *   1. widths: M fields of 5 bits, band j at bits [5j, 5j+5): 31 where sf = -128, else w_j = the bit length of the band's
+ *      largest zz(q) = (q << 1) ^ (q >> 15) on the 16 bits of the code (0 for an empty or all-zero band);
+ *   2. for every band with 1 <= w_j <= 16, in band order: its sf, 8 bits of two's complement;
+ *   3. for every such band, in band order: each bin's zz(q) in w_j bits, in bin order;
+ *   4. zero bits up to a multiple of 32.
+ * Rows follow one another in (b, f, c) order in data; index[b,f,c] int64 is a row's byte offset (a multiple of 4).
+ * ac_pack_index: the row lengths, scanned into index [B,F,C], and their sum into *total (device, one int64); scratch of
+ *   ac_pack_scratch_bytes(B, F, C) bytes (NULL where that is 0).  ac_pack: the rows into data [*total] at index.
+ * ac_unpack: data [nbytes] and index [B,F,C] (any row starts, e.g. a slice of frames) -> the canonical codes [B,F,N,C] and
+ *   sf [B,F,M,C]: codes 0 and sf -128 in a band of width 31, sf 0 in a band of width 0, the stored values elsewhere.  A
+ *   width of 17 .. 30 reads as 31; bits at or beyond nbytes (or before 0) read as 0: nothing outside data is loaded.
+ * float32 psychoacoustic plans with an even filter_bands_n, as the quantiser; an empty batch launches nothing. */
+AC_API size_t ac_pack_scratch_bytes(int B, int F, int C);
+AC_API int ac_pack_index(const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, int64_t* index, int64_t* total,
+                         void* scratch, int B, int F, int C, void* stream);
+AC_API int ac_pack(const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, const int64_t* index, uint8_t* data, int B,
+                   int F, int C, void* stream);
+AC_API int ac_unpack(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes, const int64_t* index, int16_t* codes,
+                     int8_t* sf, int B, int F, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Streaming overlap-add (chunked transform with device-resident state).

@@ -1,0 +1,100 @@
+"""Packed bitstream at the bench workload (B = 256 clips, stereo, K = 468 blocks, filters_n 1024, uniform input in [-1, 1]):
+pack_index + pack (the C ABI on caller-owned buffers, and psy.pack() with its read of the byte count), unpack, and
+decode_packed against decode_quantized, timed with HIP events.  Algorithmic bytes: codes + sf + packed bytes, each once (pack_index alone:
+codes + sf + the index; a decoder: its input + the PCM it writes).
+python tools/pack_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5]"""
+import argparse
+import ctypes
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import audiocodec_amd  # noqa: E402
+from audiocodec_amd import _lib  # noqa: E402
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--clips", type=int, default=256)
+    ap.add_argument("--blocks", type=int, default=468)
+    ap.add_argument("--filters", type=int, default=1024)
+    ap.add_argument("--channels", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    a = ap.parse_args()
+    B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    codec = audiocodec_amd.AudioCodec(48000, N)
+    psy, lib = codec.psy, _lib.load()
+    M = psy.bark_bands_n
+    x = (torch.rand((B, K * N, C), device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * 2 - 1)
+    codes, sf = codec.encode_quantized(x)
+    del x
+    F = K + 1
+    data, index = psy.pack(codes, sf)
+    rows = B * F * C
+    samples = B * F * N * C
+    code_b, sf_b, pk_b, ix_b = codes.numel() * 2, sf.numel(), data.numel(), rows * 8
+    pcm_f32 = B * (F + 1) * N * C * 4
+    print("pack_bench: B=%d K=%d N=%d C=%d M=%d  rows=%d  decode_quantized launches=%d  %s"
+          % (B, K, N, C, M, rows, codec.decode_quantized_launches(C), torch.cuda.get_device_name()))
+    print("size: codes+sf %.1f MB -> packed %.1f MB (%.2fx smaller)  bits/sample %.3f (%.3f with the 8-byte index per row)"
+          % ((code_b + sf_b) / 1e6, pk_b / 1e6, (code_b + sf_b) / pk_b, 8.0 * pk_b / samples, 8.0 * (pk_b + ix_b) / samples))
+    print("widest code: %d" % int(codes.abs().max()))
+
+    plan, dev = psy._plan(codes.device), codes.device
+    p = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
+    s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    nscr = int(lib.ac_pack_scratch_bytes(B, F, C))
+    scratch = torch.empty((max(nscr, 1),), dtype=torch.uint8, device=dev)
+    index2, total = torch.empty_like(index), torch.empty((1,), dtype=torch.int64, device=dev)
+    data2 = torch.empty_like(data)
+
+    def pack_index():
+        _lib.check(lib.ac_pack_index(plan, p(codes), p(sf), p(index2), p(total), p(scratch) if nscr else None, B, F, C, s))
+
+    def pack_both():
+        pack_index()
+        _lib.check(lib.ac_pack(plan, p(codes), p(sf), p(index2), p(data2), B, F, C, s))
+
+    pack_both()
+    torch.cuda.synchronize()
+    assert torch.equal(index2, index) and torch.equal(data2, data) and int(total.item()) == pk_b
+    out_c, out_s = torch.empty_like(codes), torch.empty_like(sf)
+
+    def unpack_into():
+        _lib.check(lib.ac_unpack(plan, p(data), pk_b, p(index), p(out_c), p(out_s), B, F, C, s))
+
+    rows_t = [
+        ("pack_index", pack_index, code_b + sf_b + ix_b),
+        ("pack_index + pack", pack_both, code_b + sf_b + pk_b),
+        ("psy.pack (syncs)", lambda: psy.pack(codes, sf), code_b + sf_b + pk_b),
+        ("unpack (into)", unpack_into, pk_b + code_b + sf_b),
+        ("psy.unpack", lambda: psy.unpack(data, index), pk_b + code_b + sf_b),
+        ("decode_packed f32", lambda: codec.decode_packed(data, index), pk_b + ix_b + pcm_f32),
+        ("decode_quantized f32", lambda: codec.decode_quantized(codes, sf), code_b + sf_b + pcm_f32),
+    ]
+    res = {}
+    for name, fn, nbytes in rows_t:
+        ms = timed(fn, a.steps, a.warmup)
+        res[name] = ms
+        print("%-24s %8.3f ms  %6.3f GB  %6.2f TB/s" % (name, ms, nbytes / 1e9, nbytes / ms / 1e9))
+    print("decode_packed / decode_quantized = %.3f" % (res["decode_packed f32"] / res["decode_quantized f32"]))
+
+
+if __name__ == "__main__":
+    main()
