@@ -17,12 +17,25 @@ import torch
 from . import _host, _lib, placement
 
 
+# 2-byte compute dtypes: float32 arithmetic inside, so their backward runs the float32 kernels (see _TransformFn)
+_TWO_BYTE = (torch.bfloat16, torch.float16)
+# the float64 synthesis kernel holds 2 N doubles of LDS per workgroup (64 KiB): inverse_transform and the backward of
+# transform stop here, while the float64 analysis (N doubles) serves 8192
+_F64_SYNTHESIS_MAX_N = 4096
+
+
 class _TransformFn(torch.autograd.Function):
     """Differentiable ``transform`` (the reference is differentiated by TensorFlow when it sits in a training graph).  The
     analysis bank T is linear and the DCT-IV symmetric, so T^T is the synthesis kernel run on the TRANSPOSED fold
     coefficients (``ac_mdct_plan_adjoint``): ``T^T g = inverse_transform_adjoint(g)[:, N:-N] / (4 N)``, one launch.  For
     Princen-Bradley windows computed in float64 the adjoint plan equals the plan (F^-1 = F^T); for the rectangular window
-    (``mdctransformer.py:209-229``: 2x2 blocks [[1, 1], [1, 0]]) and float32-precomputed constants it does not."""
+    (``mdctransformer.py:209-229``: 2x2 blocks [[1, 1], [1, 0]]) and float32-precomputed constants it does not.
+
+    bfloat16 / float16: the incoming gradient is up-cast, the float32 kernels run on the same adjoint plan and the factor
+    1 / (4 N) (4 N for ``_InverseFn``) is applied in float32 before the one cast back.  Stored unscaled, 4 N T^T g would
+    overflow float16 for incoming gradients near 1e3 at N = 1024, S^T g / (4 N) would fall into float16's subnormals near
+    1e-5, and a factor that is not a power of two would round the gradient twice.  The backward runs kernels autograd
+    cannot see, so it is not differentiable again (``once_differentiable``)."""
 
     @staticmethod
     def forward(ctx, x, mdct):
@@ -30,9 +43,12 @@ class _TransformFn(torch.autograd.Function):
         return mdct._transform(x)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, gX):
         m = ctx.mdct
         N = m.filters_n
+        if m.compute_dtype in _TWO_BYTE:   # float32 kernels and scale, one rounding to the storage type at the end
+            return (m._inverse(gX.float(), adjoint=True, f32=True)[:, N:-N] / (4.0 * N)).to(m.compute_dtype), None
         gx = m._inverse(gX.contiguous(), adjoint=True)[:, N:-N] / (4.0 * N)
         return gx, None
 
@@ -46,8 +62,11 @@ class _InverseFn(torch.autograd.Function):
         return mdct._inverse(X)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, gx):
         m = ctx.mdct
+        if m.compute_dtype in _TWO_BYTE:
+            return (m._transform(gx.float(), adjoint=True, f32=True)[:, 1:-1] * (4.0 * m.filters_n)).to(m.compute_dtype), None
         gX = m._transform(gx.contiguous(), adjoint=True)[:, 1:-1] * (4.0 * m.filters_n)
         return gX, None
 
@@ -65,7 +84,9 @@ class MDCTransformer:
                                  tensors, float32 arithmetic inside: the reference up-casts them inside its DCT-IV, ``:327-344``;
                                  float16 results beyond 65504 become infinity as a cast makes them).  ``transform`` and
                                  ``inverse_transform`` are differentiable in every one of them (the reference's op chain is,
-                                 ``:31-35``); streaming: float32, float64, bfloat16
+                                 ``:31-35``; a 2-byte gradient is a float32 result rounded once); streaming: float32,
+                                 float64, bfloat16.  float64 limit: ``inverse_transform`` and the backward of ``transform``
+                                 serve filters_n up to 4096 (ValueError above it), ``transform`` itself 8192
         :param precompute_dtype: arithmetic type the window / fold constants are computed in on the host before they are
                                  cast to float32 tables (``:14,31-35,58-59``): float64 (default) or float32 -- the latter
                                  rounds every constant and operation to float32 in the reference's order, the cancellation
@@ -145,11 +166,13 @@ class MDCTransformer:
         :return:  ``[batches_n, blocks_n + 1, filters_n, channels_n]`` amplitudes in ]-1, 1[
         """
         if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
-            return _TransformFn.apply(x, self)   # (every compute_dtype: the adjoint plan runs the same typed kernels)
+            return _TransformFn.apply(x, self)   # (every compute_dtype: the adjoint plan; a 2-byte model's through its float32 kernels)
         return self._transform(x)
 
-    def _transform(self, x, adjoint=False):
-        x = _host.check_device_tensor(x, "x", self.compute_dtype, 3)
+    def _transform(self, x, adjoint=False, f32=False):
+        # (f32: float32 tensors through the float32 kernels of this plan, for the backward of a 2-byte model)
+        dtype, dtype_id = (torch.float32, _host.MDCT_DTYPE_IDS[torch.float32]) if f32 else (self.compute_dtype, self._dtype_id)
+        x = _host.check_device_tensor(x, "x", dtype, 3)
         B, S, C = x.shape
         N = self.filters_n
         if S % N != 0:
@@ -158,7 +181,7 @@ class MDCTransformer:
         X = placement.empty(placement.REGION_SPECTRA, (B, K + 1, N, C), x.dtype, x.device)   # (see placement.py)
         with _host.on_device(x.device):
             _lib.check(self._lib.ac_mdct_forward_typed((self._adjoint_plans if adjoint else self._plans).get(x.device), _host.ptr(x), _host.ptr(X),
-                                                       self._dtype_id, B, K, C, _host.stream_ptr(x.device)))
+                                                       dtype_id, B, K, C, _host.stream_ptr(x.device)))
         return X
 
     # ---- synthesis -----------------------------------------------------------------------------------
@@ -172,15 +195,20 @@ class MDCTransformer:
             return _InverseFn.apply(mdct_amplitudes, self)
         return self._inverse(mdct_amplitudes)
 
-    def _inverse(self, mdct_amplitudes, adjoint=False):
-        X = _host.check_device_tensor(mdct_amplitudes, "mdct_amplitudes", self.compute_dtype, 4)
+    def _inverse(self, mdct_amplitudes, adjoint=False, f32=False):
+        dtype, dtype_id = (torch.float32, _host.MDCT_DTYPE_IDS[torch.float32]) if f32 else (self.compute_dtype, self._dtype_id)
+        X = _host.check_device_tensor(mdct_amplitudes, "mdct_amplitudes", dtype, 4)
         B, Kp, N, C = X.shape
         if N != self.filters_n:
             raise ValueError("axis 2 of mdct_amplitudes (%d) != filters_n (%d)" % (N, self.filters_n))
+        if dtype == torch.float64 and N > _F64_SYNTHESIS_MAX_N:
+            raise ValueError("filters_n = %d: float64 inverse_transform, and the backward of float64 transform, serve "
+                             "filters_n up to %d (the float64 synthesis kernel holds 2 filters_n doubles of LDS)"
+                             % (N, _F64_SYNTHESIS_MAX_N))
         x = placement.empty(placement.REGION_OTHER, (B, (Kp + 1) * N, C), X.dtype, X.device)
         with _host.on_device(X.device):
             _lib.check(self._lib.ac_mdct_inverse_typed((self._adjoint_plans if adjoint else self._plans).get(X.device), _host.ptr(X), _host.ptr(x),
-                                                       self._dtype_id, B, Kp, C, _host.stream_ptr(X.device)))
+                                                       dtype_id, B, Kp, C, _host.stream_ptr(X.device)))
         return x
 
     # native handle for the fused / streaming entry points

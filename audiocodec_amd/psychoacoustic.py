@@ -18,7 +18,9 @@ from . import _host, _lib, placement
 
 class _TonalityFn(torch.autograd.Function):
     """Differentiable ``tonality`` (the reference is differentiated by TensorFlow inside a training graph,
-    ``psychoacoustic.py:311``); the backward pass is the explicit adjoint kernel ``ac_tonality_backward``."""
+    ``psychoacoustic.py:311``); the backward pass is the explicit adjoint kernel ``ac_tonality_backward``.  Like every
+    backward here it runs kernels autograd cannot see, so it is marked ``once_differentiable``: a second-order backward
+    raises instead of silently dropping their part (the gradient of ``add_noise`` w.r.t. ``thr`` among them)."""
 
     @staticmethod
     def forward(ctx, X, model):
@@ -27,6 +29,7 @@ class _TonalityFn(torch.autograd.Function):
         return model._tonality(X)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, gt):
         (X,) = ctx.saved_tensors
         return ctx.model._tonality_backward(X, gt.contiguous()), None
@@ -42,6 +45,7 @@ class _ThresholdFn(torch.autograd.Function):
         return model._threshold(X, t, drown)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, gthr):
         X, t = ctx.saved_tensors
         gX, gt = ctx.model._threshold_backward(X, t, ctx.drown, gthr.contiguous())
@@ -59,6 +63,7 @@ class _AddNoiseFn(torch.autograd.Function):
         return model._add_noise(X, thr, seed)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         g = g.contiguous()
         gX = g if ctx.needs_input_grad[0] else None
@@ -77,6 +82,7 @@ class _DbFn(torch.autograd.Function):
         return model._elementwise_db(a, norm)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         (a,) = ctx.saved_tensors
         return ctx.model._db_backward(a, g.contiguous(), ctx.norm), None, None
