@@ -187,7 +187,12 @@ namespace ac {
 
 // generic O(N^2) kernels: any even N, any C, any M
 int lds_fft_tier_of(const ac_mdct_plan* p, int C);   // ac_generic.hip: 2 / 1 / 0, see ac_mdct_plan_tier
-// the 16-byte kernels of the LDS-FFT tier on mono rows (ac_wave_rows.hip)
+// the 16-byte kernels of the LDS-FFT tier (ac_wave_v.h) on stereo rows (ac_wave_stereo.hip) ...
+int launch_fwd_wave_stereo(const ac_mdct_plan* p, const float* x, float* X, const float* prev_block, int B, int Kin, int F,
+                           hipStream_t s);
+int launch_inv_wave_stereo(const ac_mdct_plan* p, const float* X, float* x, const float* tail_in, float* tail_out, int B, int Kp,
+                           int nblk, hipStream_t s);
+// ... on mono rows (ac_wave_mono.hip)
 int launch_fwd_wave_mono(const ac_mdct_plan* p, const float* x, float* X, const float* prev_block, int B, int Kin, int F,
                          hipStream_t s);
 int launch_inv_wave_mono(const ac_mdct_plan* p, const float* X, float* x, const float* tail_in, float* tail_out, int B, int Kp,
@@ -196,6 +201,8 @@ int launch_inv_wave_mono(const ac_mdct_plan* p, const float* X, float* x, const 
 bool lds_fft_serves_pcm16(const ac_mdct_plan* p, int C);
 int launch_fwd_lds_pcm16(const ac_mdct_plan* p, const int16_t* x, float* X, int B, int K, int C, hipStream_t s);
 int launch_inv_lds_pcm16(const ac_mdct_plan* p, const float* X, int16_t* x, int B, int Kp, int C, hipStream_t s);
+int launch_fwd_wave_stereo_pcm16(const ac_mdct_plan* p, const int16_t* x, float* X, int B, int Kin, int F, hipStream_t s);
+int launch_inv_wave_stereo_pcm16(const ac_mdct_plan* p, const float* X, int16_t* x, int B, int Kp, int nblk, hipStream_t s);
 int launch_fwd_wave_mono_pcm16(const ac_mdct_plan* p, const int16_t* x, float* X, int B, int Kin, int F, hipStream_t s);
 int launch_inv_wave_mono_pcm16(const ac_mdct_plan* p, const float* X, int16_t* x, int B, int Kp, int nblk, hipStream_t s);
 // the fused encode of the LDS-FFT tier (ac_wave_enc.hip): the 16-byte analysis kernels with the run-structured masking model
@@ -203,7 +210,9 @@ int launch_inv_wave_mono_pcm16(const ac_mdct_plan* p, const float* X, int16_t* x
 bool wave_encode_fuses(const ac_mdct_plan* p, const ac_psy_plan* psy, int C, const void* x, const void* X, const void* thr);
 int launch_enc_wave(const ac_mdct_plan* p, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr, float drown,
                     const float* prev_block, int B, int Kin, int F, int C, hipStream_t s);
-// ... and on channel pairs of any channel count / rows off the 16-byte grid (ac_wave_rows2.hip)
+// ... and on channel pairs of three or more channels: whole rows through LDS where the shape has that form (ac_wave_team.hip;
+// kTeamDeclined: it has not), the strided channel pairs elsewhere and on rows off the 16-byte grid (ac_wave_strided.hip)
+constexpr int kTeamDeclined = -12346;
 int launch_fwd_wave_team(const ac_mdct_plan* p, const float* x, float* X, const float* prev_block, int B, int Kin, int F, int C,
                          hipStream_t s);
 int launch_inv_wave_team(const ac_mdct_plan* p, const float* X, float* x, const float* tail_in, float* tail_out, int B, int Kp,

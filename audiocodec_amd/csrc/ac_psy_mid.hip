@@ -398,7 +398,7 @@ __global__ __launch_bounds__(256, (R >= 32 ? 1 : R >= 16 ? 2 : 3)) void k_psy_ru
   }
 }
 
-// ---- channel counts other than one and two with whole cache lines ("team" form, as k_fwd_wave_c of ac_generic.hip) ----------
+// ---- channel counts other than one and two with whole cache lines ("team" form, as k_fwd_wave_c of ac_wave_team.hip) -------
 // A workgroup = the CP = ceil(C / 2) waves that take the channel pairs of ONE frame.  The row [N, C] comes in and the threshold
 // row goes out in 16-byte pieces, consecutive lanes on consecutive addresses: wave w moves piece w (8 N bytes) between HBM and
 // its own slot, and every wave picks its pair's bins out of (puts its thresholds into) the row image that the CP slots hold

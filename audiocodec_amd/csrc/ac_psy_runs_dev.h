@@ -1,8 +1,8 @@
 // Device code of the wave-level masking model for general band layouts in its run-structured form (round 4): the model
 // of ac_psy_mid_dev.h with the structure every Bark mapping of the reference has (psychoacoustic.py:257-299) taken out of
 // the frame loop at plan time.  Shared by the stand-alone kernel (k_psy_runs, ac_psy_mid.hip), the fused encode of the
-// several-frames-per-wave MDCT kernels (k_fwd_multi, ac_fast.hip) and the fused encode of the LDS-FFT tier (k_fwd_wave_v,
-// ac_generic.hip): ONE definition of the per-frame arithmetic, so the fused and the un-fused encode agree bit for bit.
+// several-frames-per-wave MDCT kernels (k_fwd_multi, ac_fast.hip) and the fused encode of the LDS-FFT tier (k_enc_wave_v,
+// ac_wave_enc.hip): ONE definition of the per-frame arithmetic, so the fused and the un-fused encode agree bit for bit.
 //
 // What the structure is (checked by build_runs on the host; a plan that does not have it keeps the band walk):
 //   * W (bins -> bands, :301-315): the bins of band j are one contiguous run f0 .. f1; the interior bins f0+1 .. f1-1 carry

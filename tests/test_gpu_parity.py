@@ -185,7 +185,7 @@ def _smooth_half(N):
 
 
 # every filters_n the 16-byte kernels of the LDS-FFT tier serve (float32 stereo rows, filters_n % 4 == 0 up to 8192 with a
-# 5-smooth half, beside the powers of two of the wave-level kernels): one compile-time instance each (ac_generic.hip
+# 5-smooth half, beside the powers of two of the wave-level kernels): one compile-time instance each (ac_wave_v.h
 # AC_WAVE_CT_SIZES; a frame per group of lanes inside a wave up to 1024, per workgroup of two / four / eight waves and in
 # place above, up to 8192 -- 7500 has no plan of four passes and stays on the O(N^2) kernels); the reference takes any even filters_n (mdctransformer.py:26)
 WAVE16_SIZES = [N for N in range(16, 8193, 4) if _smooth_half(N) and N not in (64, 128, 256, 512, 1024, 2048, 7500)]
@@ -481,7 +481,7 @@ def test_codec_golden_beside_the_powers_of_two(golden, path, N):
 @pytest.mark.parametrize("N", [108, 120, 240, 480, 500, 576, 768, 960, 1000, 1080, 1536, 1920, 2304, 3240, 4096])
 @pytest.mark.parametrize("C", [2, 1])
 def test_fused_encode_of_the_lds_fft_tier_equals_the_unfused_calls(N, C, monkeypatch):
-    """k_enc_wave_v (ac_generic.hip): the LDS-FFT instances with the masking model in the same launch -- tonality and the band
+    """k_enc_wave_v (ac_wave_enc.hip): the LDS-FFT instances with the masking model in the same launch -- tonality and the band
     intensities frame by frame while the spectrum is in LDS, the rest four frames at a time after the strip -- against
     transform -> tonality -> global_masking_threshold (psychoacoustic.py:102-148 on mdctransformer.py:62-125): bit for bit (one
     definition of the arithmetic), every instance forced on (AC_LDS_WAVE_NOFUSE=2: the product fuses where it measured faster),
@@ -567,7 +567,7 @@ def test_fused_encode_at_launches_that_fill_the_chip(N, C, monkeypatch):
 @pytest.mark.parametrize("N", [64, 120, 128, 480, 500, 960, 1024, 1536, 2048, 4096])
 @pytest.mark.parametrize("C", [3, 4, 5, 6, 7])
 def test_more_than_two_channels_through_whole_rows_equals_the_strided_pairs(N, C, monkeypatch):
-    """k_fwd_wave_c / k_inv_wave_c (ac_generic.hip): the channel pairs of one signal as a team that moves whole [filters_n, C]
+    """k_fwd_wave_c / k_inv_wave_c (ac_wave_team.hip): the channel pairs of one signal as a team that moves whole [filters_n, C]
     rows between HBM and LDS in 16-byte pieces (mdctransformer.py:112, 289-297 takes any channels_n) -- forced on wherever the
     shape fits (AC_LDS_WAVE_NOTEAM=2; the product takes it where it measured faster) against the strided channel pairs
     (=1): bit for bit, one-shot and chunked (the stream state crosses the two forms), odd channel counts (a half-empty last

@@ -7,7 +7,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import audiocodec_amd
-src = open(os.path.join(ROOT, "audiocodec_amd", "csrc", "ac_generic.hip")).read()
+src = open(os.path.join(ROOT, "audiocodec_amd", "csrc", "ac_wave_v.h")).read()
 blk = src[src.index("#define AC_WAVE_CT_SIZES"):]
 blk = blk[:blk.index("#endif")]
 sizes = sorted({int(m.group(1)) for m in re.finditer(r"AC_WAVE_CT\((\d+),", blk)})
