@@ -10,7 +10,9 @@ and SURVEY.md section 0 item 3 defines them as thin compositions of the referenc
 from __future__ import annotations
 
 import ctypes
+import math
 
+import numpy as np
 import torch
 
 from . import _host, _lib, placement
@@ -222,6 +224,36 @@ class AudioCodec:
         float32 only, not differentiable."""
         codes, sf = self.encode_quantized(x, drown)
         return self.psy.pack(codes, sf)
+
+    # ---- rate control (extension; DESIGN.md section 8c) ---------------------------------------------------------
+    def row_bits_for_bitrate(self, bits_per_second):
+        """The per-channel row budget of a bitrate: floor(bits_per_second * filters_n / sample_rate) bits per frame and
+        channel (a frame advances filters_n samples).  Pass it to :meth:`encode_quantized_budget`."""
+        if isinstance(bits_per_second, bool) or not isinstance(bits_per_second, (int, float, np.integer, np.floating)):
+            raise TypeError("bits_per_second must be a number, got %s" % type(bits_per_second).__name__)
+        if not bits_per_second > 0:
+            raise ValueError("bits_per_second must be positive, got %r" % (bits_per_second,))
+        return int(math.floor(bits_per_second * self.filters_n / self.psy.sample_rate))
+
+    def encode_quantized_budget(self, x, row_bits, min_offset=0, drown=0.0):
+        """:meth:`encode`, then :meth:`PsychoacousticModel.quantize_to_budget` on its X and threshold: x [B, K*N, C] ->
+        (codes int16 [B, K+1, N, C], sf int8 [B, K+1, M, C], offset int16 [B, K+1, C], row_bits_out int32 [B, K+1, C]).
+        ``row_bits`` is an int (e.g. :meth:`row_bits_for_bitrate`) or an int32 tensor [B, K+1, C].  Two launches; float32
+        only, not differentiable."""
+        _host.require_float32(self.compute_dtype, "encode_quantized_budget")
+        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+            raise ValueError("x requires a gradient: quantisation is not differentiable -- use encode() and "
+                             "psy.add_noise(), its differentiable stand-in")
+        X, _, thr = self.encode(x, drown)
+        return self.psy.quantize_to_budget(X, thr, row_bits, min_offset)
+
+    def encode_packed_budget(self, x, row_bits, min_offset=0, drown=0.0):
+        """:meth:`encode_quantized_budget`, then :meth:`PsychoacousticModel.pack`: x [B, K*N, C] -> (data uint8 [nbytes],
+        index int64 [B, K+1, C], offset int16 [B, K+1, C]).  A row that met its budget R takes at most ceil(R / 32) * 4
+        bytes of ``data``; :meth:`decode_packed` reads the stream as it is.  Synchronises with the device; float32 only."""
+        codes, sf, offset, _ = self.encode_quantized_budget(x, row_bits, min_offset, drown)
+        data, index = self.psy.pack(codes, sf)
+        return data, index, offset
 
     def decode_packed(self, data, index, pcm16=False):
         """:meth:`PsychoacousticModel.unpack`, then :meth:`decode_quantized`: data uint8 [nbytes], index int64

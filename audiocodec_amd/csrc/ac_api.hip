@@ -1000,6 +1000,22 @@ int ac_dequantize(const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf
   return launch_dequantize(psy, codes, sf, X, B, F, C, (hipStream_t)stream);
 }
 
+int ac_quantize_budget(const ac_psy_plan* psy, const float* X, const float* thr, int row_bits, const int32_t* row_bits_per_row,
+                       int kmin, int16_t* codes, int8_t* sf, int16_t* offset, int32_t* row_bits_out, int B, int F, int C,
+                       void* stream) {
+  int st = check_quant(psy, B, F, C);
+  if (st) return st;
+  AC_REQUIRE(kmin >= -254 && kmin <= 254, "kmin (%d) outside [-254, 254]", kmin);
+  AC_REQUIRE(row_bits_per_row != nullptr || row_bits >= 5 * psy->M,
+             "row_bits (%d) below 5 * bark_bands_n = %d, the length of a row that stores no band", row_bits, 5 * psy->M);
+  if (B == 0 || F == 0 || C == 0) return AC_OK;
+  AC_REQUIRE(X != nullptr && thr != nullptr && codes != nullptr && sf != nullptr && offset != nullptr, "NULL tensor pointer");
+  AC_REQUIRE_ALIGNED(X, thr, codes, sf, offset, row_bits_per_row, row_bits_out);
+  DeviceGuard guard(psy->device);
+  return launch_quantize_budget(psy, X, thr, row_bits, row_bits_per_row, kmin, codes, sf, offset, row_bits_out, B, F, C,
+                                (hipStream_t)stream);
+}
+
 static bool decode_quantized_fuses(const ac_mdct_plan* mdct, int C) {
   return !g_force_generic && wave_level(mdct, C, 0, 1) && fast_inv_quant_serves(mdct, C);
 }

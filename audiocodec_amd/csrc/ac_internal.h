@@ -313,6 +313,11 @@ int launch_add_noise(const float* X, const float* thr, float* out, size_t n, uin
 int launch_quantize(const ac_psy_plan* p, const float* X, const float* thr, int16_t* codes, int8_t* sf, int B, int F, int C,
                     hipStream_t s);
 int launch_dequantize(const ac_psy_plan* p, const int16_t* codes, const int8_t* sf, float* X, int B, int F, int C, hipStream_t s);
+// rate control (ac_rate.hip): the quantiser at the smallest offset in [kmin, 254] whose packed row fits the row's budget
+// (row_budget [B,F,C] int32, or the scalar budget where it is NULL) -> codes, sf, offset int16 [B,F,C], row_bits (or NULL)
+int launch_quantize_budget(const ac_psy_plan* p, const float* X, const float* thr, int budget, const int32_t* row_budget,
+                           int kmin, int16_t* codes, int8_t* sf, int16_t* offset, int32_t* row_bits, int B, int F, int C,
+                           hipStream_t s);
 // packed bitstream (ac_pack.hip): codes, sf -> index [B,F,C] (row byte offsets) + total, data; and back
 size_t pack_scratch_bytes(long long rows);
 int launch_pack_index(const ac_psy_plan* p, const int16_t* codes, const int8_t* sf, int64_t* index, int64_t* total,

@@ -21,24 +21,6 @@ namespace {
 constexpr int kQuantThreads = 256;
 constexpr int kQuantLdsBytes = 32768;   // 8 bytes per (band, channel) slot of a workgroup: key + inverse step
 
-// float -> int key whose signed order is the float order (the map is its own inverse); NaN / Inf are flagged apart
-__device__ __forceinline__ int ordered_key(float v) {
-  const int u = __float_as_int(v);
-  return u >= 0 ? u : (u ^ 0x7fffffff);
-}
-__device__ __forceinline__ float key_value(int k) { return __int_as_float(k >= 0 ? k : (k ^ 0x7fffffff)); }
-
-// the largest s in [-127, 127] with fp32(step(s) * sqrt 3) <= m, else -127: a log2 estimate corrected against the criterion
-__device__ int scale_factor_of(float m) {
-  auto ok = [m](int s) { return qmul(quant_step(s), kQuantSqrt3) <= m; };
-  if (!(m > 0.f)) return -127;
-  int s = (int)floorf(4.f * log2f(m / kQuantSqrt3));
-  s = max(-127, min(127, s));
-  while (s < 127 && ok(s + 1)) ++s;
-  while (s > -127 && !ok(s)) --s;
-  return s;
-}
-
 // grid (B*F rows, channel groups); block: a multiple of 64 threads; CG channels per group (a group's slots fit the LDS)
 __global__ __launch_bounds__(kQuantThreads) void k_quantize(const float* __restrict__ X, const float* __restrict__ thr,
                                                            int16_t* __restrict__ codes, int8_t* __restrict__ sf,

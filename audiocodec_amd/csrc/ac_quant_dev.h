@@ -1,5 +1,6 @@
-// Device helpers of the quantiser shared by its kernels (ac_quant.hip) and the synthesis from codes (ac_fast.hip): one
-// definition, so that every path dequantises bit for bit alike.  DESIGN.md section 8a has the definition.
+// Device helpers of the quantiser shared by its kernels (ac_quant.hip, ac_rate.hip) and the synthesis from codes
+// (ac_fast.hip): one definition, so that every path quantises and dequantises bit for bit alike.  DESIGN.md section 8a has
+// the definition.
 #pragma once
 #include <cstdint>
 #include <hip/hip_runtime.h>
@@ -32,6 +33,24 @@ __device__ __forceinline__ float quant_inv_step(int s) { return __builtin_ldexpf
 __device__ __forceinline__ float dequant(int code, int sf) {
   const uint32_t st = sf == -128 ? 0x7fc00000u : quant_step_bits(sf);
   return qmul((float)code, __uint_as_float(st));
+}
+
+// float -> int key whose signed order is the float order (the map is its own inverse); NaN / Inf are flagged apart
+__device__ __forceinline__ int ordered_key(float v) {
+  const int u = __float_as_int(v);
+  return u >= 0 ? u : (u ^ 0x7fffffff);
+}
+__device__ __forceinline__ float key_value(int k) { return __int_as_float(k >= 0 ? k : (k ^ 0x7fffffff)); }
+
+// the largest s in [-127, 127] with fp32(step(s) * sqrt 3) <= m, else -127: a log2 estimate corrected against the criterion
+__device__ inline int scale_factor_of(float m) {
+  auto ok = [m](int s) { return qmul(quant_step(s), kQuantSqrt3) <= m; };
+  if (!(m > 0.f)) return -127;
+  int s = (int)floorf(4.f * log2f(m / kQuantSqrt3));
+  s = max(-127, min(127, s));
+  while (s < 127 && ok(s + 1)) ++s;
+  while (s > -127 && !ok(s)) --s;
+  return s;
 }
 
 }  // namespace ac

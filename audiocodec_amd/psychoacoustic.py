@@ -377,6 +377,52 @@ class PsychoacousticModel:
                                                B, F, C, _host.stream_ptr(codes.device)))
         return X
 
+    # ---- rate control (extension) ------------------------------------------------
+    def quantize_to_budget(self, mdct_amplitudes, masking_threshold, row_bits, min_offset=0):
+        """:meth:`quantize` with every scale factor of a (clip, frame, channel) row raised by one offset, the smallest in
+        ``[min_offset, 254]`` whose packed row (:meth:`pack`, before its padding to 32 bits) is at most ``row_bits`` long:
+        X, thr [B, F, N, C] float32 -> (codes int16 [B, F, N, C], sf int8 [B, F, M, C], offset int16 [B, F, C],
+        row_bits_out int32 [B, F, C]).
+
+        ``row_bits`` is an int (at least 5 * bark_bands_n, the length of a row that stores no band) or an int32 tensor
+        [B, F, C] of per-row budgets.  A row that cannot meet its budget gets offset 254 and ``row_bits_out`` above it.
+        Each unit of offset makes the row's steps 2^(1/4) coarser; scale factors stay in [-127, 127], empty bands keep 0 and
+        bands with NaN / Inf keep -128.  ``min_offset`` in [-254, 254]: 0 with an unlimited budget gives :meth:`quantize`,
+        a fixed budget of 16N + 13M and a fixed ``min_offset`` is a constant-quality mode.  One launch; not
+        differentiable; float32 only."""
+        _host.require_float32(self.compute_dtype, "the quantiser")
+        X = self._check_quant_tensor(mdct_amplitudes, "mdct_amplitudes", torch.float32)
+        B, F, N, C = X.shape
+        if N != self.filter_bands_n:
+            raise ValueError("axis 2 of mdct_amplitudes (%d) != filter_bands_n (%d)" % (N, self.filter_bands_n))
+        thr = self._check_quant_tensor(masking_threshold, "masking_threshold", torch.float32, X.shape, X.device)
+        if isinstance(min_offset, bool) or not isinstance(min_offset, (int, np.integer)):
+            raise TypeError("min_offset must be an int, got %s" % type(min_offset).__name__)
+        if not -254 <= int(min_offset) <= 254:
+            raise ValueError("min_offset (%d) outside [-254, 254]" % min_offset)
+        per_row = None
+        scalar = 0
+        if isinstance(row_bits, torch.Tensor):
+            per_row = self._check_quant_tensor(row_bits, "row_bits", torch.int32, (B, F, C), X.device, ndim=3)
+        elif isinstance(row_bits, (int, np.integer)) and not isinstance(row_bits, bool):
+            if not 5 * self.bark_bands_n <= int(row_bits) <= 2 ** 31 - 1:
+                raise ValueError("row_bits (%d) below 5 * bark_bands_n = %d, the length of a row that stores no band, or "
+                                 "above int32" % (row_bits, 5 * self.bark_bands_n))
+            scalar = int(row_bits)
+        else:
+            raise TypeError("row_bits must be an int or an int32 tensor [B, F, C], got %s" % type(row_bits).__name__)
+        dev = X.device
+        codes = torch.empty((B, F, N, C), dtype=torch.int16, device=dev)
+        sf = torch.empty((B, F, self.bark_bands_n, C), dtype=torch.int8, device=dev)
+        offset = torch.empty((B, F, C), dtype=torch.int16, device=dev)
+        bits = torch.empty((B, F, C), dtype=torch.int32, device=dev)
+        with _host.on_device(dev):
+            _lib.check(self._lib.ac_quantize_budget(
+                self._plans.get(dev), _host.ptr(X), _host.ptr(thr), scalar, _host.ptr(per_row) if per_row is not None else None,
+                int(min_offset), _host.ptr(codes), _host.ptr(sf), _host.ptr(offset), _host.ptr(bits), B, F, C,
+                _host.stream_ptr(dev)))
+        return codes, sf, offset, bits
+
     # ---- packed bitstream of quantised spectra (extension; DESIGN.md section 8b) ------------------------
     def pack(self, codes, sf):
         """Packs :meth:`quantize` output into a bitstream: codes int16 [B, F, N, C], sf int8 [B, F, M, C] ->

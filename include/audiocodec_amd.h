@@ -45,8 +45,9 @@ extern "C" {
 #endif
 
 #define AC_VERSION 171 /* 0.1.8 + the quantiser (int16 codes, int8 per-band scale factors: ac_quantize, ac_dequantize,
-                          * ac_decode_quantized[_launches], ac_psy_scale_bands_host) and its packed bitstream (ac_pack_index,
-                          * ac_pack, ac_unpack, ac_pack_scratch_bytes); additions only, so the number stays.
+                          * ac_decode_quantized[_launches], ac_psy_scale_bands_host), its packed bitstream (ac_pack_index,
+                          * ac_pack, ac_unpack, ac_pack_scratch_bytes) and its rate control (ac_quantize_budget); additions
+                          * only, so the number stays.
                           * 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
                           * with a 5-smooth half up to 8192, float32); masking model for general band layouts up to 4096 bins.
                           * 0.1.7: only the ac_* entry points are exported; ac_stream_settle (home buffers for the streaming state);
@@ -282,6 +283,19 @@ AC_API int ac_pack(const ac_psy_plan* psy, const int16_t* codes, const int8_t* s
                    int F, int C, void* stream);
 AC_API int ac_unpack(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes, const int64_t* index, int16_t* codes,
                      int8_t* sf, int B, int F, int C, void* stream);
+
+/* Rate control (extension): ac_quantize with every scale factor of a row (b, f, c) raised by one offset.
+ * With sf0 the scale factors of ac_quantize, a row's scale factors at offset k are 0 in an empty band, -128 where sf0 = -128
+ * and clamp(sf0 + k, -127, 127) elsewhere; its codes are ac_quantize's rule with those steps.  bits(k), the row's packed
+ * length before padding (5M + sum over bands of width 1..16 of 8 + width * band length), does not grow with k.
+ * ac_quantize_budget: X, thr [B,F,N,C] float32 -> codes int16 [B,F,N,C], sf int8 [B,F,M,C], offset int16 [B,F,C] and
+ *   row_bits_out int32 [B,F,C] (may be NULL) = bits(offset), where offset is the smallest k in [kmin, 254] with
+ *   bits(k) <= the row's budget, else 254 (a budget not met shows as row_bits_out > budget).  The budget is
+ *   row_bits_per_row[b,f,c] (int32 [B,F,C], entries not checked) or, where that is NULL, row_bits (>= 5M).  kmin = 0 with a
+ *   budget of 16N + 13M gives ac_quantize's output.  kmin in [-254, 254]; plans as ac_quantize. */
+AC_API int ac_quantize_budget(const ac_psy_plan* psy, const float* X, const float* thr, int row_bits,
+                              const int32_t* row_bits_per_row, int kmin, int16_t* codes, int8_t* sf, int16_t* offset,
+                              int32_t* row_bits_out, int B, int F, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Streaming overlap-add (chunked transform with device-resident state).

@@ -1,0 +1,347 @@
+"""Rate control: the quantiser with every scale factor of a row raised by the smallest offset whose
+packed row fits a bit budget.
+
+``rate_reference.py`` restates rules 1-3 in numpy, with a brute-force search (every bin requantised at every offset) and
+the band-extremes search the kernel uses; the CPU tests pin the two to each other and to the worked example of the
+section, the GPU tests check ``quantize_to_budget`` against them bit for bit.
+"""
+
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import audiocodec_amd
+from audiocodec_amd import _lib
+from pack_reference import np_row_bits
+from rate_reference import K_MAX, band_extremes, brute_force, fast_bits, fast_search, quantize_budget, sf_at
+from test_quantizer import np_offsets, np_quantize
+
+# the worked example of DESIGN.md section 8c: M = 4, band 0 empty
+EX_OFF = np.array([0, 0, 2, 5, 8])
+EX_X = np.array([0.3, -0.2, 1.0, -0.7, 0.05, 0.01, 0.0, -0.02], np.float32).reshape(1, 1, 8, 1)
+EX_THR = np.array([0.01, 0.02, 0.05, 0.04, 0.06, 0.001, 0.002, 0.003], np.float32).reshape(1, 1, 8, 1)
+EX_BITS = [100, 100, 97, 94, 92, 92, 89, 86, 84, 84, 81, 78, 76, 73, 73, 70, 68, 65, 65, 65, 62, 60, 57, 57, 57, 57, 32,
+           32, 20]
+
+
+def unlimited(N, M):
+    return 16 * N + 13 * M
+
+
+def adversarial(rng, off, B, F, C):
+    """X, thr [B, F, N, C] with rows that reach every corner of the search: scale factors at both clamp limits, saturated
+    codes at every offset, -0.0, NaN / Inf bands, all-zero rows, and ordinary rows at many levels."""
+    N = int(off[-1])
+    X = (rng.standard_normal((B, F, N, C)) * 10.0 ** rng.uniform(-5, 1, (B, F, 1, C))).astype(np.float32)
+    thr = (np.abs(rng.standard_normal((B, F, N, C))) * 10.0 ** rng.uniform(-5, -1, (B, F, 1, C)) + 1e-8).astype(np.float32)
+    X[0, 0, :, 0] = np.where(np.arange(N) % 2 == 0, np.float32(-0.0), np.float32(0.0))    # -0.0 and +0.0 only
+    if F > 1:
+        X[0, 1, : N // 2, C - 1] = 3e38          # saturates at every offset: the row never fits a small budget
+        X[0, 1, N // 2:, C - 1] = -3e38
+    if B > 1:
+        thr[1, 0, :, 0] = 1e30                   # sf0 = 127: raised offsets stay clamped at the top
+        thr[1, 0, N // 3:, C - 1] = 1e-30        # sf0 = -127: negative offsets stay clamped at the bottom
+        X[1, 0, N // 3:, C - 1] *= 1e-20
+        X[1, F - 1, N // 2, 0] = np.nan
+        thr[1, F - 1, N - 1, C - 1] = np.inf
+        X[B - 1, F - 1, 0, C - 1] = -np.inf
+    return X, thr
+
+
+# ---- CPU -----------------------------------------------------------------------------------------------------------
+def test_worked_example():
+    codes0, sf0 = np_quantize(EX_X, EX_THR, EX_OFF)
+    np.testing.assert_array_equal(sf0.ravel(), [0, -30, -22, -44])
+    np.testing.assert_array_equal(codes0.ravel(), [54, -36, 45, -32, 2, 20, 0, -41])
+    assert np_row_bits(codes0, sf0, EX_OFF).ravel()[0] == 100
+    table = {100: (0, 100), 96: (3, 94), 64: (20, 62), 56: (26, 32), 20: (28, 20)}
+    for R, (k, bits) in table.items():
+        for search in (brute_force, fast_search):
+            codes, sf, offset, row_bits, over_k = search(EX_X, EX_THR, EX_OFF, R)
+            assert offset.ravel()[0] == k and row_bits.ravel()[0] == bits, (search.__name__, R)
+            np.testing.assert_array_equal(over_k[:29].ravel(), EX_BITS)
+            if R == 100:
+                np.testing.assert_array_equal(sf, sf0)
+                np.testing.assert_array_equal(codes, codes0)
+            if R == 64:
+                np.testing.assert_array_equal(sf.ravel(), [0, -10, -2, -24])
+                np.testing.assert_array_equal(codes.ravel(), [2, -1, 1, -1, 0, 1, 0, -1])
+            if R == 20:
+                assert not codes.any()
+
+
+def test_worked_example_min_offset():
+    """kmin bounds the search from below; a budget below the floor 5M is never met (offset 254)."""
+    _, _, offset, row_bits = quantize_budget(EX_X, EX_THR, EX_OFF, 100, kmin=5)
+    assert offset.ravel()[0] == 5 and row_bits.ravel()[0] == 92
+    _, _, offset, row_bits = quantize_budget(EX_X, EX_THR, EX_OFF, 100, kmin=-3)
+    assert offset.ravel()[0] == 0 and row_bits.ravel()[0] == 100
+    codes, sf, offset, row_bits = quantize_budget(EX_X, EX_THR, EX_OFF, unlimited(8, 4), kmin=-3)
+    assert offset.ravel()[0] == -3 and row_bits.ravel()[0] > 100
+    np.testing.assert_array_equal(sf.ravel(), [0, -33, -25, -47])
+    codes, sf, offset, row_bits = quantize_budget(EX_X, EX_THR, EX_OFF, 19)
+    assert offset.ravel()[0] == K_MAX and row_bits.ravel()[0] == 20
+    np.testing.assert_array_equal(sf.ravel(), [0, 127, 127, 127])
+
+
+@pytest.mark.parametrize("sr,N,M,kmin", [(44100, 256, 48, -254), (48000, 64, 64, -40), (48000, 1024, 64, 0),
+                                         (48000, 256, 4096, 150)])
+def test_brute_force_equals_band_extremes(sr, N, M, kmin):
+    off = np_offsets(sr, N, M)
+    rng = np.random.default_rng(N + M)
+    B, F, C = 2, 3, 2
+    X, thr = adversarial(rng, off, B, F, C)
+    natural = np_row_bits(*np_quantize(X, thr, off), off)
+    R = np.maximum(5 * M, (natural * rng.uniform(0.0, 1.1, natural.shape)).astype(np.int64))
+    a = brute_force(X, thr, off, R, kmin)
+    b = fast_search(X, thr, off, R, kmin)
+    for u, v in zip(a, b):
+        np.testing.assert_array_equal(u, v)
+    codes, sf, offset, row_bits, over_k = a
+    assert (offset == K_MAX).any() and (offset < K_MAX).any()
+    assert (sf == -128).any() and (sf == 127).any() and (np.abs(codes) == 32767).any()
+    met = row_bits <= R
+    assert np.all(offset[~met] == K_MAX)
+    # the row bits at the offset are those of its codes, and the offset is the first that fits
+    np.testing.assert_array_equal(row_bits, np_row_bits(codes, sf, off))
+    first = offset > kmin
+    assert np.all(over_k[offset[first] - kmin - 1, first.nonzero()[0], first.nonzero()[1], first.nonzero()[2]] >
+                  R[first])
+
+
+def test_bits_do_not_grow_with_the_offset():
+    rng = np.random.default_rng(11)
+    for sr, N, M in [(44100, 256, 48), (48000, 1024, 64), (48000, 128, 64)]:
+        off = np_offsets(sr, N, M)
+        X, thr = adversarial(rng, off, 2, 4, 2)
+        _, sf0 = np_quantize(X, thr, off)
+        xmax, xmin = band_extremes(X, off)
+        bits = np.stack([fast_bits(sf0, xmax, xmin, off, k) for k in range(-254, K_MAX + 1)])
+        assert np.all(np.diff(bits, axis=0) <= 0)
+        assert np.all(bits >= 5 * M) and np.all(bits <= unlimited(N, M))
+        # offset 0 is the quantiser's own row length
+        np.testing.assert_array_equal(bits[254], np_row_bits(*np_quantize(X, thr, off), off))
+
+
+def test_scale_factors_at_an_offset():
+    sf0 = np.array([[[[0], [-128], [-127], [127], [5]]]], np.int8)
+    off = np.array([0, 0, 1, 2, 3, 4])      # band 0 empty
+    np.testing.assert_array_equal(sf_at(sf0, off, 3).ravel(), [0, -128, -124, 127, 8])
+    np.testing.assert_array_equal(sf_at(sf0, off, -254).ravel(), [0, -128, -127, -127, -127])
+    np.testing.assert_array_equal(sf_at(sf0, off, 254).ravel(), [0, -128, 127, 127, 127])
+
+
+def test_library_exports_the_rate_entry_point():
+    lib = _lib.load()
+    assert "ac_quantize_budget" in _lib.PROTOTYPES and hasattr(lib, "ac_quantize_budget")
+    assert lib.ac_quantize_budget(None, None, None, 10000, None, 0, None, None, None, None, 1, 1, 1, None) == _lib.AC_EINVAL
+    assert "plan" in lib.ac_last_error().decode()
+    codec = audiocodec_amd.AudioCodec(48000, 1024)
+    assert codec.row_bits_for_bitrate(128000) == 2730            # floor(128000 * 1024 / 48000)
+    assert codec.row_bits_for_bitrate(64000.5) == 1365
+    assert audiocodec_amd.AudioCodec(44100, 2048).row_bits_for_bitrate(96000) == 4458
+    with pytest.raises(ValueError):
+        codec.row_bits_for_bitrate(0)
+    with pytest.raises(TypeError):
+        codec.row_bits_for_bitrate("128k")
+    for name in ("quantize_to_budget",):
+        assert callable(getattr(audiocodec_amd.PsychoacousticModel, name))
+    for name in ("encode_quantized_budget", "encode_packed_budget"):
+        assert callable(getattr(audiocodec_amd.AudioCodec, name))
+
+
+# ---- GPU -----------------------------------------------------------------------------------------------------------
+gpu = pytest.mark.gpu
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _check(psy, X, thr, R, kmin):
+    """quantize_to_budget against the numpy restatement, bit for bit; returns the reference."""
+    off = psy.scale_band_offsets
+    Rd = _dev(np.asarray(R, dtype=np.int32)) if isinstance(R, np.ndarray) else R
+    codes, sf, offset, row_bits = psy.quantize_to_budget(_dev(X), _dev(thr), Rd, min_offset=kmin)
+    rc, rs, ro, rb = quantize_budget(X, thr, off, R, kmin)
+    B, F, N, C = X.shape
+    assert codes.dtype == torch.int16 and sf.dtype == torch.int8
+    assert offset.dtype == torch.int16 and row_bits.dtype == torch.int32
+    assert offset.shape == (B, F, C) and row_bits.shape == (B, F, C)
+    np.testing.assert_array_equal(offset.cpu().numpy(), ro)
+    np.testing.assert_array_equal(row_bits.cpu().numpy(), rb)
+    np.testing.assert_array_equal(sf.cpu().numpy(), rs)
+    np.testing.assert_array_equal(codes.cpu().numpy(), rc)
+    return rc, rs, ro, rb
+
+
+@gpu
+@pytest.mark.parametrize("sr,N,M,C", [(48000, 1024, 64, 2), (48000, 1024, 64, 1), (48000, 1024, 64, 6),
+                                      (48000, 2048, 64, 2), (48000, 2048, 64, 1), (48000, 960, 64, 2), (48000, 960, 64, 6),
+                                      (48000, 128, 64, 2), (48000, 128, 64, 1), (48000, 64, 64, 6), (48000, 512, 64, 2),
+                                      (48000, 8192, 256, 2), (48000, 8192, 4096, 2), (48000, 1024, 600, 7)])
+def test_quantize_to_budget_bit_exact(sr, N, M, C):
+    """Plans through every kernel instance (X in registers at N <= 1024 with one or two channels, re-read otherwise),
+    channel groups (M = 4096: one channel per group; 600 bands x 7 channels: groups of 4, the last partial), scalar and
+    per-row budgets, min_offset below, at and above 0."""
+    psy = audiocodec_amd.PsychoacousticModel(sr, filter_bands_n=N, bark_bands_n=M)
+    off = psy.scale_band_offsets
+    rng = np.random.default_rng(N * 7 + M + C)
+    B, F = 2, 3
+    X, thr = adversarial(rng, off, B, F, C)
+    natural = np_row_bits(*np_quantize(X, thr, off), off)
+    per_row = np.maximum(5 * M - 3, (natural * rng.uniform(0.0, 1.05, natural.shape))).astype(np.int32)
+    per_row[0, 0, 0] = -5                                          # entries are not checked: never met
+    scalar = int(max(5 * M, np.median(natural) // 2))
+    seen = set()
+    for kmin in (-30, 0, 17):
+        for R in (scalar, per_row):
+            _, _, ro, _ = _check(psy, X, thr, R, kmin)
+            seen.update(np.unique(ro).tolist())
+    assert K_MAX in seen and len(seen) > 3
+
+
+@gpu
+@pytest.mark.parametrize("sr,N,M,C", [(48000, 1024, 64, 2), (48000, 2048, 64, 1), (48000, 960, 64, 6), (48000, 64, 64, 2),
+                                      (48000, 8192, 4096, 1)])
+def test_unlimited_budget_is_quantize(sr, N, M, C):
+    psy = audiocodec_amd.PsychoacousticModel(sr, filter_bands_n=N, bark_bands_n=M)
+    rng = np.random.default_rng(3 * N + C)
+    X, thr = adversarial(rng, psy.scale_band_offsets, 2, 3, C)
+    Xd, td = _dev(X), _dev(thr)
+    codes0, sf0 = psy.quantize(Xd, td)
+    codes, sf, offset, row_bits = psy.quantize_to_budget(Xd, td, unlimited(N, M))
+    assert torch.equal(codes, codes0) and torch.equal(sf, sf0)
+    assert not offset.any()
+    np.testing.assert_array_equal(row_bits.cpu().numpy(), np_row_bits(codes0.cpu().numpy(), sf0.cpu().numpy(),
+                                                                       psy.scale_band_offsets))
+    # a fixed-quality mode: an unlimited budget from min_offset k is the quantiser at offset k
+    codes, sf, offset, _ = psy.quantize_to_budget(Xd, td, unlimited(N, M), min_offset=12)
+    assert torch.equal(offset, torch.full_like(offset, 12))
+    np.testing.assert_array_equal(sf.cpu().numpy(), sf_at(sf0.cpu().numpy(), psy.scale_band_offsets, 12))
+
+
+@gpu
+def test_unmet_budget_gives_the_largest_offset():
+    psy = audiocodec_amd.PsychoacousticModel(48000, filter_bands_n=1024, bark_bands_n=64)
+    rng = np.random.default_rng(21)
+    X, thr = adversarial(rng, psy.scale_band_offsets, 2, 3, 2)
+    X[1, 2, :, 0] = 1e38                                            # every band saturated at every offset
+    R = np.full((2, 3, 2), 2000, np.int32)
+    R[0, 2, 1] = 5 * 64 - 1                                         # below the floor
+    _, rs, ro, rb = _check(psy, X, thr, R, 0)
+    assert ro[1, 2, 0] == K_MAX and rb[1, 2, 0] > 2000 and ro[0, 2, 1] == K_MAX and rb[0, 2, 1] >= 5 * 64
+    assert ro[0, 1, 1] == K_MAX                                     # the +-3e38 row of adversarial()
+    assert np.all(ro[rb > R] == K_MAX)
+
+
+def _row_bytes(data, index):
+    """Each row's byte length in (b, f, c) order, from index differences and len(data)."""
+    starts = index.cpu().numpy().reshape(-1)
+    return np.diff(np.concatenate([starts, [data.numel()]]))
+
+
+@gpu
+@pytest.mark.parametrize("N,C,bps", [(1024, 2, 64000), (1024, 1, 32000), (2048, 2, 128000), (960, 6, 48000)])
+def test_encode_packed_budget_at_a_bitrate(N, C, bps):
+    """End to end: every row that met its budget takes at most ceil(R / 32) * 4 bytes; the stream decodes to
+    decode_quantized of the budgeted codes, bit for bit."""
+    codec = audiocodec_amd.AudioCodec(48000, N)
+    rng = np.random.default_rng(N + C)
+    B, K = 2, 6
+    x = (rng.uniform(-1, 1, (B, K * N, C)) * np.linspace(0.01, 1, K * N)[None, :, None]).astype(np.float32)
+    xd = _dev(x)
+    R = codec.row_bits_for_bitrate(bps)
+    assert R == bps * N // 48000
+    data, index, offset = codec.encode_packed_budget(xd, R)
+    codes, sf, offset2, row_bits = codec.encode_quantized_budget(xd, R)
+    assert torch.equal(offset, offset2)
+    met = (row_bits.cpu().numpy() <= R).reshape(-1)
+    assert met.mean() > 0.9
+    lens = _row_bytes(data, index)
+    assert np.all(lens[met] <= (R + 31) // 32 * 4)
+    np.testing.assert_array_equal(lens, (row_bits.cpu().numpy().reshape(-1) + 31) // 32 * 4)
+    # the budget costs quality only where it must: unbudgeted rows that fit keep offset 0
+    codes0, sf0 = codec.encode_quantized(xd)
+    natural = np_row_bits(codes0.cpu().numpy(), sf0.cpu().numpy(), codec.psy.scale_band_offsets)
+    np.testing.assert_array_equal(offset.cpu().numpy() == 0, natural <= R)
+    for pcm16 in (False, True) if C <= 2 else (False,):      # (16-bit PCM out: mono / stereo at 960)
+        a = codec.decode_packed(data, index, pcm16=pcm16)
+        b = codec.decode_quantized(codes, sf, pcm16=pcm16)
+        assert a.dtype == b.dtype and a.shape == b.shape
+        assert torch.equal(a.view(torch.int32) if not pcm16 else a, b.view(torch.int32) if not pcm16 else b)
+
+
+@gpu
+def test_error_paths():
+    psy = audiocodec_amd.PsychoacousticModel(48000, filter_bands_n=1024, bark_bands_n=64)
+    rng = np.random.default_rng(1)
+    X, thr = adversarial(rng, psy.scale_band_offsets, 1, 2, 2)
+    Xd, td = _dev(X), _dev(thr)
+    R = torch.full((1, 2, 2), 3000, dtype=torch.int32, device=Xd.device)
+    with pytest.raises(ValueError):
+        psy.quantize_to_budget(Xd.double(), td.double(), 3000)
+    with pytest.raises(ValueError):
+        psy.quantize_to_budget(Xd, td[:, :1], 3000)
+    with pytest.raises(ValueError):
+        psy.quantize_to_budget(Xd, td, R.long())
+    with pytest.raises(ValueError):
+        psy.quantize_to_budget(Xd, td, R[:, :1])
+    with pytest.raises(ValueError):
+        psy.quantize_to_budget(Xd, td, R.cpu())
+    with pytest.raises(ValueError):
+        psy.quantize_to_budget(Xd, td, 5 * 64 - 1)
+    with pytest.raises(ValueError):
+        psy.quantize_to_budget(Xd, td, 3000, min_offset=255)
+    with pytest.raises(ValueError):
+        psy.quantize_to_budget(Xd, td, 3000, min_offset=-255)
+    with pytest.raises(TypeError):
+        psy.quantize_to_budget(Xd, td, 3000.0)
+    with pytest.raises(ValueError, match="add_noise"):
+        psy.quantize_to_budget(Xd.clone().requires_grad_(), td, 3000)
+    codec = audiocodec_amd.AudioCodec(48000, 1024)
+    with pytest.raises(ValueError, match="add_noise"):
+        codec.encode_quantized_budget(_dev(np.zeros((1, 2048, 2), np.float32)).requires_grad_(), 3000)
+    other = audiocodec_amd.PsychoacousticModel(48000, filter_bands_n=1024, bark_bands_n=64, compute_dtype=torch.float64)
+    with pytest.raises(NotImplementedError, match="float32"):
+        other.quantize_to_budget(Xd.double(), td.double(), 3000)
+    # the C ABI refuses what the Python layer refuses, with a message
+    lib = _lib.load()
+    out = [torch.empty(s, dtype=d, device=Xd.device) for s, d in (((1, 2, 1024, 2), torch.int16), ((1, 2, 64, 2), torch.int8),
+                                                                   ((1, 2, 2), torch.int16), ((1, 2, 2), torch.int32))]
+    p = [ctypes.c_void_p(t.data_ptr()) for t in [Xd, td] + out]
+
+    def call(R, Rrow, kmin):
+        return lib.ac_quantize_budget(psy._plan(Xd.device), p[0], p[1], R, Rrow, kmin, p[2], p[3], p[4], p[5], 1, 2, 2, None)
+
+    assert call(3000, None, 255) == _lib.AC_EINVAL and "kmin" in lib.ac_last_error().decode()
+    assert call(3000, None, -255) == _lib.AC_EINVAL
+    assert call(5 * 64 - 1, None, 0) == _lib.AC_EINVAL and "row_bits" in lib.ac_last_error().decode()
+    assert call(0, ctypes.c_void_p(R.data_ptr()), 0) == _lib.AC_OK        # a per-row budget: the scalar is not read
+    torch.cuda.synchronize()
+    ref = psy.quantize_to_budget(Xd, td, R)
+    assert torch.equal(out[0], ref[0]) and torch.equal(out[2], ref[2])
+    # row_bits_out may be NULL
+    assert lib.ac_quantize_budget(psy._plan(Xd.device), p[0], p[1], 3000, None, 0, p[2], p[3], p[4], None, 1, 2, 2,
+                                  None) == _lib.AC_OK
+    torch.cuda.synchronize()
+
+
+@gpu
+def test_side_stream():
+    codec = audiocodec_amd.AudioCodec(48000, 1024)
+    rng = np.random.default_rng(8)
+    x = _dev(rng.uniform(-1, 1, (4, 20 * 1024, 2)).astype(np.float32))
+    X, _, thr = codec.encode(x)
+    R = codec.row_bits_for_bitrate(48000)
+    ref = codec.psy.quantize_to_budget(X, thr, R)
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        out = codec.psy.quantize_to_budget(X, thr, R)
+    torch.cuda.current_stream().wait_stream(s)
+    for a, b in zip(out, ref):
+        assert torch.equal(a, b)
