@@ -1,5 +1,5 @@
 // Generic kernels: any even N, any channel count, any Bark-band count.  O(N^2) direct DCT-IV.
-// They are the path for sizes the wave-level FFT kernels (ac_fast.hip) do not cover and an
+// They are the path for sizes the wave-level FFT kernels (ac_fast_*.hip) do not cover and an
 // independent on-device cross-check for them.  Also here: the run-time forms of the LDS-FFT middle tier (the 16-byte kernels
 // with compile-time plans are instantiated in ac_wave_*.hip), the generic masking model and its backward, the element-wise
 // kernels, and the dispatch between the tiers with the host plan and geometry helpers of ac_wave_v.h.  gfx950 only.

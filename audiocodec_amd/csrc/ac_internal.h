@@ -60,7 +60,7 @@ struct DeviceGuard {
 
 extern int g_force_generic;
 
-// ---- element-wise pieces shared by the stand-alone utilities (ac_generic.hip) and the fused encode epilogue (ac_fast.hip):
+// ---- element-wise pieces shared by the stand-alone utilities (ac_generic.hip) and the fused encode epilogue (ac_fast_psy_dev.h):
 // one definition, so that fused and un-fused results agree bit for bit
 // counter-based generator: a 64-bit mix (splitmix64) of (seed, pair index) -> Box-Muller, both outputs used:
 // elements 2p and 2p+1 of the flattened tensor take R cos(theta) and R sin(theta)
@@ -119,7 +119,7 @@ struct ac_mdct_plan {
   float* d_ctab = nullptr;     // [8N]      cos(pi i / (4N)), generic kernels
   double* d_coef64 = nullptr;  // the same two tables in float64 (AC_F64 entry points)
   double* d_ctab64 = nullptr;
-  // fast-path tables (ac_fast.hip): per-FFT-element fold coefficients and twiddles
+  // fast-path tables (ac_fast_plan.hip): per-FFT-element fold coefficients and twiddles
   float* d_fast = nullptr;
   size_t fast_bytes = 0;
 };
@@ -143,7 +143,7 @@ struct ac_psy_plan {
   double* d_wb_val64 = nullptr; double* d_wi_val64 = nullptr;
   double* d_wf_val64 = nullptr; double* d_vb_val64 = nullptr;   // ... of the transposed walks (backward in float64)
   double* d_S64 = nullptr; double* d_quiet64 = nullptr; double* d_beta64 = nullptr;
-  // fast-path tables (ac_fast.hip)
+  // fast-path tables (ac_fast_plan.hip)
   float* d_fast = nullptr;
   size_t fast_bytes = 0;
   // wave-level masking model for general band layouts (ac_psy_mid.hip): any even filter_bands_n <= 1024, <= 64 bands
@@ -229,7 +229,7 @@ int launch_tonality_generic(const ac_psy_plan* p, const float* X, float* t, int 
 int launch_threshold_generic(const ac_psy_plan* p, const float* X, const float* t, float drown, float* thr, int B,
                              int F, int C, hipStream_t s);
 
-// wave-level FFT kernels (ac_fast.hip)
+// wave-level FFT kernels (ac_fast_*.hip; what they share among themselves: ac_fast.h)
 bool fast_mdct_supported(int N, const FoldCoef& c);
 // filters_n 512 / 256 run several frames per wave (2 / 4); those kernels serve float32 mono / stereo tensors with at least
 // one block (streaming state included) -- everything else at these sizes takes the LDS-FFT tier

@@ -1,4 +1,4 @@
-// Wave-level masking model for the configurations the fused epilogue of ac_fast.hip does not serve: any even
+// Wave-level masking model for the configurations the fused epilogue of ac_fast_psy_dev.h does not serve: any even
 // filter_bands_n up to 4096 (a frame is up to R = 1, 2, 4, 8, 16 or 32 granule registers per lane, the last ones partly filled
 // when filter_bands_n is not a multiple of 128: 960, 576, 480 ...; above 512 the W_inv entries stay in global memory) with any Bark-band count up to 64 and any band layout (a bin may overlap several bands, bands may share
 // bins freely) -- e.g. the models beside the several-frames-per-wave MDCT kernels (filters_n 256 / 512), where the
@@ -210,7 +210,7 @@ bool build_mid(const ac_psy_plan* p, std::vector<uint32_t>* out, MidLayout* lay)
       if ((float)t.S[(size_t)i * M + j] != (float)t.g[(size_t)(M - i + j)]) return false;
   {
     // bf16 tiles for spread_tiles: copy c, entry y = rev[y - c], rev[m] = gp[128 - m] (m = 1 .. 127), with
-    // gp[64 + d] = g[M + d] where |d| < M, else 0; hi parts, then lo parts (the layout of spread_mfma in ac_fast.hip)
+    // gp[64 + d] = g[M + d] where |d| < M, else 0; hi parts, then lo parts (the layout of spread_mfma in ac_fast_psy_dev.h)
     auto gp = [&](int k) { const int d = k - 64; return (d > -M && d < M) ? (float)t.g[(size_t)(M + d)] : 0.f; };
     auto bf16_rne = [](float f) { uint32_t u; memcpy(&u, &f, 4); u += 0x7fffu + ((u >> 16) & 1u); return (uint16_t)(u >> 16); };
     auto bf16_val = [](uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; };

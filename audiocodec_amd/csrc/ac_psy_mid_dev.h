@@ -1,5 +1,5 @@
 // Device code of the wave-level masking model for general band layouts, shared by the stand-alone kernel (k_psy_mid,
-// ac_psy_mid.hip) and the fused encode of the several-frames-per-wave MDCT kernels (k_fwd_multi, ac_fast.hip): ONE
+// ac_psy_mid.hip) and the fused encode of the several-frames-per-wave MDCT kernels (k_fwd_multi, ac_fast_multi.hip): ONE
 // definition of the per-frame arithmetic, so that the fused and the un-fused encode agree bit for bit.  gfx950 only.
 //
 // One frame (both signals of a pair) per call, all 64 lanes: the frame's granules xq[i] = (X[2q], X[2q+1]) x (s0, s1),
@@ -29,7 +29,7 @@ __device__ __forceinline__ float dpp_add(float v) {
   const int iv = __builtin_bit_cast(int, v);
   return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, iv, CTRL, ROW_MASK, 0xf, false));
 }
-__device__ __forceinline__ float wave_sum(float v) {   // as in ac_fast.hip: xor butterflies per row of 16, two row broadcasts
+__device__ __forceinline__ float wave_sum(float v) {   // as in ac_fast_dev.h: xor butterflies per row of 16, two row broadcasts
   v = dpp_add<0xB1, 0xf>(v);
   v = dpp_add<0x4E, 0xf>(v);
   v = dpp_add<0x141, 0xf>(v);
@@ -44,7 +44,7 @@ __device__ __forceinline__ v2f maxv(v2f a, float b) { return v2f{fmaxf(a.x, b), 
 
 // ---- band x band product with the Toeplitz spreading matrix on the matrix cores ------------------------------------------
 //   out_j = sum_i Q_i S[i, j],  S[i, j] = g[64 - i + j]   (psychoacoustic.py:205-207, 223-228)
-// as 32 v_mfma_f32_4x4x4_16b_bf16 on split-bfloat16 operands (the scheme of spread_mfma in ac_fast.hip, BASELINE
+// as 32 v_mfma_f32_4x4x4_16b_bf16 on split-bfloat16 operands (the scheme of spread_mfma in ac_fast_psy_dev.h, BASELINE
 // configs[3]): the instruction's 16 blocks are the 16 column tiles of S, so band j of the result lands in lane j; step s
 // contracts bands 4 s .. 4 s + 3; its A tile (rows 0, 1 = the two signals' Q rounded to bfloat16, rows 2, 3 = the
 // remainders Q - hi) is built by a quad-local transpose in the four lanes of block s and broadcast with cbsz = 4 /
@@ -146,7 +146,7 @@ __device__ __forceinline__ bool in_frame(const MidParams& a, int i, int lane) { 
 // entries) are read once for all of them.  Every frame sees exactly the operations, in the order, it would see alone:
 // results do not depend on FB or on which frames share a group.
 
-// tonality of FB frames (psychoacoustic.py:102-120; the arithmetic of psy_stage in ac_fast.hip)
+// tonality of FB frames (psychoacoustic.py:102-120; the arithmetic of psy_stage in ac_fast_psy_dev.h)
 template <int R, int FB>
 __device__ __forceinline__ void tonality_frames(const v4f (&xq)[FB][R], const MidParams& a, int lane, v2f (&t)[FB]) {
   v2f slog[FB], ssq[FB];

@@ -1,7 +1,7 @@
 // Device code of the wave-level masking model for general band layouts in its run-structured form (round 4): the model
 // of ac_psy_mid_dev.h with the structure every Bark mapping of the reference has (psychoacoustic.py:257-299) taken out of
 // the frame loop at plan time.  Shared by the stand-alone kernel (k_psy_runs, ac_psy_mid.hip), the fused encode of the
-// several-frames-per-wave MDCT kernels (k_fwd_multi, ac_fast.hip) and the fused encode of the LDS-FFT tier (k_enc_wave_v,
+// several-frames-per-wave MDCT kernels (k_fwd_multi, ac_fast_multi.hip) and the fused encode of the LDS-FFT tier (k_enc_wave_v,
 // ac_wave_enc.hip): ONE definition of the per-frame arithmetic, so the fused and the un-fused encode agree bit for bit.
 //
 // What the structure is (checked by build_runs on the host; a plan that does not have it keeps the band walk):
@@ -218,7 +218,7 @@ __device__ __forceinline__ void tonality_from(ISRC isrc, const RunsParams& a, in
   tonality_finish<FB>(acc, a, lane, t);
 }
 // the intensities of a granule: rounded products (left to -ffp-contract=fast the compiler fuses one of the two squares of
-// ie + io into the sum of squares -- which one differs between instantiations; see psy_stage in ac_fast.hip)
+// ie + io into the sum of squares -- which one differs between instantiations; see psy_stage in ac_fast_psy_dev.h)
 __device__ __forceinline__ v4f squares(v4f x) {
   v4f I = x * x;
   asm("" : "+v"(I));

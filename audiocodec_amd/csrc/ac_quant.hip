@@ -4,7 +4,7 @@
 //
 //   k_quantize    X, thr [B,F,N,C] float32 -> codes int16 [B,F,N,C], sf int8 [B,F,M,C]
 //   k_dequantize  codes, sf -> X^ = fp32(code * step(sf)) (the fallback of ac_decode_quantized; the independent path the
-//                 fused synthesis from codes, k_inv_fast_q in ac_fast.hip, is tested against)
+//                 fused synthesis from codes, k_inv_fast_q in ac_fast_inv.hip, is tested against)
 //
 // One workgroup per (clip, frame) row and group of channels.  The band minimum is a segmented reduction over contiguous
 // bins: each wave takes 64 consecutive bins, reduces every run of equal band index with a log-step suffix minimum across

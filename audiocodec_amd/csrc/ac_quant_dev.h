@@ -1,5 +1,5 @@
 // Device helpers of the quantiser shared by its kernels (ac_quant.hip, ac_rate.hip) and the synthesis from codes
-// (ac_fast.hip): one definition, so that every path quantises and dequantises bit for bit alike.  DESIGN.md section 8a has
+// (ac_fast_inv_dev.h): one definition, so that every path quantises and dequantises bit for bit alike.  DESIGN.md section 8a has
 // the definition.
 #pragma once
 #include <cstdint>

@@ -60,7 +60,7 @@ struct RowPair {
     }
   }
   // the same rows as 16-bit PCM (x = pcm / 32768 on the way in, clamp(round(32768 x)) on the way out, as the wave-level
-  // kernels of ac_fast.hip do): 8 / 4 bytes per access
+  // kernels of ac_fast_dev.h do): 8 / 4 bytes per access
   __device__ __forceinline__ v4f_t load2(const int16_t* a, const int16_t* b, int m) const {
     static_assert(LAY <= 1, "16-bit PCM: stereo or mono rows");
     typedef short s4_t __attribute__((ext_vector_type(4)));
@@ -417,7 +417,7 @@ int allow_lds(K kernel, size_t bytes) {
 }
 
 // Sizes with compile-time instances of the 16-byte kernels: filters_n, lanes per frame, super-radices (every filters_n % 4 == 0
-// with a 5-smooth half up to 8192 -- the powers of two as well: the wave-level kernels of ac_fast.hip leave them the
+// with a 5-smooth half up to 8192 -- the powers of two as well: the wave-level kernels of ac_fast_*.hip leave them the
 // rectangular window and, below 1024, more than two channels; the plan lds_wave_plan's search would pick, with lanes >= N / 16).  Strides, round counts and buffer offsets fold into immediates: 960 runs 0.156 -> 0.103 ms against the run-time form of
 // the same kernel.  lds_wave_plan returns these plans, so the launch geometry and the instance agree by construction; any
 // other size runs the run-time form.

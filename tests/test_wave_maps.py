@@ -1,4 +1,4 @@
-"""CPU: the index maps of the wave-level kernels (audiocodec_amd/csrc/ac_fast.hip), emulated lane by lane in numpy
+"""CPU: the index maps of the wave-level kernels (audiocodec_amd/csrc/ac_fast_dev.h), emulated lane by lane in numpy
 (tests/emulate_wave_fft.py): LDS exchanges are bijections and bank-conflict-free under the gfx950 lane-group rules, the
 in-wave FFT equals numpy's, and the fold / unfold register maps reproduce the oracle's transform for 8 and 16 points per
 lane (filters_n 1024 and 2048)."""

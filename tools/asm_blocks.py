@@ -2,8 +2,8 @@
 """Static instruction census of one kernel in a hipcc -S listing: per basic block, the number of vector-ALU,
 transcendental, matrix, scalar, LDS and vector-memory instructions, with the back edges (loops) marked.
 
-    hipcc --offload-arch=gfx950 -O3 ... --offload-device-only -S ac_fast.hip -o /tmp/ac_fast.s
-    python tools/asm_blocks.py /tmp/ac_fast.s 'k_fwd_multiILi2ELi0ELi4ELi0ELb0ELb1E'
+    hipcc --offload-arch=gfx950 -O3 ... --offload-device-only -S ac_fast_multi.hip -o /tmp/ac_fast_multi.s
+    python tools/asm_blocks.py /tmp/ac_fast_multi.s 'k_fwd_multiILi2ELi0ELi4ELi0ELb0ELb1E'
 
 Used to see where a kernel's issue slots go before spending GPU time on counters (profiles/r4/*census*.txt).
 """

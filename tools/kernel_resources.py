@@ -1,5 +1,5 @@
 """Register / scratch / occupancy table of the kernels of one .hip file (device-only compile with
--Rpass-analysis=kernel-resource-usage): python tools/kernel_resources.py audiocodec_amd/csrc/ac_fast.hip [name filter]"""
+-Rpass-analysis=kernel-resource-usage): python tools/kernel_resources.py audiocodec_amd/csrc/ac_fast_fwd.hip [name filter]"""
 import re
 import subprocess
 import sys
