@@ -310,7 +310,8 @@ static void launch_psy_bf16(const PsyArgs& a, bool want_t, bool want_thr, unsign
   const dim3 blk(AC_WAVES * 64);
   if (want_t && !want_thr) hipLaunchKernelGGL((k_psy_fast<R, CMODE, true, false, AC_WAVES, 0, 2>), dim3(grid), blk, 0, s, a);
   else if (!want_t && want_thr) hipLaunchKernelGGL((k_psy_fast<R, CMODE, false, true, AC_WAVES, 0, 2>), dim3(grid), blk, 0, s, a);
-  else if (want_t && want_thr) hipLaunchKernelGGL((k_psy_fast<R, CMODE, true, true, AC_WAVES, 0, 2>), dim3(grid), blk, 0, s, a);
+  else if constexpr (R == 16 && CMODE == 2)   // (both in one pass: the second launch of the mono encode at 2048 only, see launch_psy_fast)
+    if (want_t && want_thr) hipLaunchKernelGGL((k_psy_fast<R, CMODE, true, true, AC_WAVES, 0, 2>), dim3(grid), blk, 0, s, a);
 }
 template <int R, int CMODE>
 static void launch_psy_R(const PsyArgs& a, bool want_t, bool want_thr, int spread, unsigned grid, hipStream_t s) {
@@ -346,6 +347,11 @@ int launch_psy_fast(const ac_psy_plan* p, const float* X, const float* t_in, flo
   const int cmode = (C == 2) ? 0 : (C == 1) ? 2 : 1;
   if (iof == 2 && C > 2) {
     set_error("internal: no wave-level masking-model kernel for bfloat16 tensors with %d channels", C);
+    return AC_EUNSUPPORTED;
+  }
+  if (iof == 2 && want_t && want_thr && !(p->N == PsyGeo<16>::FN && cmode == 2)) {
+    // (every other bfloat16 encode is one fused launch or calls tonality and threshold in turn: ac_encode_fused_typed)
+    set_error("internal: no wave-level kernel for tonality and threshold of bfloat16 tensors in one pass at filters_n = %d, %d channels", p->N, C);
     return AC_EUNSUPPORTED;
   }
   if (iof == 2) {   // bfloat16 tensors: stereo and mono

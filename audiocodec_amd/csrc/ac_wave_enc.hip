@@ -334,7 +334,10 @@ static __global__ __launch_bounds__((NTC > kThreads ? NTC : kThreads), 2) void k
 
 // the fused encode (k_enc_wave_v): sizes with an instance whose frame region holds a slot of the model -- filters_n 108 ...
 // 4096 (the masking model's range ends there; below 108 a frame's LDS is smaller than the model's smallest slot)
-static bool enc_size(int N) { return N >= 108 && N <= 4096 && lds_wave_ct_size(N); }
+// (128, 256 and 512 have none: mono and stereo float32 tensors of those sizes run the several-frames-per-wave kernels under
+// every window -- wave_level() in ac_api.hip -- so this launch was never reached there)
+static inline constexpr bool enc_instance(int N) { return N >= 108 && N <= 4096 && N != 128 && N != 256 && N != 512; }
+static bool enc_size(int N) { return enc_instance(N) && lds_wave_ct_size(N); }
 // ... and where the one launch measured faster than transform + masking kernel on an MI355X (ratio <= 0.98 over B = 256 stereo
 // clips of 10 s, profiles/r4/lds_fft_fused_encode_sweep.txt: 0.73 - 0.98; the instances left out ran 0.99 - 1.31 x -- the ones
 // that spill registers, and the small sizes, where the per-frame part of the model outweighs the second read of X)
@@ -388,7 +391,7 @@ static int launch_enc_wave_v(const ac_mdct_plan* p, const ac_psy_plan* psy, cons
   int st = AC_OK;
   bool done = false;
 #define AC_WAVE_CT(NC, NTC, R0, R1, R2, R3)                                                                                   \
-  if constexpr (NC >= 108 && NC <= 4096) {                                                                                     \
+  if constexpr (enc_instance(NC)) {                                                                                            \
     if (!done && N == NC) {                                                                                                    \
       done = true;                                                                                                             \
       st = allow_lds(k_enc_wave_v<NC, NTC, R0, R1, R2, R3, LAY>, lds);                                                         \

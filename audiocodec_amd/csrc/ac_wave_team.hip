@@ -366,6 +366,10 @@ static bool team_pays(int N, bool inverse) {
   }
   return false;
 }
+// sizes with an instance of the team kernels: a team is at least two channel pairs and at most the kernels' launch bound of 512
+// lanes, so a frame on eight waves (4320 ... 8192) has no team under any channel count -- team_geometry declines them below
+// (CP nt > 512) and the strided pairs serve them; their instances were never launched and are not compiled
+static inline constexpr bool team_instance(int nt) { return nt <= 64 || 2 * nt <= 512; }
 static bool team_geometry(int N, const WavePlan& wp, int C, bool inverse, int* w, int* tpw, size_t* lds) {
   const char* e = getenv("AC_LDS_WAVE_NOTEAM");   // (read per call -- A/B measurements, tests: 1 never, 2 wherever the shape fits)
   const int mode = e ? atoi(e) : 0;
@@ -414,6 +418,7 @@ int launch_fwd_wave_team(const ac_mdct_plan* p, const float* x, float* X, const 
   int st = AC_OK;
   bool done = false;
 #define AC_WAVE_CT(NC, NTC, R0, R1, R2, R3)                                                                                   \
+  if constexpr (team_instance(NTC))                                                                                            \
   if (!done && p->N == NC) {                                                                                                   \
     done = true;                                                                                                               \
     st = allow_lds(k_fwd_wave_c<NC, NTC, R0, R1, R2, R3>, lds);                                                                \
@@ -445,6 +450,7 @@ int launch_inv_wave_team(const ac_mdct_plan* p, const float* X, float* x, const 
   int st = AC_OK;
   bool done = false;
 #define AC_WAVE_CT(NC, NTC, R0, R1, R2, R3)                                                                                   \
+  if constexpr (team_instance(NTC))                                                                                            \
   if (!done && p->N == NC) {                                                                                                   \
     done = true;                                                                                                               \
     st = allow_lds(k_inv_wave_c<NC, NTC, R0, R1, R2, R3>, lds);                                                                \

@@ -16,6 +16,7 @@ from audiocodec_amd import _lib
 from oracle.audiocodec_oracle import MDCTOracle, PsychoOracle, sine_wav
 from psy_torch_reference import torch_psy_reference as _torch_psy_reference
 from psy_torch_reference import torch_tonality_reference as _torch_tonality_reference
+from wave_sizes import CT_SIZES, ENC_SIZES, team_sizes
 
 pytestmark = pytest.mark.gpu
 
@@ -157,7 +158,10 @@ def test_shape_like_reference(path):
                                      # filters_n whose half is 5-smooth: the mixed-radix LDS-FFT tier (Opus / MP3 sizes)
                                      (2, 5, 2, 960), (3, 4, 1, 480), (2, 7, 2, 240), (1, 9, 3, 120), (2, 3, 2, 576),
                                      (2, 4, 1, 192), (1, 2, 2, 1920), (1, 2, 2, 3072), (2, 3, 2, 30), (1, 3, 2, 1536),
-                                     (2, 2, 2, 2000), (1, 4, 2, 36)])
+                                     (2, 2, 2, 2000), (1, 4, 2, 36),
+                                     # filters_n % 4 == 2 above 2048: the workgroup form of the tier with its second FFT buffer
+                                     # aliased (k_fwd_lds<float, true>) and its synthesis (k_inv_lds<float>), three channels too
+                                     (2, 3, 2, 2250), (1, 2, 3, 4050), (3, 2, 1, 2430)])
 def test_mdct_random_vs_oracle(path, B, K, C, N):
     rng = np.random.default_rng(B * 1000 + K * 10 + C)
     x = rng.uniform(-1, 1, (B, K * N, C)).astype(np.float32)
@@ -202,6 +206,29 @@ def test_lds_fft_wave_16_byte_kernels_every_size(N, C):
     B, K = 3, (70 if N <= 128 else 37 if N <= 480 else 11 if N <= 2048 else 6 if N <= 4096 else 3)
     x = rng.uniform(-1, 1, (B, K * N, C)).astype(np.float32)
     m = audiocodec_amd.MDCTransformer(N)
+    o = MDCTOracle(N, "vorbis", np.float64)
+    X = host(m.transform(dev(x)))
+    Xo = o.transform(x.astype(np.float64))
+    assert rel_peak(X, Xo) <= TOL and rel_l2(X, Xo) <= TOL
+    xh = host(m.inverse_transform(dev(X)))
+    assert np.max(np.abs(xh[:, N:-N] - x)) <= LSB
+    assert np.max(np.abs(xh - o.inverse_transform(Xo))) <= LSB
+
+
+@pytest.mark.parametrize("C", [3, 4])
+@pytest.mark.parametrize("N", CT_SIZES)
+def test_lds_fft_wave_16_byte_kernels_every_size_as_strided_pairs(N, C, monkeypatch):
+    """The strided channel pairs (LAY = 2 of k_fwd_wave_v / k_inv_wave_v) at every size with an instance, the powers of two
+    included: where the team form is the default for three or more channels, test_..._every_size at C = 3 runs the team
+    kernels and these instances never ran, yet they serve misaligned and very wide tensors.  AC_LDS_WAVE_NOTEAM=1 at three
+    channels (pairs (0, 1) and (2, -)) and four, against the fp64 oracle with the bars of that test: analysis, synthesis
+    incl. the aliased head / tail blocks, the round trip to 1 LSB."""
+    monkeypatch.setenv("AC_LDS_WAVE_NOTEAM", "1")
+    rng = np.random.default_rng(N + C)
+    m = audiocodec_amd.MDCTransformer(N)
+    assert m.tier(C) == 2
+    B, K = 3, (70 if N <= 128 else 37 if N <= 480 else 11 if N <= 2048 else 6 if N <= 4096 else 3)
+    x = rng.uniform(-1, 1, (B, K * N, C)).astype(np.float32)
     o = MDCTOracle(N, "vorbis", np.float64)
     X = host(m.transform(dev(x)))
     Xo = o.transform(x.astype(np.float64))
@@ -335,6 +362,11 @@ def test_lds_fft_wave_16_byte_kernels_run_time_form(tmp_path):
             "    X = m.transform(x)\n"
             "    out['X%%d' %% N] = X.cpu().numpy()\n"
             "    out['y%%d' %% N] = m.inverse_transform(X).cpu().numpy()\n"
+            "    for C in (1, 3):\n"          # (the other two row layouts of the run-time form: an odd mono batch, three channels)
+            "        xc = torch.empty(3, 9 * N, C, device='cuda').uniform_(-1, 1, generator=g)\n"
+            "        Xc = m.transform(xc)\n"
+            "        out['X%%d_%%d' %% (N, C)] = Xc.cpu().numpy()\n"
+            "        out['y%%d_%%d' %% (N, C)] = m.inverse_transform(Xc).cpu().numpy()\n"
             "np.savez(sys.argv[1], **out)\n" % (sizes,))
     got = []
     for noct in ("0", "1"):
@@ -344,7 +376,7 @@ def test_lds_fft_wave_16_byte_kernels_run_time_form(tmp_path):
         assert r.returncode == 0, r.stderr[-2000:]
         got.append(np.load(f))
     for N in sizes:
-        for k in ("X%d" % N, "y%d" % N):
+        for k in ("X%d" % N, "y%d" % N, "X%d_1" % N, "y%d_1" % N, "X%d_3" % N, "y%d_3" % N):
             a, b = got[0][k], got[1][k]
             assert np.max(np.abs(a - b)) <= 2e-6 * np.max(np.abs(a)), k
 
@@ -360,7 +392,10 @@ def test_int16_pcm_round_trip_exact(path):
     assert np.array_equal(np.round(xh * 32768.0).astype(np.int32), pcm.astype(np.int32))
 
 
-@pytest.mark.parametrize("N,C", [(960, 2), (960, 1), (120, 3), (4096, 2), (8192, 1), (16, 2)])
+@pytest.mark.parametrize("N,C", [(960, 2), (960, 1), (120, 3), (4096, 2), (8192, 1), (16, 2),
+                                 # the powers of two below 1024: mono and stereo tensors run the several-frames-per-wave kernels
+                                 # there and come to the tier's instances with no block at all (the calls on empty signals below)
+                                 (64, 2), (64, 1), (128, 2), (128, 1), (256, 2), (256, 1), (512, 2), (512, 1)])
 def test_empty_and_edge_shapes_on_the_lds_fft_instances(N, C):
     """No samples, no clips, one block, one clip through the instances of the LDS-FFT tier (strips of one frame, a lone pair
     of a mono batch, frames that are all aliased halves)."""
@@ -478,7 +513,7 @@ def test_codec_golden_beside_the_powers_of_two(golden, path, N):
     assert tonality_err(host(te), t64) <= 1.0 and rel_elem(host(thre), o.global_masking_threshold(X64, t64)) <= TOL
 
 
-@pytest.mark.parametrize("N", [108, 120, 240, 480, 500, 576, 768, 960, 1000, 1080, 1536, 1920, 2304, 3240, 4096])
+@pytest.mark.parametrize("N", ENC_SIZES)
 @pytest.mark.parametrize("C", [2, 1])
 def test_fused_encode_of_the_lds_fft_tier_equals_the_unfused_calls(N, C, monkeypatch):
     """k_enc_wave_v (ac_wave_enc.hip): the LDS-FFT instances with the masking model in the same launch -- tonality and the band
@@ -486,14 +521,25 @@ def test_fused_encode_of_the_lds_fft_tier_equals_the_unfused_calls(N, C, monkeyp
     transform -> tonality -> global_masking_threshold (psychoacoustic.py:102-148 on mdctransformer.py:62-125): bit for bit (one
     definition of the arithmetic), every instance forced on (AC_LDS_WAVE_NOFUSE=2: the product fuses where it measured faster),
     one / several frames per wave and a frame on two / four waves, short and ragged strips, a batch that leaves lanes without
-    a task; thresholds against the oracle at the bar."""
+    a task; thresholds against the oracle at the bar.
+
+    Every size with an instance (the table of ac_wave_v.h, 108 ... 4096: each instance has its own registers, LDS geometry and
+    radix plan, and a wrong one passes every neighbour's case), both row layouts (the mono batches 3 and 1 leave the last
+    pair half empty); the spectrum itself against the fp64 oracle, a second fused run (bit-equal), a drown other than 0, and
+    -- where encode() is this launch without the switch -- the product's own choice."""
+    monkeypatch.delenv("AC_LDS_WAVE_NOFUSE", raising=False)
+    # (the powers of two up to 2048 belong to the wave-level kernels under the 'vorbis' and 'sine' windows: the tier's
+    # instances of those sizes, this one included, serve the rectangular window)
+    window = "vorbis" if audiocodec_amd.MDCTransformer(N).tier(C) == 2 else "rect"
+    codec = audiocodec_amd.AudioCodec(48000, N, window_type=window)
+    assert codec.mdct.tier(C) == 2 and codec.psy.tier() == (2 if N in (1024, 2048) else 1)   # (2: wave-level masking kernels too)
+    pays = codec.encode_launches(C) == 1            # (the library's policy, enc_pays: not a copied list)
     monkeypatch.setenv("AC_LDS_WAVE_NOFUSE", "2")
-    codec = audiocodec_amd.AudioCodec(48000, N)
-    assert codec.mdct.tier(C) == 2 and codec.psy.tier() == 1
     for (B, K) in ((3, 5), (1, 1), (2, 37)):
         x = (torch.rand((B, K * N, C), device="cuda") * 2 - 1) * torch.rand((B, 1, C), device="cuda")
         assert codec.encode_launches(C) == 1
         X, t, thr = codec.encode(x)
+        Xb, tb, thrb = codec.encode(x)
         monkeypatch.setenv("AC_LDS_WAVE_NOFUSE", "1")
         assert codec.encode_launches(C) == 2
         X2 = codec.mdct.transform(x)
@@ -501,13 +547,79 @@ def test_fused_encode_of_the_lds_fft_tier_equals_the_unfused_calls(N, C, monkeyp
         thr2 = codec.psy.global_masking_threshold(X2, t2)
         X3, t3, thr3 = codec.encode(x)
         monkeypatch.setenv("AC_LDS_WAVE_NOFUSE", "2")
-        for a, b in ((X, X2), (t, t2), (thr, thr2), (X, X3), (t, t3), (thr, thr3)):
+        for a, b in ((X, Xb), (t, tb), (thr, thrb), (X, X2), (X, X3), (t2, t3), (thr2, thr3)):
             assert torch.equal(a, b)
-        if (B, K) == (3, 5):
+        if codec.psy.tier() == 1:
+            for a, b in ((t, t2), (thr, thr2), (t, t3), (thr, thr3)):
+                assert torch.equal(a, b)
+        else:
+            # 1024 / 2048: the stand-alone calls run the wave-level masking kernels (k_psy_fast), another definition of the
+            # arithmetic than the run-structured model inside this launch; both are held to the oracle at the bars below,
+            # and to each other at the same bars
+            assert tonality_err(t, t2) <= 1.0 and float(((thr - thr2).abs() / thr2).max()) <= TOL
+        if pays:
+            monkeypatch.delenv("AC_LDS_WAVE_NOFUSE")
+            assert codec.encode_launches(C) == 1
+            for a, b in zip(codec.encode(x), (X, t, thr)):
+                assert torch.equal(a, b)
+            monkeypatch.setenv("AC_LDS_WAVE_NOFUSE", "2")
+        if (B, K) == (3, 5) or codec.psy.tier() != 1:
+            Xo = MDCTOracle(N, window, np.float64).transform(host(x).astype(np.float64))
+            assert rel_peak(host(X), Xo) <= TOL and rel_l2(host(X), Xo) <= TOL
             o = PsychoOracle(48000, N, 64, compute_dtype=np.float64)
             X64 = host(X).astype(np.float64)
             t64 = o.tonality(X64)
             assert tonality_err(host(t), t64) <= 1.0 and rel_elem(host(thr), o.global_masking_threshold(X64, t64)) <= TOL
+            Xd, td, thrd = codec.encode(x, 0.3)
+            thr2d = codec.psy.global_masking_threshold(X2, t2, 0.3)
+            assert torch.equal(Xd, X) and torch.equal(td, t)
+            assert torch.equal(thrd, thr2d) if codec.psy.tier() == 1 else float(((thrd - thr2d).abs() / thr2d).max()) <= TOL
+            assert rel_elem(host(thrd), o.global_masking_threshold(X64, t64, 0.3)) <= TOL
+
+
+@pytest.mark.parametrize("N,C,B", [(3200, 2, 2304), (3200, 1, 4097), (3600, 2, 2304)])
+def test_fused_encode_of_a_frame_on_four_waves_at_2048_workgroups(N, C, B, monkeypatch):
+    """The two sizes of k_enc_wave_v that form their LDS offsets per frame (enc_rebase) and had no chip-filling launch: a
+    frame takes a workgroup of four waves, so a launch has at least as many workgroups as row pairs -- 2304 stereo clips,
+    2049 pairs of 4097 mono clips (the last half empty) -- whatever strip length the launcher picks.  The product's own
+    choice (encode() is this launch at both sizes); two runs bit-equal, bit-equal to transform -> tonality -> threshold, and
+    frame by frame against the float64 kernels at the bars of the family (TOL, tonality_err)."""
+    monkeypatch.delenv("AC_LDS_WAVE_NOFUSE", raising=False)
+    K = 3
+    g = torch.Generator(device="cuda").manual_seed(N + C)
+    x = torch.empty((B, K * N, C), device="cuda").uniform_(-1, 1, generator=g)
+    x *= torch.empty((B, 1, C), device="cuda").uniform_(1e-3, 1, generator=g)
+    codec = audiocodec_amd.AudioCodec(48000, N)
+    assert codec.mdct.tier(C) == 2 and codec.encode_launches(C) == 1
+    X, t, thr = codec.encode(x)
+    Xb, tb, thrb = codec.encode(x)
+    assert torch.equal(X, Xb) and torch.equal(t, tb) and torch.equal(thr, thrb)
+    monkeypatch.setenv("AC_LDS_WAVE_NOFUSE", "1")
+    X2 = codec.mdct.transform(x)
+    t2 = codec.psy.tonality(X2)
+    thr2 = codec.psy.global_masking_threshold(X2, t2)
+    assert torch.equal(X, X2) and torch.equal(t, t2) and torch.equal(thr, thr2)
+    m64 = audiocodec_amd.MDCTransformer(N, compute_dtype=torch.float64)
+    p64 = audiocodec_amd.PsychoacousticModel(48000, N, compute_dtype=torch.float64)
+    step = 256
+    for b0 in range(0, B, step):
+        sl = slice(b0, min(B, b0 + step))
+        X64 = m64.transform(x[sl].double())
+        peak = X64.abs().amax(dim=2).clamp_min(1e-300)
+        assert float(((X[sl].double() - X64).abs().amax(dim=2) / peak).max()) <= TOL, ("X", b0)
+        assert float((X[sl].double() - X64).norm() / X64.norm()) <= TOL, ("X rel-L2", b0)
+        Xs = X[sl].double()
+        t64 = p64.tonality(Xs)
+        thr64 = p64.global_masking_threshold(Xs, t[sl].double())
+        assert tonality_err(t[sl], t64) <= 1.0, ("tonality", b0)
+        assert float(((thr[sl].double() - thr64).abs() / thr64).max()) <= TOL, ("threshold", b0)
+        if b0 == 0:   # the float64 kernels themselves against the CPU oracle on the first clip (bars of test_chip_scale's anchors)
+            Xo = MDCTOracle(N, "vorbis", np.float64).transform(host(x[:1]).astype(np.float64))
+            assert np.max(np.abs(host(X64[:1]) - Xo)) <= 1e-12 * np.max(np.abs(Xo))
+            o = PsychoOracle(48000, N, 64, compute_dtype=np.float64)
+            assert np.max(np.abs(host(t64[:1]) - o.tonality(host(Xs[:1])))) <= 1e-12
+            tho = o.global_masking_threshold(host(Xs[:1]), host(t[:1]).astype(np.float64))
+            assert np.max(np.abs(host(thr64[:1]) - tho) / tho) <= 1e-10
 
 
 @pytest.mark.parametrize("N", [300, 480, 512, 600, 640, 960, 1024, 1280, 1536, 2048])
@@ -564,8 +676,16 @@ def test_fused_encode_at_launches_that_fill_the_chip(N, C, monkeypatch):
     assert torch.equal(X, X2) and torch.equal(t, t2) and torch.equal(thr, thr2)
 
 
-@pytest.mark.parametrize("N", [64, 120, 128, 480, 500, 960, 1024, 1536, 2048, 4096])
-@pytest.mark.parametrize("C", [3, 4, 5, 6, 7])
+def _team_cases():
+    """Every size whose team form takes the channel count (wave_sizes.team_sizes, from the table of ac_wave_v.h) at three, five
+    and six channels, and the ten sizes this test began with at every count (4096 has no team of three pairs: the strided
+    pairs against themselves, as before)."""
+    first = [64, 120, 128, 480, 500, 960, 1024, 1536, 2048, 4096]
+    return [pytest.param(N, C, id="%d-%d" % (C, N)) for C in (3, 4, 5, 6, 7)
+            for N in (sorted(set(team_sizes(C)) | set(first)) if C in (3, 5, 6) else first)]
+
+
+@pytest.mark.parametrize("N,C", _team_cases())
 def test_more_than_two_channels_through_whole_rows_equals_the_strided_pairs(N, C, monkeypatch):
     """k_fwd_wave_c / k_inv_wave_c (ac_wave_team.hip): the channel pairs of one signal as a team that moves whole [filters_n, C]
     rows between HBM and LDS in 16-byte pieces (mdctransformer.py:112, 289-297 takes any channels_n) -- forced on wherever the
@@ -588,6 +708,7 @@ def test_more_than_two_channels_through_whole_rows_equals_the_strided_pairs(N, C
             Xo = o.transform(host(x).astype(np.float64))
             assert rel_peak(host(X), Xo) <= TOL and rel_l2(host(X), Xo) <= TOL
             assert np.max(np.abs(host(y) - o.inverse_transform(Xo))) <= LSB
+            assert np.max(np.abs(host(y)[:, N:-N] - host(x))) <= LSB                    # the round trip
             # chunked, the analysis in the team form and the synthesis in the strided one, then the other way round
             for fwd_mode, inv_mode in (("2", "1"), ("1", "2")):
                 st = audiocodec_amd.StreamingMDCT(m, B, C)
@@ -783,6 +904,203 @@ def test_db_and_noise(golden, path):
     assert float((y.abs() > 0.3).float().mean()) < 0.01
 
 
+# ---- every instance of the wave-level kernels and of the masking kernels for general band layouts -------------
+# (tests/kernel_coverage.txt: the template combinations below had no launch in the suite)
+
+def _vs_oracle(N, x64, X, t, thr, drown, thr_tol, t_in=None, xbar=TOL):
+    """X against the fp64 filter bank, t and thr against the fp64 masking model on the kernel's own X (and t): the bars of
+    this module (TOL, tonality_err, rel_elem <= thr_tol)."""
+    if x64 is not None:
+        Xo = MDCTOracle(N, "vorbis", np.float64).transform(x64)
+        assert rel_peak(host(X), Xo) <= xbar and rel_l2(host(X), Xo) <= xbar
+    o = PsychoOracle(48000, N, 64, compute_dtype=np.float64)
+    X64 = host(X).astype(np.float64)
+    t64 = o.tonality(X64)
+    if t is not None:
+        assert tonality_err(host(t), t64) <= 1.0
+    if thr is not None:
+        tt = t64 if t_in is None else host(t_in).astype(np.float64)
+        assert rel_elem(host(thr), o.global_masking_threshold(X64, tt, drown)) <= thr_tol
+
+
+@pytest.mark.parametrize("spreading", ["f32", "bf16_mfma", "bf16x2_mfma"])
+@pytest.mark.parametrize("pcm", [False, True])
+@pytest.mark.parametrize("N,C", [(1024, 2), (1024, 1), (1024, 3), (2048, 2), (2048, 1), (2048, 3)])
+def test_wave_level_encode_in_every_input_format_and_spreading_form(N, C, pcm, spreading):
+    """k_fwd_fast / k_psy_fast are instantiated per (filters_n, row layout, float32 or 16-bit PCM input, form of the spreading
+    product); the suite ran the default form on float32 and a few others.  Every combination the launchers take: encode()
+    and the stand-alone tonality / threshold calls of the same plan, each against the fp64 oracle (the threshold at the bar
+    of the plan's spreading form), 16-bit PCM against the float path fed pcm / 32768, a drown other than 0, an odd batch."""
+    B, K, drown = 3, 5, 0.2
+    pcm16 = torch.randint(-32768, 32768, (B, K * N, C), device="cuda", dtype=torch.int16)
+    pcm16[1] //= 64                                                  # a quiet clip
+    xf = pcm16.float() / 32768.0
+    codec = audiocodec_amd.AudioCodec(48000, N, spreading=spreading)
+    assert codec.psy.plan_spreading() == spreading and codec.psy.is_fast()
+    tol = SPREAD_TOL[spreading] if C <= 2 else TOL          # (the matrix-core forms serve mono and stereo)
+    X, t, thr = codec.encode(pcm16 if pcm else xf, drown)
+    _vs_oracle(N, host(xf).astype(np.float64), X, t, thr, drown, tol)
+    ts = codec.psy.tonality(X)
+    thrs = codec.psy.global_masking_threshold(X, ts, drown)
+    _vs_oracle(N, None, X, ts, thrs, drown, tol, t_in=ts)
+    assert tonality_err(t, ts) <= 1.0 and float(((thr - thrs).abs() / thrs).max()) <= tol
+    if pcm:
+        Xf, tf, thrf = codec.encode(xf, drown)
+        assert float((X - Xf).abs().max()) <= 2e-6 * float(Xf.abs().max())
+        assert float((t - tf).abs().max()) <= 1e-5 and float(((thr - thrf).abs() / thrf).max()) <= max(tol, 1e-4)
+
+
+@pytest.mark.parametrize("N,C", [(1024, 2), (1024, 1), (2048, 2), (2048, 1), (1024, 3), (2048, 3)])
+def test_pcm16_transform_without_the_masking_model(N, C):
+    """ac_mdct_forward_pcm16 (the C ABI's transform of 16-bit PCM; the package reaches it only inside encode()): the
+    wave-level kernels' PCM instances without the fused masking model -- bit-identical to the float path fed pcm / 32768
+    for mono / stereo (test_pcm16_at_the_boundary), to float32 rounding for three channels (two routes), and against the
+    oracle."""
+    from audiocodec_amd import _host
+    B, K = 3, 5
+    pcm = torch.randint(-32768, 32768, (B, K * N, C), device="cuda", dtype=torch.int16)
+    m = audiocodec_amd.MDCTransformer(N)
+    X = torch.empty((B, K + 1, N, C), device="cuda")
+    _lib.check(_lib.load().ac_mdct_forward_pcm16(m._plan(pcm.device), _host.ptr(pcm), _host.ptr(X), B, K, C,
+                                                 _host.stream_ptr(pcm.device)))
+    xf = pcm.float() / 32768.0
+    Xf = m.transform(xf)
+    if C <= 2:
+        assert torch.equal(X, Xf)
+    else:
+        assert float((X - Xf).abs().max()) <= 2e-6 * float(Xf.abs().max())
+    Xo = MDCTOracle(N, "vorbis", np.float64).transform(host(xf).astype(np.float64))
+    assert rel_peak(host(X), Xo) <= TOL and rel_l2(host(X), Xo) <= TOL
+
+
+@pytest.mark.parametrize("spreading", ["f32", "bf16_mfma", "bf16x2_mfma"])
+@pytest.mark.parametrize("N,C", [(1024, 2), (1024, 1), (1024, 3), (2048, 2), (2048, 1), (2048, 3)])
+def test_streaming_encode_where_the_filter_bank_is_not_wave_level(N, C, spreading):
+    """A rectangular window keeps the filter bank off the wave-level kernels while the masking model stays on them: the
+    streaming encode then runs tonality and threshold in ONE pass over the chunk's spectrum (k_psy_fast with both outputs),
+    an instance per row layout and spreading form that no other route launches for stereo (bfloat16 streams are wave-level
+    throughout and have no such pass but at 2048 mono).  Chunked against the stand-alone calls on the same spectrum, and
+    both against the oracle: TOL / tonality_err, the threshold at the bar of the plan's spreading form."""
+    B, drown = 3, 0.2
+    codec = audiocodec_amd.AudioCodec(48000, N, window_type="rect", spreading=spreading)
+    assert codec.psy.is_fast() and codec.mdct.tier(C) != 3
+    g = torch.Generator(device="cuda").manual_seed(N + C)
+    x = torch.empty(B, 6 * N, C, device="cuda").uniform_(-1, 1, generator=g)
+    st = codec.stream(B, C)
+    parts = [st.encode_chunk(x[:, a * N:b * N].contiguous(), drown=drown) for a, b in ((0, 2), (2, 3), (3, 6))]
+    st.close()
+    X, t, thr = (torch.cat([p[i] for p in parts], dim=1) for i in range(3))
+    ts = codec.psy.tonality(X)
+    thrs = codec.psy.global_masking_threshold(X, ts, drown)
+    o = PsychoOracle(48000, N, 64, compute_dtype=np.float64)
+    X64 = host(X).astype(np.float64)
+    t64 = o.tonality(X64)
+    tol = SPREAD_TOL[spreading] if C <= 2 else TOL      # (the matrix-core forms serve mono and stereo)
+    assert tonality_err(t, ts) <= 1.0 and float(((thr - thrs).abs() / thrs).max()) <= tol
+    assert tonality_err(host(t), t64) <= 1.0
+    assert rel_elem(host(thr), o.global_masking_threshold(X64, t64, drown)) <= tol
+
+
+@pytest.mark.parametrize("N", [120, 256, 480, 1024, 2048, 4096])
+@pytest.mark.parametrize("C", [3, 5])
+def test_masking_model_strided_pairs_at_every_granule_count(N, C, monkeypatch):
+    """k_psy_runs on the channel pairs of three and five channels (AC_PSY_NOTEAM=1; the default at 1, 2 and 32 granule registers
+    per lane, where there is no team form), one instance per register count and per set of outputs: tonality alone, the
+    threshold from a given tonality, and both in one pass (encode() of more than two channels) -- each against the oracle."""
+    monkeypatch.setenv("AC_PSY_NOTEAM", "1")
+    B, K, drown = 3, 4, 0.2
+    codec = audiocodec_amd.AudioCodec(48000, N)
+    x = (torch.rand((B, K * N, C), device="cuda") * 2 - 1) * torch.rand((B, 1, C), device="cuda")
+    X, t, thr = codec.encode(x, drown)
+    _vs_oracle(N, host(x).astype(np.float64), X, t, thr, drown, TOL)
+    ts = codec.psy.tonality(X)
+    thrs = codec.psy.global_masking_threshold(X, ts, drown)
+    _vs_oracle(N, None, X, ts, thrs, drown, TOL, t_in=ts)
+    assert tonality_err(t, ts) <= 1.0 and float(((thr - thrs).abs() / thrs).max()) <= TOL
+
+
+def _run_child(code, env, tmp_path, name, *args):
+    import os, subprocess, sys
+    from conftest import ROOT
+    f = str(tmp_path / name)
+    r = subprocess.run([sys.executable, "-c", code, f, *args], cwd=ROOT, env=dict(os.environ, **env), capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return np.load(f)
+
+
+def test_masking_model_band_walk_at_every_granule_count(tmp_path):
+    """k_psy_mid, the band walk the run-structured model replaced where a plan has a run image: AC_NO_RUNS=1 (read once per
+    process) puts it back on every plan.  One instance per granule-register count (filters_n 120 ... 3840), row layout
+    (stereo, three channels, mono with an odd batch) and set of outputs (tonality, threshold from a given tonality, both in
+    the un-fused encode()); the child returns what it computed and each is held to the oracle here."""
+    sizes, chans = (120, 240, 480, 960, 1920, 3840), (2, 3, 1)
+    code = ("import sys, numpy as np, torch, audiocodec_amd\n"
+            "out = {}\n"
+            "for N in %r:\n"
+            "    for C in %r:\n"
+            "        g = torch.Generator(device='cuda').manual_seed(N + C)\n"
+            "        x = torch.empty(3, 4 * N, C, device='cuda').uniform_(-1, 1, generator=g)\n"
+            "        x *= torch.empty(3, 1, C, device='cuda').uniform_(1e-3, 1, generator=g)\n"
+            "        codec = audiocodec_amd.AudioCodec(48000, N)\n"
+            "        assert codec.psy.tier() == 1 and codec.encode_launches(C) >= 2\n"
+            "        X, t, thr = codec.encode(x, 0.2)\n"
+            "        ts = codec.psy.tonality(X)\n"
+            "        thrs = codec.psy.global_masking_threshold(X, ts, 0.2)\n"
+            "        for k, v in (('x', x), ('X', X), ('t', t), ('thr', thr), ('ts', ts), ('thrs', thrs)):\n"
+            "            out['%%s_%%d_%%d' %% (k, N, C)] = v.cpu().numpy()\n"
+            "np.savez(sys.argv[1], **out)\n" % (sizes, chans))
+    got = _run_child(code, {"AC_NO_RUNS": "1", "AC_LDS_WAVE_NOFUSE": "1"}, tmp_path, "walk.npz")
+    for N in sizes:
+        o = PsychoOracle(48000, N, 64, compute_dtype=np.float64)
+        om = MDCTOracle(N, "vorbis", np.float64)
+        for C in chans:
+            x, X, t, thr, ts, thrs = (got["%s_%d_%d" % (k, N, C)] for k in ("x", "X", "t", "thr", "ts", "thrs"))
+            Xo = om.transform(x.astype(np.float64))
+            assert rel_peak(X, Xo) <= TOL and rel_l2(X, Xo) <= TOL, (N, C)
+            X64 = X.astype(np.float64)
+            t64 = o.tonality(X64)
+            assert tonality_err(t, t64) <= 1.0 and tonality_err(ts, t64) <= 1.0, (N, C)
+            assert rel_elem(thr, o.global_masking_threshold(X64, t64, 0.2)) <= TOL, (N, C)
+            assert rel_elem(thrs, o.global_masking_threshold(X64, ts.astype(np.float64), 0.2)) <= TOL, (N, C)
+
+
+def test_wave_level_kernels_on_more_than_two_float32_channels(tmp_path):
+    """float32 tensors of three or more channels run the channel-pair instances of the LDS-FFT tier; with those off
+    (AC_LDS_WAVE_NOVEC=1, read once per process) the wave-level kernels' strided form takes them -- the form 16-bit PCM of
+    three channels always takes, here in its float32 instances: transform, inverse_transform and encode() with the float32
+    spreading product at 1024 and 2048, three and five channels, against the oracle."""
+    sizes, chans = (1024, 2048), (3, 5)
+    code = ("import sys, numpy as np, torch, audiocodec_amd\n"
+            "out = {}\n"
+            "for N in %r:\n"
+            "    for C in %r:\n"
+            "        g = torch.Generator(device='cuda').manual_seed(N + C)\n"
+            "        x = torch.empty(3, 5 * N, C, device='cuda').uniform_(-1, 1, generator=g)\n"
+            "        codec = audiocodec_amd.AudioCodec(48000, N, spreading='f32')\n"
+            "        assert codec.mdct.tier(C) == 3\n"
+            "        X, t, thr = codec.encode(x, 0.2)\n"
+            "        Xu = codec.mdct.transform(x)\n"
+            "        y = codec.mdct.inverse_transform(Xu)\n"
+            "        for k, v in (('x', x), ('X', X), ('t', t), ('thr', thr), ('Xu', Xu), ('y', y)):\n"
+            "            out['%%s_%%d_%%d' %% (k, N, C)] = v.cpu().numpy()\n"
+            "np.savez(sys.argv[1], **out)\n" % (sizes, chans))
+    got = _run_child(code, {"AC_LDS_WAVE_NOVEC": "1"}, tmp_path, "novec.npz")
+    for N in sizes:
+        o = PsychoOracle(48000, N, 64, compute_dtype=np.float64)
+        om = MDCTOracle(N, "vorbis", np.float64)
+        for C in chans:
+            x, X, t, thr, Xu, y = (got["%s_%d_%d" % (k, N, C)] for k in ("x", "X", "t", "thr", "Xu", "y"))
+            Xo = om.transform(x.astype(np.float64))
+            assert rel_peak(X, Xo) <= TOL and rel_l2(X, Xo) <= TOL, (N, C)
+            assert rel_peak(Xu, Xo) <= TOL and rel_l2(Xu, Xo) <= TOL, (N, C)
+            assert np.max(np.abs(y[:, N:-N] - x)) <= LSB and np.max(np.abs(y - om.inverse_transform(Xo))) <= LSB, (N, C)
+            X64 = X.astype(np.float64)
+            t64 = o.tonality(X64)
+            assert tonality_err(t, t64) <= 1.0, (N, C)
+            assert rel_elem(thr, o.global_masking_threshold(X64, t64, 0.2)) <= TOL, (N, C)
+
+
 # ---- streaming ------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("N,C,chunks", [(1024, 2, (3, 1, 4, 2)), (256, 1, (2, 2, 5)), (1024, 1, (5, 3)), (960, 2, (2, 3, 1)),
@@ -888,9 +1206,22 @@ def test_stream_run_duplex_equals_the_chain(N, C, k, K, masking):
     """ac_stream_run with synthesis on small chunks: analysis of chunk i + 1 and synthesis of chunk i share one launch
     (k_duplex_fast).  Same results, bit for bit, as the chunk-by-chunk calls of the streaming API -- and a caller that
     hands over ONE X buffer for all chunks (so the two halves would collide) gets the dependent chain, same results."""
+    _duplex_equals_the_chain(N, C, k, K, masking, None)
+
+
+@pytest.mark.parametrize("spreading", ["f32", "bf16x2_mfma"])
+def test_stream_run_duplex_with_each_spreading_product(spreading):
+    """k_duplex_fast has an instance per form of the spreading product it serves (float32, split bfloat16): the same checks
+    with the plan's form chosen, and the thresholds of the whole run against the oracle at the form's bar."""
+    _duplex_equals_the_chain(1024, 2, 7, 28, True, spreading)
+
+
+def _duplex_equals_the_chain(N, C, k, K, masking, spreading):
     g = torch.Generator(device="cuda").manual_seed(N + K + C)
     x = torch.empty(1, K * N, C, device="cuda").uniform_(-1, 1, generator=g)
-    codec = audiocodec_amd.AudioCodec(48000, N)
+    codec = audiocodec_amd.AudioCodec(48000, N, spreading=spreading)
+    if spreading is not None:
+        assert codec.psy.plan_spreading() == spreading
     st = codec.stream(1, C)
     X, t, thr, xh = st.run(x, k, masking=masking, drown=0.2)
     ref = codec.stream(1, C)
@@ -924,6 +1255,12 @@ def test_stream_run_duplex_equals_the_chain(N, C, k, K, masking):
     torch.cuda.synchronize()
     assert torch.equal(xh2[:, :n * k * N], xh[:, :n * k * N]) and torch.equal(Xone, Xs[n - 1])
     st.close(), ref.close(), st2.close()
+    if spreading is not None:
+        o = PsychoOracle(48000, N, 64, compute_dtype=np.float64)
+        X64 = host(X).astype(np.float64)
+        t64 = o.tonality(X64)
+        assert tonality_err(host(t), t64) <= 1.0
+        assert rel_elem(host(thr), o.global_masking_threshold(X64, t64, 0.2)) <= SPREAD_TOL[spreading]
 
 
 @pytest.mark.parametrize("N,C,k,K,masking", [(1024, 2, 16, 83, True), (1024, 1, 8, 40, False), (2048, 2, 8, 24, False),
@@ -1786,7 +2123,8 @@ def test_float32_kernels_vs_float64_kernels_at_full_size(N, K):
     assert worst_thr <= TOL, worst_thr                        # threshold of the float32 X and t (two rounding sources)
 
 
-@pytest.mark.parametrize("N,wt,C", [(1024, "vorbis", 2), (256, "sine", 1), (12, "vorbis", 3), (2048, "vorbis", 2), (64, "rect", 3)])
+@pytest.mark.parametrize("N,wt,C", [(1024, "vorbis", 2), (256, "sine", 1), (12, "vorbis", 3), (2048, "vorbis", 2), (64, "rect", 3),
+                                    (1920, "vorbis", 2), (250, "sine", 1)])   # (k_fwd_lds<bf16, false>: the workgroup form below 2048)
 def test_bfloat16_filter_bank(path, N, wt, C):
     """compute_dtype = bfloat16: bfloat16 tensors, float32 arithmetic.  Tolerance: the output rounding of bfloat16
     (2^-9 of each value) on top of the float32 kernels' own error -- 4e-3 of the frame's peak."""
@@ -1805,7 +2143,8 @@ def test_bfloat16_filter_bank(path, N, wt, C):
         assert np.max(np.abs(xh[:, N:-N] - x)) <= 2e-2       # round trip through bfloat16 coefficients
 
 
-@pytest.mark.parametrize("N,wt,C", [(1024, "vorbis", 2), (960, "vorbis", 2), (256, "sine", 1), (12, "vorbis", 3), (4096, "vorbis", 2), (64, "rect", 3)])
+@pytest.mark.parametrize("N,wt,C", [(1024, "vorbis", 2), (960, "vorbis", 2), (256, "sine", 1), (12, "vorbis", 3), (4096, "vorbis", 2), (64, "rect", 3),
+                                    (1920, "vorbis", 2), (250, "sine", 1)])   # (k_fwd_lds<half, false>: the workgroup form below 2048)
 def test_float16_filter_bank(path, N, wt, C):
     """compute_dtype = float16 (the reference's filter bank accepts it and up-casts inside its DCT-IV, mdctransformer.py:
     327-344): float16 tensors, float32 arithmetic.  Tolerance: the output rounding of float16 (2^-11 of each value) on top of

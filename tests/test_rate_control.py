@@ -181,7 +181,8 @@ def _check(psy, X, thr, R, kmin):
 @pytest.mark.parametrize("sr,N,M,C", [(48000, 1024, 64, 2), (48000, 1024, 64, 1), (48000, 1024, 64, 6),
                                       (48000, 2048, 64, 2), (48000, 2048, 64, 1), (48000, 960, 64, 2), (48000, 960, 64, 6),
                                       (48000, 128, 64, 2), (48000, 128, 64, 1), (48000, 64, 64, 6), (48000, 512, 64, 2),
-                                      (48000, 8192, 256, 2), (48000, 8192, 4096, 2), (48000, 1024, 600, 7)])
+                                      (48000, 8192, 256, 2), (48000, 8192, 4096, 2), (48000, 1024, 600, 7),
+                                      (48000, 512, 64, 1), (48000, 480, 64, 1)])   # (one channel in two passes of the block)
 def test_quantize_to_budget_bit_exact(sr, N, M, C):
     """Plans through every kernel instance (X in registers at N <= 1024 with one or two channels, re-read otherwise),
     channel groups (M = 4096: one channel per group; 600 bands x 7 channels: groups of 4, the last partial), scalar and
