@@ -112,6 +112,9 @@ PROTOTYPES = {
     "ac_unpack": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ac_quantize_budget": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_int, c_int, c_int, c_void_p]),
+    "ac_clip_budget_scratch_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "ac_quantize_clip_budget": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
 }
 
 _lock = threading.Lock()

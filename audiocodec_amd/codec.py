@@ -255,6 +255,38 @@ class AudioCodec:
         data, index = self.psy.pack(codes, sf)
         return data, index, offset
 
+    # ---- rate control per clip (extension) ------------------------------------------------
+    def clip_bits_for_bitrate(self, bits_per_second, frames_n, channels_n):
+        """The clip budget of a per-channel bitrate: frames_n * channels_n rows of :meth:`row_bits_for_bitrate` bits each,
+        rounded down to the 32 bits rows are padded to, so that a clip that met it takes at most that many bits of
+        ``pack()``'s data.  Pass it to :meth:`encode_quantized_clip_budget`."""
+        for name, v in (("frames_n", frames_n), ("channels_n", channels_n)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError("%s must be an int, got %s" % (name, type(v).__name__))
+            if v < 0:
+                raise ValueError("%s must not be negative, got %d" % (name, v))
+        return int(frames_n) * int(channels_n) * 32 * (self.row_bits_for_bitrate(bits_per_second) // 32)
+
+    def encode_quantized_clip_budget(self, x, clip_bits, min_offset=0, drown=0.0):
+        """:meth:`encode`, then :meth:`PsychoacousticModel.quantize_to_clip_budget` on its X and threshold: x [B, K*N, C]
+        -> (codes int16 [B, K+1, N, C], sf int8 [B, K+1, M, C], offset int16 [B, K+1, C], row_bits_out int32 [B, K+1, C],
+        clip_bits_out int64 [B]).  ``clip_bits`` is an int (e.g. :meth:`clip_bits_for_bitrate` with frames_n = K + 1) or
+        an int64 tensor [B].  float32 only, not differentiable."""
+        _host.require_float32(self.compute_dtype, "encode_quantized_clip_budget")
+        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+            raise ValueError("x requires a gradient: quantisation is not differentiable -- use encode() and "
+                             "psy.add_noise(), its differentiable stand-in")
+        X, _, thr = self.encode(x, drown)
+        return self.psy.quantize_to_clip_budget(X, thr, clip_bits, min_offset)
+
+    def encode_packed_clip_budget(self, x, clip_bits, min_offset=0, drown=0.0):
+        """:meth:`encode_quantized_clip_budget`, then :meth:`PsychoacousticModel.pack`: x [B, K*N, C] -> (data uint8
+        [nbytes], index int64 [B, K+1, C], offset int16 [B, K+1, C]).  A clip that met its budget T takes at most T / 8
+        bytes of ``data``; :meth:`decode_packed` reads the stream as it is.  Synchronises with the device; float32 only."""
+        codes, sf, offset, _, _ = self.encode_quantized_clip_budget(x, clip_bits, min_offset, drown)
+        data, index = self.psy.pack(codes, sf)
+        return data, index, offset
+
     def decode_packed(self, data, index, pcm16=False):
         """:meth:`PsychoacousticModel.unpack`, then :meth:`decode_quantized`: data uint8 [nbytes], index int64
         [B, K', C] -> x [B, (K'+1)*N, C] (``torch.int16`` with ``pcm16=True``); bit-equal to ``decode_quantized`` on the

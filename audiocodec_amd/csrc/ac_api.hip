@@ -1016,6 +1016,32 @@ int ac_quantize_budget(const ac_psy_plan* psy, const float* X, const float* thr,
                                 (hipStream_t)stream);
 }
 
+size_t ac_clip_budget_scratch_bytes(const ac_psy_plan* psy, int B, int F, int C) {
+  if (psy == nullptr || B <= 0 || F <= 0 || C <= 0) return 0;
+  return clip_budget_scratch_bytes(psy, B, (long long)F * C);
+}
+
+int ac_quantize_clip_budget(const ac_psy_plan* psy, const float* X, const float* thr, int64_t clip_bits,
+                            const int64_t* clip_bits_per_clip, int kmin, int16_t* codes, int8_t* sf, int16_t* offset,
+                            int32_t* row_bits_out, int16_t* clip_offset, int64_t* clip_bits_out, void* scratch, int B, int F,
+                            int C, void* stream) {
+  int st = check_quant(psy, B, F, C);
+  if (st) return st;
+  AC_REQUIRE(kmin >= -254 && kmin <= 254, "kmin (%d) outside [-254, 254]", kmin);
+  const long long floor_bits = (long long)F * C * 32 * ((5 * psy->M + 31) / 32);
+  AC_REQUIRE(clip_bits_per_clip != nullptr || clip_bits >= floor_bits,
+             "clip_bits (%lld) below frames * C * 32 * ceil(5 * bark_bands_n / 32) = %lld, the length of a clip that stores "
+             "no band", (long long)clip_bits, floor_bits);
+  if (B == 0 || F == 0 || C == 0) return AC_OK;
+  AC_REQUIRE(X != nullptr && thr != nullptr && codes != nullptr && sf != nullptr && offset != nullptr, "NULL tensor pointer");
+  AC_REQUIRE(scratch != nullptr, "scratch of ac_clip_budget_scratch_bytes() = %zu bytes is required",
+             ac_clip_budget_scratch_bytes(psy, B, F, C));
+  AC_REQUIRE_ALIGNED(X, thr, codes, sf, offset, clip_bits_per_clip, row_bits_out, clip_offset, clip_bits_out, scratch);
+  DeviceGuard guard(psy->device);
+  return launch_quantize_clip_budget(psy, X, thr, clip_bits, clip_bits_per_clip, kmin, codes, sf, offset, row_bits_out,
+                                     clip_offset, clip_bits_out, scratch, B, F, C, (hipStream_t)stream);
+}
+
 static bool decode_quantized_fuses(const ac_mdct_plan* mdct, int C) {
   return !g_force_generic && wave_level(mdct, C, 0, 1) && fast_inv_quant_serves(mdct, C);
 }

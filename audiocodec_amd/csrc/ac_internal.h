@@ -318,6 +318,14 @@ int launch_dequantize(const ac_psy_plan* p, const int16_t* codes, const int8_t* 
 int launch_quantize_budget(const ac_psy_plan* p, const float* X, const float* thr, int budget, const int32_t* row_budget,
                            int kmin, int16_t* codes, int8_t* sf, int16_t* offset, int32_t* row_bits, int B, int F, int C,
                            hipStream_t s);
+// rate control per clip (ac_clip_rate.hip): one budget for the F*C rows of a clip (clip_budget [B] int64,
+// or the scalar budget where it is NULL); row_bits, clip_offset and clip_bits may be NULL; scratch of
+// clip_budget_scratch_bytes(p, B, F*C) bytes
+size_t clip_budget_scratch_bytes(const ac_psy_plan* p, long long B, long long rows_per_clip);
+int launch_quantize_clip_budget(const ac_psy_plan* p, const float* X, const float* thr, int64_t budget,
+                                const int64_t* clip_budget, int kmin, int16_t* codes, int8_t* sf, int16_t* offset,
+                                int32_t* row_bits, int16_t* clip_offset, int64_t* clip_bits, void* scratch, int B, int F, int C,
+                                hipStream_t s);
 // packed bitstream (ac_pack.hip): codes, sf -> index [B,F,C] (row byte offsets) + total, data; and back
 size_t pack_scratch_bytes(long long rows);
 int launch_pack_index(const ac_psy_plan* p, const int16_t* codes, const int8_t* sf, int64_t* index, int64_t* total,

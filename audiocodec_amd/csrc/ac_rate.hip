@@ -12,85 +12,14 @@
 //      fixed step), so an evaluation of the row's length reads three LDS words per band and never touches the bins;
 //   3. every bin quantised with the step of its band at the row's offset.  Where a group's bins fit IT passes of the
 //      block and CGT channels (N <= 1024, one or two channels), X stays in registers from phase 1; otherwise it is re-read.
-#include <climits>
-
 #include "ac_internal.h"
-#include "ac_quant_dev.h"
+#include "ac_rate_dev.h"
 
 namespace ac {
 namespace {
 
 constexpr int kRateThreads = 256;
 constexpr int kRateLdsBytes = 32768;   // a group's slots: 12 bytes per (band, channel)
-constexpr int kRateMaxOffset = 254;
-
-__device__ __forceinline__ int qcode(float x, float r) {
-  return (int)fminf(fmaxf(__builtin_rintf(qmul(x, r)), -32767.f), 32767.f);
-}
-// zz(q) of section 8b for |q| <= 32767
-__device__ __forceinline__ uint32_t zigzag(int q) { return (uint32_t)((q << 1) ^ (q >> 31)); }
-
-// A band's slot after phase 2 starts: meta = (length << 8) | (sf0 & 0xff); 0 for an empty band, -1 for sf0 = -128 (both
-// store nothing at any offset)
-__device__ __forceinline__ int band_bits(int meta, int kx, int kn, int k) {
-  if (meta <= 0) return 0;
-  const int s = max(-127, min(127, (int)(int8_t)(meta & 0xff) + k));
-  const float r = quant_inv_step(s);
-  const uint32_t z = max(zigzag(qcode(key_value(kx), r)), zigzag(qcode(key_value(kn), r)));
-  const int w = z ? 32 - __builtin_clz(z) : 0;
-  return w ? 8 + w * (meta >> 8) : 0;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
-// the segmented reduction of k_quantize over one pass of the block: runs of equal band index along the wave
-struct BandRuns {
-  int key;        // band of the lane's bin, -1 past the last bin
-  bool head;      // the lane folds its run into the band's slot
-  bool same[6];   // lane + 2^k lies in the same run
-};
-
-__device__ __forceinline__ BandRuns band_runs(const uint16_t* __restrict__ band, int i, int N, int lane) {
-  BandRuns r;
-  const bool valid = i < N;
-  r.key = valid ? (int)band[i] : -1;
-  const int prev = __shfl_up(r.key, 1);
-  r.head = valid && (lane == 0 || prev != r.key);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    // (the shuffle outside the condition: under a divergent branch ds_bpermute would read 0 from the lanes it masks off)
-    const int d = 1 << k, kd = __shfl_down(r.key, d);
-    r.same[k] = (lane + d < 64) && kd == r.key;
-  }
-  return r;
-}
-
-__device__ __forceinline__ void fold(const BandRuns& r, bool valid, float x, float t, int* kt, int* kx, int* kn, int slot) {
-  int vt = INT_MAX, vx = INT_MIN, vn = INT_MAX;
-  if (valid) {
-    vt = (__builtin_isfinite(x) && __builtin_isfinite(t)) ? ordered_key(t) : INT_MIN;
-    vx = vn = ordered_key(x);
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const int d = 1 << k;
-    const int wt = __shfl_down(vt, d), wx = __shfl_down(vx, d), wn = __shfl_down(vn, d);
-    if (r.same[k]) {
-      vt = min(vt, wt);
-      vx = max(vx, wx);
-      vn = min(vn, wn);
-    }
-  }
-  if (r.head) {
-    atomicMin(&kt[slot], vt);
-    atomicMax(&kx[slot], vx);
-    atomicMin(&kn[slot], vn);
-  }
-}
 
 // grid (B*F rows, channel groups); block: a multiple of 64 threads.  IT > 0: N <= IT * blockDim and every group holds CGT
 // channels (X kept in registers); IT = 0: any N and group, X re-read in phase 3.

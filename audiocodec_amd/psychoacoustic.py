@@ -423,6 +423,55 @@ class PsychoacousticModel:
                 _host.stream_ptr(dev)))
         return codes, sf, offset, bits
 
+    # ---- rate control per clip (extension) ---------------------------------------
+    def quantize_to_clip_budget(self, mdct_amplitudes, masking_threshold, clip_bits, min_offset=0):
+        """:meth:`quantize_to_budget` with one budget for the whole clip: X, thr [B, F, N, C] float32 -> (codes int16
+        [B, F, N, C], sf int8 [B, F, M, C], offset int16 [B, F, C], row_bits_out int32 [B, F, C], clip_bits_out int64 [B]).
+
+        ``clip_bits`` is an int (at least F * C * 32 * ceil(5 * bark_bands_n / 32), the length of a clip that stores no
+        band) or an int64 tensor [B] of per-clip budgets.  A clip's rows, padded to 32 bits as :meth:`pack` stores them,
+        take the smallest offset k in ``[min_offset, 254]`` at which their total is at most the budget; the bits left
+        over then lower the first rows of the clip (frame by frame, channel by channel) to k - 1 as far as they reach.
+        ``clip_bits_out`` is the clip's length in ``pack()``'s data in bits; a clip that cannot meet its budget gets
+        offset 254 and ``clip_bits_out`` above it.  No host synchronisation; not differentiable; float32 only."""
+        _host.require_float32(self.compute_dtype, "the quantiser")
+        X = self._check_quant_tensor(mdct_amplitudes, "mdct_amplitudes", torch.float32)
+        B, F, N, C = X.shape
+        if N != self.filter_bands_n:
+            raise ValueError("axis 2 of mdct_amplitudes (%d) != filter_bands_n (%d)" % (N, self.filter_bands_n))
+        thr = self._check_quant_tensor(masking_threshold, "masking_threshold", torch.float32, X.shape, X.device)
+        if isinstance(min_offset, bool) or not isinstance(min_offset, (int, np.integer)):
+            raise TypeError("min_offset must be an int, got %s" % type(min_offset).__name__)
+        if not -254 <= int(min_offset) <= 254:
+            raise ValueError("min_offset (%d) outside [-254, 254]" % min_offset)
+        per_clip = None
+        scalar = 0
+        if isinstance(clip_bits, torch.Tensor):
+            per_clip = self._check_quant_tensor(clip_bits, "clip_bits", torch.int64, (B,), X.device, ndim=1)
+        elif isinstance(clip_bits, (int, np.integer)) and not isinstance(clip_bits, bool):
+            floor = F * C * 32 * ((5 * self.bark_bands_n + 31) // 32)
+            if not floor <= int(clip_bits) <= 2 ** 63 - 1:
+                raise ValueError("clip_bits (%d) below frames * channels * 32 * ceil(5 * bark_bands_n / 32) = %d, the length "
+                                 "of a clip that stores no band, or above int64" % (clip_bits, floor))
+            scalar = int(clip_bits)
+        else:
+            raise TypeError("clip_bits must be an int or an int64 tensor [B], got %s" % type(clip_bits).__name__)
+        dev = X.device
+        codes = torch.empty((B, F, N, C), dtype=torch.int16, device=dev)
+        sf = torch.empty((B, F, self.bark_bands_n, C), dtype=torch.int8, device=dev)
+        offset = torch.empty((B, F, C), dtype=torch.int16, device=dev)
+        bits = torch.empty((B, F, C), dtype=torch.int32, device=dev)
+        clip_out = torch.empty((B,), dtype=torch.int64, device=dev)
+        plan = self._plans.get(dev)
+        nscratch = int(self._lib.ac_clip_budget_scratch_bytes(plan, B, F, C))
+        scratch = torch.empty((nscratch,), dtype=torch.uint8, device=dev) if nscratch else None
+        with _host.on_device(dev):
+            _lib.check(self._lib.ac_quantize_clip_budget(
+                plan, _host.ptr(X), _host.ptr(thr), scalar, _host.ptr(per_clip) if per_clip is not None else None,
+                int(min_offset), _host.ptr(codes), _host.ptr(sf), _host.ptr(offset), _host.ptr(bits), None,
+                _host.ptr(clip_out), _host.ptr(scratch) if scratch is not None else None, B, F, C, _host.stream_ptr(dev)))
+        return codes, sf, offset, bits, clip_out
+
     # ---- packed bitstream of quantised spectra (extension; DESIGN.md section 8b) ------------------------
     def pack(self, codes, sf):
         """Packs :meth:`quantize` output into a bitstream: codes int16 [B, F, N, C], sf int8 [B, F, M, C] ->

@@ -46,7 +46,8 @@ extern "C" {
 
 #define AC_VERSION 171 /* 0.1.8 + the quantiser (int16 codes, int8 per-band scale factors: ac_quantize, ac_dequantize,
                           * ac_decode_quantized[_launches], ac_psy_scale_bands_host), its packed bitstream (ac_pack_index,
-                          * ac_pack, ac_unpack, ac_pack_scratch_bytes) and its rate control (ac_quantize_budget); additions
+                          * ac_pack, ac_unpack, ac_pack_scratch_bytes) and its rate control (ac_quantize_budget, per clip
+                          * ac_quantize_clip_budget, ac_clip_budget_scratch_bytes); additions
                           * only, so the number stays.
                           * 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
                           * with a 5-smooth half up to 8192, float32); masking model for general band layouts up to 4096 bins.
@@ -296,6 +297,23 @@ AC_API int ac_unpack(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes
 AC_API int ac_quantize_budget(const ac_psy_plan* psy, const float* X, const float* thr, int row_bits,
                               const int32_t* row_bits_per_row, int kmin, int16_t* codes, int8_t* sf, int16_t* offset,
                               int32_t* row_bits_out, int B, int F, int C, void* stream);
+
+/* Rate control per clip (extension): one budget for the F*C rows of a clip, r = f*C + c.  With bits_r(k)
+ * of ac_quantize_budget, len_r(k) = 32 * ceil(bits_r(k) / 32) is a row's packed length with its padding and total_b(k) the sum
+ * over the clip's rows.  k_b = the smallest k in [kmin, 254] with total_b(k) <= T_b, else 254.  Where k_b > kmin and
+ * total_b(k_b) <= T_b, the first p_b rows take the offset k_b - 1: with d_r = len_r(k_b - 1) - len_r(k_b), p_b is the number of
+ * rows whose inclusive prefix sum of d is at most T_b - total_b(k_b); otherwise p_b = 0.  Every other row takes k_b.
+ * ac_quantize_clip_budget: X, thr [B,F,N,C] float32 -> codes int16 [B,F,N,C], sf int8 [B,F,M,C], offset int16 [B,F,C] and,
+ *   each NULL or given, row_bits_out int32 [B,F,C] = bits_r(offset_r), clip_offset int16 [B] = k_b and clip_bits_out
+ *   int64 [B] = the sum of len_r(offset_r): the clip's bits in ac_pack's data (a budget not met shows as clip_bits_out > T_b).
+ *   T_b is clip_bits_per_clip[b] (device int64 [B], entries not checked) or, where that is NULL, clip_bits
+ *   (>= F * C * 32 * ceil(5M / 32)).  scratch: ac_clip_budget_scratch_bytes(psy, B, F, C) device bytes, 16-byte aligned; the
+ *   call allocates nothing and does not synchronise with the host.  kmin in [-254, 254]; plans as ac_quantize. */
+AC_API size_t ac_clip_budget_scratch_bytes(const ac_psy_plan* psy, int B, int F, int C);
+AC_API int ac_quantize_clip_budget(const ac_psy_plan* psy, const float* X, const float* thr, int64_t clip_bits,
+                                   const int64_t* clip_bits_per_clip, int kmin, int16_t* codes, int8_t* sf, int16_t* offset,
+                                   int32_t* row_bits_out, int16_t* clip_offset, int64_t* clip_bits_out, void* scratch, int B,
+                                   int F, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Streaming overlap-add (chunked transform with device-resident state).

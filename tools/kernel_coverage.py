@@ -14,7 +14,12 @@
           rocprofv3 --kernel-trace --stats -M --output-format csv -d DIR/<file> -- python -m pytest tests/<file>.py -q -m gpu
 
       (-M: mangled, untruncated names, so that a traced name equals a symbol).  Prints, for every symbol, the test files
-      that launched it and how often; with --manifest, (re)writes that column of tests/kernel_coverage.txt.
+      that launched it and how often; with --manifest, (re)writes that column of tests/kernel_coverage.txt.  With
+      --part NAME instead, writes tests/kernel_coverage.d/NAME.txt from a traced run of the new test files alone: the rows
+      of the kernels the manifest does not list yet and the code letters of the test files it does not name, and nothing
+      else -- how a change that adds kernels records them while every existing row stays as the last full trace wrote
+      it.  read_manifest() reads the manifest and every part; the next full re-trace (--manifest) takes the parts' rows
+      and letters into the manifest and removes the part files.
 
 The library's own kernels live in namespace ac (_ZN2ac..., or an anonymous namespace inside it); a traced name of that form
 that matches no symbol is an error.  Kernels of torch, rocBLAS, RCCL ... are ignored.
@@ -34,6 +39,7 @@ LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MANIFEST = os.path.join(ROOT, "tests", "kernel_coverage.txt")
+PARTS = os.path.join(ROOT, "tests", "kernel_coverage.d")      # additions to the manifest, one file per change (--part)
 
 
 def code_objects(lib):
@@ -166,29 +172,71 @@ def merge(lib, dirs):
 
 
 # ---- the manifest: tests/kernel_coverage.txt
-def read_manifest(path=MANIFEST):
-    """(header lines, codes {code: test file}, rows {symbol: (parent codes, head codes)})."""
+def part_files():
+    return sorted(glob.glob(os.path.join(PARTS, "*.txt")))
+
+
+def read_manifest(path=MANIFEST, parts=True, skip=None):
+    """(header lines, codes {code: test file}, rows {symbol: (parent codes, head codes)}) of the manifest and, for the
+    manifest of the tree, of every part under tests/kernel_coverage.d (but ``skip``).  A part may only add: a code letter
+    or a kernel named twice is an error.  Of a part's comment lines only its code letters join the header."""
     header, codes, rows = [], {}, {}
-    for ln in open(path).read().splitlines():
-        if ln.startswith("#"):
-            header.append(ln)
-            w = ln[1:].split()
-            if len(w) == 3 and w[0] == "code":
-                codes[w[1]] = w[2]
-        elif ln.strip():
-            w = ln.split()
-            assert len(w) == 3, ln
-            rows[w[0]] = (w[1], w[2])
+    files = [path]
+    if parts and os.path.abspath(path) == os.path.abspath(MANIFEST):
+        files += [f for f in part_files() if skip is None or os.path.abspath(f) != os.path.abspath(skip)]
+    for f in files:
+        for ln in open(f).read().splitlines():
+            if ln.startswith("#"):
+                w = ln[1:].split()
+                code = len(w) == 3 and w[0] == "code"
+                if code:
+                    assert w[1] not in codes, "%s: code %s is defined twice" % (f, w[1])
+                    codes[w[1]] = w[2]
+                if code or f == path:
+                    header.append(ln)
+            elif ln.strip():
+                w = ln.split()
+                assert len(w) == 3, ln
+                assert w[0] not in rows, "%s: kernel %s is listed twice" % (f, w[0])
+                rows[w[0]] = (w[1], w[2])
     return header, codes, rows
 
 
+def next_code(codes):
+    return next(c for c in "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz" if c not in codes)
+
+
+def write_part(cover, name):
+    """tests/kernel_coverage.d/NAME.txt: the kernels of cover that the manifest (and the other parts) do not list, with the
+    test files of cover that launched them; test files without a code letter get the next free one."""
+    out = os.path.join(PARTS, name + ".txt")
+    _, codes, rows = read_manifest(skip=out)
+    by_file = {v: k for k, v in codes.items()}
+    new = sorted(s for s in cover if s not in rows)
+    header = ["# Addition to tests/kernel_coverage.txt, in its format (tools/kernel_coverage.py merge LIB DIR --part %s):" % name,
+              "# the kernels that manifest does not list, from a traced run of the test files below.  The next full re-trace",
+              "# (merge --manifest) moves these rows and code letters into the manifest and removes this file."]
+    for f in sorted(set(f for s in new for f in cover[s])):
+        if f not in by_file:
+            code = next_code(codes)
+            codes[code], by_file[f] = f, code
+            header.append("# code %s %s" % (code, f))
+    os.makedirs(PARTS, exist_ok=True)
+    with open(out, "w") as fh:
+        fh.write("\n".join(header) + "\n")
+        for s in new:
+            fh.write("%s - %s\n" % (s, "".join(sorted(by_file[f] for f in cover[s])) or "-"))
+
+
 def write_column(cover, column, path=MANIFEST):
+    """(Re)writes one column of the manifest from a trace of the whole suite.  The parts are read with it, so their code
+    letters and first columns carry over, and are removed once the manifest holds their rows: one source again."""
     header, codes, rows = read_manifest(path) if os.path.exists(path) else ([], {}, {})
     by_file = {v: k for k, v in codes.items()}
     files = sorted(set(f for c in cover.values() for f in c))
     for f in files:
         if f not in by_file:
-            code = next(c for c in "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz" if c not in codes)
+            code = next_code(codes)
             codes[code], by_file[f] = f, code
             header.append("# code %s %s" % (code, f))
     out = {}
@@ -200,6 +248,9 @@ def write_column(cover, column, path=MANIFEST):
         fh.write("\n".join(header) + "\n")
         for s in sorted(out):
             fh.write("%s %s %s\n" % (s, out[s][0], out[s][1]))
+    if os.path.abspath(path) == os.path.abspath(MANIFEST):
+        for f in part_files():
+            os.remove(f)
 
 
 def main():
@@ -215,6 +266,7 @@ def main():
     b.add_argument("dirs", nargs="+")
     b.add_argument("--manifest", help="write this column of the manifest (default tests/kernel_coverage.txt)", nargs="?", const=MANIFEST)
     b.add_argument("--column", choices=("parent", "head"), default="head")
+    b.add_argument("--part", help="write tests/kernel_coverage.d/PART.txt (kernels the manifest does not list) instead")
     b.add_argument("--json", help="the full table {symbol: {test file: calls}}")
     b.add_argument("--demangle", action="store_true")
     args = ap.parse_args()
@@ -236,7 +288,9 @@ def main():
     print("%d of %d kernels launched, %d never" % (len(cover) - len(never), len(cover), len(never)), file=sys.stderr)
     if args.json:
         json.dump(cover, open(args.json, "w"), indent=0, sort_keys=True)
-    if args.manifest:
+    if args.part:
+        write_part(cover, args.part)
+    elif args.manifest:
         write_column(cover, args.column, args.manifest)
 
 

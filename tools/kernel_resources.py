@@ -16,7 +16,8 @@ for blk in re.split(r"remark: Function Name: ", err)[1:]:
         continue
     seen.add(name)
     dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-    dem = dem.replace("void ac::(anonymous namespace)::", "").split("(")[0]
+    # (a template instance demangles with its return type, a plain kernel without)
+    dem = dem.replace("void ac::(anonymous namespace)::", "").replace("ac::(anonymous namespace)::", "").split("(")[0]
 
     def g(k):
         m = re.search(re.escape(k) + r": (\d+)", blk)
