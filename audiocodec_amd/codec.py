@@ -183,15 +183,20 @@ class AudioCodec:
         return x
 
     # ---- quantised spectra (extension) ------------------------------------------------
-    def encode_quantized(self, x, drown=0.0):
-        """:meth:`encode`, then :meth:`PsychoacousticModel.quantize` on its X and threshold: x [B, K*N, C] (float or
-        ``torch.int16`` PCM) -> (codes int16 [B, K+1, N, C], sf int8 [B, K+1, M, C]).  Two launches; X, tonality and
-        threshold are temporaries.  float32 only, not differentiable."""
-        _host.require_float32(self.compute_dtype, "encode_quantized")
+    def _encode_for_quantizer(self, x, drown, what):
+        """X and the threshold of :meth:`encode` for the quantising method ``what``: float32 only, and no gradient."""
+        _host.require_float32(self.compute_dtype, what)
         if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
             raise ValueError("x requires a gradient: quantisation is not differentiable -- use encode() and "
                              "psy.add_noise(), its differentiable stand-in")
         X, _, thr = self.encode(x, drown)
+        return X, thr
+
+    def encode_quantized(self, x, drown=0.0):
+        """:meth:`encode`, then :meth:`PsychoacousticModel.quantize` on its X and threshold: x [B, K*N, C] (float or
+        ``torch.int16`` PCM) -> (codes int16 [B, K+1, N, C], sf int8 [B, K+1, M, C]).  Two launches; X, tonality and
+        threshold are temporaries.  float32 only, not differentiable."""
+        X, thr = self._encode_for_quantizer(x, drown, "encode_quantized")
         return self.psy.quantize(X, thr)
 
     def decode_quantized_launches(self, channels_n=2, device=None):
@@ -240,11 +245,7 @@ class AudioCodec:
         (codes int16 [B, K+1, N, C], sf int8 [B, K+1, M, C], offset int16 [B, K+1, C], row_bits_out int32 [B, K+1, C]).
         ``row_bits`` is an int (e.g. :meth:`row_bits_for_bitrate`) or an int32 tensor [B, K+1, C].  Two launches; float32
         only, not differentiable."""
-        _host.require_float32(self.compute_dtype, "encode_quantized_budget")
-        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
-            raise ValueError("x requires a gradient: quantisation is not differentiable -- use encode() and "
-                             "psy.add_noise(), its differentiable stand-in")
-        X, _, thr = self.encode(x, drown)
+        X, thr = self._encode_for_quantizer(x, drown, "encode_quantized_budget")
         return self.psy.quantize_to_budget(X, thr, row_bits, min_offset)
 
     def encode_packed_budget(self, x, row_bits, min_offset=0, drown=0.0):
@@ -272,11 +273,7 @@ class AudioCodec:
         -> (codes int16 [B, K+1, N, C], sf int8 [B, K+1, M, C], offset int16 [B, K+1, C], row_bits_out int32 [B, K+1, C],
         clip_bits_out int64 [B]).  ``clip_bits`` is an int (e.g. :meth:`clip_bits_for_bitrate` with frames_n = K + 1) or
         an int64 tensor [B].  float32 only, not differentiable."""
-        _host.require_float32(self.compute_dtype, "encode_quantized_clip_budget")
-        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
-            raise ValueError("x requires a gradient: quantisation is not differentiable -- use encode() and "
-                             "psy.add_noise(), its differentiable stand-in")
-        X, _, thr = self.encode(x, drown)
+        X, thr = self._encode_for_quantizer(x, drown, "encode_quantized_clip_budget")
         return self.psy.quantize_to_clip_budget(X, thr, clip_bits, min_offset)
 
     def encode_packed_clip_budget(self, x, clip_bits, min_offset=0, drown=0.0):

@@ -3,12 +3,16 @@
 // as the remaining bits reach.
 //
 //   k_clip_stats   X, thr [B,F,N,C] -> per (row, band) the three words band_bits() reads (meta with sf0, largest and
-//                  smallest X key): stat [B*F*C][3][M] int32
+//                  smallest X key): stat [B*F*C][3][M] int32 (band_stats and band_meta of ac_rate_dev.h)
 //   k_clip_total   one bisection step: adds the clip's total length at the step's offset into total[step][b]
 //   k_clip_rows    each row's bits at k_b and at k_b - 1 -> rowbits [rows][2]; per (clip, split) the sums of the padded
 //                  lengths at k_b and of the steps d_r
-//   k_clip_fill    the scan of d_r over the clip's rows -> offset, row_bits_out, clip_offset, clip_bits_out
-//   k_clip_codes   the codes and scale factors at each row's offset (reads X, the meta words and the offsets)
+//   k_clip_fill    the scan of d_r over the clip's rows (block_scan of ac_band_dev.h) -> offset, row_bits_out, clip_offset,
+//                  clip_bits_out
+//   k_clip_codes   the codes and scale factors at each row's offset (reads X, the meta words and the offsets; band_sf,
+//                  store_sf and, for any group, quantize_bins)
+//
+// A row's bits at an offset are row_bits_at (ac_rate_dev.h), the count k_quantize_budget searches with.
 //
 // A clip's rows are cut into S equal splits, one workgroup each (grid B x S), so that many short clips and one long clip
 // both fill the chip.  Every sum is an integer sum: the results do not depend on the order of the additions.  No kernel
@@ -22,7 +26,7 @@
 namespace ac {
 namespace {
 
-constexpr int kClipThreads = 256;
+constexpr int kClipThreads = kRowThreads;
 constexpr int kClipWaves = kClipThreads / 64;
 constexpr int kClipLdsBytes = 32768;      // k_clip_stats: a group's slots, 12 bytes per (band, channel)
 constexpr int kClipMaxSteps = 9;          // ceil(log2(509)): bisection steps over [-254, 254]
@@ -69,14 +73,7 @@ __device__ __forceinline__ void clip_range(const i64* __restrict__ total, int B,
   }
 }
 
-// bits_r(k) of the row whose statistics start at st (the whole wave calls; lanes take the bands)
-__device__ __forceinline__ int row_bits_at(const int* __restrict__ st, int M, int lane, int k) {
-  int acc = 0;
-  for (int j = lane; j < M; j += 64) acc += band_bits(st[j], st[M + j], st[2 * M + j], k);
-  return 5 * M + wave_sum(acc);
-}
-
-// ---- band statistics: grid (B*F rows, channel groups), as k_quantize_budget's phase 1 and sf0 pass
+// ---- band statistics: grid (B*F rows, channel groups), k_quantize_budget's phase 1 and sf0 pass
 template <int CGT>
 __global__ __launch_bounds__(kClipThreads) void k_clip_stats(const float* __restrict__ X, const float* __restrict__ thr,
                                                               int* __restrict__ stat, const int32_t* __restrict__ off,
@@ -89,43 +86,7 @@ __global__ __launch_bounds__(kClipThreads) void k_clip_stats(const float* __rest
   const int c0 = blockIdx.y * CG, cg = CGT > 0 ? CGT : min(CG, C - c0);
   const size_t row = (size_t)blockIdx.x;
   const size_t rowN = row * (size_t)N * C;
-  for (int s = threadIdx.x; s < slots; s += blockDim.x) {
-    kt[s] = INT_MAX;
-    kx[s] = INT_MIN;
-    kn[s] = INT_MAX;
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  for (int base = 0; base < N; base += blockDim.x) {
-    const int i = base + (int)threadIdx.x;
-    const bool valid = i < N;
-    const BandRuns r = band_runs(band, i, N, lane);
-    if constexpr (CGT > 0) {
-      float x[CGT], t[CGT];
-#pragma unroll
-      for (int c = 0; c < CGT; ++c) {
-        x[c] = t[c] = 0.f;
-        if (valid) {
-          const size_t e = rowN + (size_t)i * C + c0 + c;
-          x[c] = X[e];
-          t[c] = thr[e];
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < CGT; ++c) fold(r, valid, x[c], t[c], kt, kx, kn, r.key * CG + c);
-    } else {
-      for (int c = 0; c < cg; ++c) {
-        float x = 0.f, t = 0.f;
-        if (valid) {
-          const size_t e = rowN + (size_t)i * C + c0 + c;
-          x = X[e];
-          t = thr[e];
-        }
-        fold(r, valid, x, t, kt, kx, kn, r.key * CG + c);
-      }
-    }
-  }
-  __syncthreads();
+  band_stats<CGT>(X, thr, rowN, band, N, M, C, c0, cg, CG, kt, kx, kn);
   // per (channel, band) in the order the words are stored: consecutive threads write consecutive bands
   for (int s = threadIdx.x; s < M * cg; s += blockDim.x) {
     const int c = s / M, j = s - c * M, slot = j * CG + c;
@@ -151,7 +112,7 @@ __global__ __launch_bounds__(kClipThreads) void k_clip_total(const int* __restri
   const int r0 = blockIdx.y * rps, r1 = min(R, r0 + rps);
   i64 acc = 0;
   for (int r = r0 + wave; r < r1; r += kClipWaves)
-    acc += padded(row_bits_at(stat + ((size_t)b * R + r) * (size_t)(3 * M), M, lane, mid));
+    acc += padded(row_bits_at(stat + ((size_t)b * R + r) * (size_t)(3 * M), 1, M, M, lane, mid));
   if (lane == 0) part[wave] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -178,8 +139,8 @@ __global__ __launch_bounds__(kClipThreads) void k_clip_rows(const int* __restric
   i64 len = 0, step_sum = 0;
   for (int r = r0 + wave; r < r1; r += kClipWaves) {
     const int* st = stat + ((size_t)b * R + r) * (size_t)(3 * M);
-    const int at = row_bits_at(st, M, lane, k);
-    const int under = below ? row_bits_at(st, M, lane, k - 1) : at;
+    const int at = row_bits_at(st, 1, M, M, lane, k);
+    const int under = below ? row_bits_at(st, 1, M, M, lane, k - 1) : at;
     if (lane == 0) {
       rowbits[2 * ((size_t)b * R + r)] = at;
       rowbits[2 * ((size_t)b * R + r) + 1] = under;
@@ -208,7 +169,7 @@ __global__ __launch_bounds__(kClipThreads) void k_clip_fill(const i64* __restric
                                                              i64* __restrict__ clip_bits, i64 budget,
                                                              const i64* __restrict__ clip_budget, int kmin, int steps, int B,
                                                              int R, int rps) {
-  __shared__ i64 wsum[kClipWaves];
+  __shared__ uint64_t sc[16];
   __shared__ i64 wbest[kClipWaves];
   const int b = blockIdx.x, S = gridDim.y, me = blockIdx.y;
   const i64 T = clip_budget ? clip_budget[b] : budget;
@@ -238,30 +199,16 @@ __global__ __launch_bounds__(kClipThreads) void k_clip_fill(const i64* __restric
       at = rowbits[2 * ((size_t)b * R + r)];
       under = rowbits[2 * ((size_t)b * R + r) + 1];
     }
-    i64 v = padded(under) - padded(at);
-    // inclusive scan over the workgroup: along the wave, then over the waves' sums
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const i64 u = __shfl_up(v, d);
-      if (lane >= d) v += u;
-    }
-    if (lane == 63) wsum[wave] = v;
-    __syncthreads();
-    i64 before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kClipWaves; ++w) {
-      if (w < wave) before += wsum[w];
-      all += wsum[w];
-    }
-    const i64 incl = carry + before + v;
+    const i64 v = padded(under) - padded(at);
+    uint64_t all;
+    const i64 incl = carry + (i64)block_scan<kClipWaves>((uint64_t)v, &all, sc) + v;
     const bool lower = fill && incl <= left;
     if (valid) {
       offset[(size_t)b * R + r] = (int16_t)(lower ? k - 1 : k);
       if (row_bits) row_bits[(size_t)b * R + r] = lower ? under : at;
       if (lower) best = max(best, incl);
     }
-    carry += all;
-    __syncthreads();
+    carry += (i64)all;
   }
   if (me != last) return;
   best = max(best, __shfl_xor(best, 32));
@@ -293,12 +240,9 @@ __global__ __launch_bounds__(kClipThreads) void k_clip_codes(const float* __rest
   for (int s = threadIdx.x; s < M * cg; s += blockDim.x) {
     const int c = s / M, j = s - c * M;
     const size_t rc = row * C + c0 + c;
-    const int q = band_sf(stat[rc * (size_t)(3 * M) + j], (int)offset[rc]);
-    sfrow[(size_t)j * C + c] = (int8_t)q;
-    inv[j * CG + c] = q == -128 ? __builtin_nanf("") : quant_inv_step(q);
+    store_sf(band_sf(stat[rc * (size_t)(3 * M) + j], (int)offset[rc]), &sfrow[(size_t)j * C + c], &inv[j * CG + c]);
   }
   __syncthreads();
-  auto code = [](float x, float r) { return __builtin_isnan(r) ? (short)0 : (short)qcode(x, r); };
   if constexpr (CGT == 2) {
     const float4* X4 = reinterpret_cast<const float4*>(X + rowN);
     short4* out = reinterpret_cast<short4*>(codes + rowN);
@@ -306,10 +250,10 @@ __global__ __launch_bounds__(kClipThreads) void k_clip_codes(const float* __rest
       const int j0 = band[2 * p], j1 = band[2 * p + 1];
       const float4 x = X4[p];
       short4 q;
-      q.x = code(x.x, inv[j0 * 2]);
-      q.y = code(x.y, inv[j0 * 2 + 1]);
-      q.z = code(x.z, inv[j1 * 2]);
-      q.w = code(x.w, inv[j1 * 2 + 1]);
+      q.x = code_or_zero(x.x, inv[j0 * 2]);
+      q.y = code_or_zero(x.y, inv[j0 * 2 + 1]);
+      q.z = code_or_zero(x.z, inv[j1 * 2]);
+      q.w = code_or_zero(x.w, inv[j1 * 2 + 1]);
       out[p] = q;
     }
   } else if constexpr (CGT == 1) {
@@ -318,18 +262,12 @@ __global__ __launch_bounds__(kClipThreads) void k_clip_codes(const float* __rest
     for (int p = threadIdx.x; p < N / 2; p += blockDim.x) {
       const float2 x = X2[p];
       short2 q;
-      q.x = code(x.x, inv[band[2 * p]]);
-      q.y = code(x.y, inv[band[2 * p + 1]]);
+      q.x = code_or_zero(x.x, inv[band[2 * p]]);
+      q.y = code_or_zero(x.y, inv[band[2 * p + 1]]);
       out[p] = q;
     }
   } else {
-    for (int i = threadIdx.x; i < N; i += blockDim.x) {
-      const int j = band[i];
-      for (int c = 0; c < cg; ++c) {
-        const size_t e = rowN + (size_t)i * C + c0 + c;
-        codes[e] = code(X[e], inv[j * CG + c]);
-      }
-    }
+    quantize_bins(X, codes, rowN, band, inv, N, C, c0, cg, CG);
   }
 }
 
@@ -341,13 +279,11 @@ int launch_quantize_clip_budget(const ac_psy_plan* p, const float* X, const floa
                                 const int64_t* clip_budget, int kmin, int16_t* codes, int8_t* sf, int16_t* offset,
                                 int32_t* row_bits, int16_t* clip_offset, int64_t* clip_bits, void* scratch, int B, int F, int C,
                                 hipStream_t s) {
-  const long long rows = (long long)B * F, R = (long long)F * C;
-  if (rows == 0 || C == 0) return AC_OK;
-  if (rows > 2147483647ll || R > 2147483647ll) {
-    set_error("problem too large for one launch (%lld rows, %lld rows per clip)", rows, R);
-    return AC_EINVAL;
-  }
+  const long long R = (long long)F * C;
+  if ((long long)B * F == 0 || C == 0) return AC_OK;
   const int M = p->M, N = p->N;
+  RowLaunch rl;
+  if (int st = row_launch(p, B, F, C, lds_group(C, kClipLdsBytes, 12 * M), &rl, R)) return st;
   const ClipLayout l = clip_layout(M, B, R);
   char* base = static_cast<char*>(scratch);
   int* stat = reinterpret_cast<int*>(base + l.stat);
@@ -356,11 +292,8 @@ int launch_quantize_clip_budget(const ac_psy_plan* p, const float* X, const floa
   int* rowbits = reinterpret_cast<int*>(base + l.rowbits);
   const i64* cb = reinterpret_cast<const i64*>(clip_budget);
 
-  const int CG = std::max(1, std::min(C, kClipLdsBytes / (12 * M)));
-  const int groups = (C + CG - 1) / CG;
-  const int threads = std::min(kClipThreads, (N + 63) / 64 * 64);
-  const int cgt = (CG == C && C <= 2) ? C : 0;
-  const dim3 row_grid((unsigned)rows, (unsigned)groups), clip_grid((unsigned)B, (unsigned)l.S);
+  const int CG = rl.CG, threads = rl.threads, cgt = rl.cgt;
+  const dim3 row_grid = rl.grid(), clip_grid((unsigned)B, (unsigned)l.S);
   int steps = 0;
   while ((1 << steps) < kRateMaxOffset - kmin + 1) ++steps;
   if (steps) AC_HIP_CHECK(hipMemsetAsync(total, 0, sizeof(i64) * steps * B, s));

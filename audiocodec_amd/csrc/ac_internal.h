@@ -3,6 +3,7 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <string>
@@ -309,6 +310,35 @@ int launch_add_noise_typed(const void* X, const void* thr, void* out, size_t n, 
 int launch_db(const float* a, float* out, size_t n, int norm, hipStream_t s);
 int launch_db_bwd(const float* a, const float* g, float* ga, size_t n, int norm, hipStream_t s);
 int launch_add_noise(const float* X, const float* thr, float* out, size_t n, uint64_t seed, hipStream_t s);
+// Launch geometry of the quantiser, pack and rate kernels: grid (B*F rows, channel groups), a block of whole waves.
+constexpr int kRowThreads = 256;   // the most threads of a block: the __launch_bounds__ of every kernel row_launch serves
+struct RowLaunch {
+  long long rows;   // B * F
+  int threads;      // the row's bins rounded up to whole waves, at most kRowThreads
+  int CG, groups;   // channels per workgroup, workgroups per row
+  int cgt;          // the kernels' CGT: C where one group is the whole of one or two channels, else 0
+  dim3 grid() const { return dim3((unsigned)rows, (unsigned)groups); }
+};
+// as many channels per group as lds_budget bytes hold at lds_per_channel bytes each, at least one
+inline int lds_group(int C, int lds_budget, int lds_per_channel) {
+  return std::max(1, std::min(C, lds_budget / lds_per_channel));
+}
+// Fills *out for [B,F,N,C] in groups of CG channels.  rows_per_clip >= 0 is checked and reported with the rows.
+inline int row_launch(const ac_psy_plan* p, int B, int F, int C, int CG, RowLaunch* out, long long rows_per_clip = -1) {
+  out->rows = (long long)B * F;
+  if (out->rows > 2147483647ll || rows_per_clip > 2147483647ll) {
+    char per_clip[48] = "";
+    if (rows_per_clip >= 0) snprintf(per_clip, sizeof per_clip, ", %lld rows per clip", rows_per_clip);
+    set_error("problem too large for one launch (%lld rows%s)", out->rows, per_clip);
+    return AC_EINVAL;
+  }
+  out->threads = std::min(kRowThreads, (p->N + 63) / 64 * 64);
+  out->CG = CG;
+  out->groups = (C + CG - 1) / CG;
+  out->cgt = (CG == C && C <= 2) ? C : 0;
+  return AC_OK;
+}
+
 // quantiser (ac_quant.hip): X, thr [B,F,N,C] -> codes int16 [B,F,N,C], sf int8 [B,F,M,C], and back
 int launch_quantize(const ac_psy_plan* p, const float* X, const float* thr, int16_t* codes, int8_t* sf, int B, int F, int C,
                     hipStream_t s);

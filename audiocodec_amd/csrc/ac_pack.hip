@@ -11,23 +11,22 @@
 //   k_unpack       data, index -> the canonical codes and sf (the row staged in LDS from loads clamped to nbytes)
 //
 // One workgroup per (clip, frame) and group of channels, as in k_quantize: the [N, C] block of a frame is read and written
-// coalesced.  The band maximum of zz(code) is k_quantize's run-wise segmented reduction with one ds_max per run.  A band's
-// bit offset comes from a block-wide exclusive scan over the bands of (stored bands, code bits) in one 64-bit sum.
-#include <climits>
-
+// coalesced.  The band maximum of zz(code) is the run-wise segmented reduction of ac_band_dev.h (band_runs, run_reduce) with
+// one ds_max per run.  A band's bit offset comes from a block-wide exclusive scan (block_scan, ac_band_dev.h) over the bands
+// of (stored bands, code bits) in one 64-bit sum.  zigzag is ac_quant_dev.h's; rows and threads come from row_launch
+// (ac_internal.h).
+#include "ac_band_dev.h"
 #include "ac_internal.h"
 
 namespace ac {
 namespace {
 
-constexpr int kPackThreads = 256;
+constexpr int kPackThreads = kRowThreads;
 constexpr int kPackLdsBytes = 32768;   // the LDS a workgroup's channel group aims at (one channel may take more, < 64 KB)
 constexpr int kScanThreads = 256;
 constexpr int kScanPer = 8;            // row lengths per thread of the scan
 constexpr int kScanTile = kScanThreads * kScanPer;
 
-// zz(q) = (q << 1) ^ (q >> 15) on the 16 bits of q: 0, -1, 1, -2, ... -> 0, 1, 2, 3, ...
-__device__ __forceinline__ uint32_t zigzag(int q) { return (uint32_t)((q << 1) ^ (q >> 15)) & 0xffffu; }
 __device__ __forceinline__ int16_t unzigzag(uint32_t z) { return (int16_t)((z >> 1) ^ (0u - (z & 1u))); }
 __device__ __forceinline__ uint32_t bit_length(uint32_t m) { return 32u - (uint32_t)__clz(m); }
 __device__ __forceinline__ bool stores(uint32_t w) { return w - 1u < 16u; }   // widths 1 .. 16 store an sf and codes
@@ -49,55 +48,18 @@ __device__ __forceinline__ uint32_t get_bits(const uint32_t* st, uint32_t p, uin
   return __builtin_amdgcn_alignbit(hi, lo, sh) & ((1u << w) - 1u);
 }
 
-// exclusive scan of v over the block (every thread calls it, blockDim.x <= 1024); *total = the sum.  sc: 16 LDS slots,
-// free again when it returns.
-__device__ uint64_t block_scan(uint64_t v, uint64_t* total, uint64_t* sc) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = (blockDim.x + 63) >> 6;
-  uint64_t x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t y = __shfl_up(x, d);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) sc[wave] = x;
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-  for (int k = 0; k < waves; ++k) {
-    const uint64_t s = sc[k];
-    before += k < wave ? s : 0;
-    all += s;
-  }
-  __syncthreads();
-  *total = all;
-  return before + x - v;
-}
-
-// the largest zz(code) of every band and channel of the group into mx[j * CG + c] (zeroed by the caller): k_quantize's
-// segmented reduction -- each wave takes 64 consecutive bins, reduces every run of one band with a log-step suffix maximum
-// across the lanes, and the run's first lane folds it into the band's slot with one ds_max
+// the largest zz(code) of every band and channel of the group into mx[j * CG + c] (zeroed by the caller): the segmented
+// reduction of ac_band_dev.h with one ds_max per run
 __device__ void band_max(const int16_t* __restrict__ codes, size_t rowN, const uint16_t* __restrict__ band, int N, int C,
                          int c0, int cg, int CG, uint32_t* mx) {
   const int lane = threadIdx.x & 63;
   for (int base = 0; base < N; base += blockDim.x) {
     const int i = base + (int)threadIdx.x;
-    const bool valid = i < N;
-    const int key = valid ? (int)band[i] : -1;
-    const int prev = __shfl_up(key, 1);
-    const bool head = valid && (lane == 0 || prev != key);
-    bool same[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const int d = 1 << k, kd = __shfl_down(key, d);   // (outside any condition, as in k_quantize)
-      same[k] = (lane + d < 64) && kd == key;
-    }
+    const BandRuns r = band_runs(band, i, N, lane);
     for (int c = 0; c < cg; ++c) {
-      uint32_t v = valid ? zigzag(codes[rowN + (size_t)i * C + c0 + c]) : 0u;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        const uint32_t w = __shfl_down(v, 1 << k);
-        if (same[k]) v = max(v, w);
-      }
-      if (head && v) atomicMax(&mx[key * CG + c], v);
+      uint32_t v = i < N ? zigzag(codes[rowN + (size_t)i * C + c0 + c]) : 0u;
+      v = run_reduce(r, v, MaxOp());
+      if (r.head && v) atomicMax(&mx[r.key * CG + c], v);
     }
   }
 }
@@ -360,14 +322,6 @@ int pack_group(int N, int M, int C, bool unpack) {
   return CG;
 }
 
-int check_rows(long long rows) {
-  if (rows > 2147483647ll) {
-    set_error("problem too large for one launch (%lld rows)", rows);
-    return AC_EINVAL;
-  }
-  return AC_OK;
-}
-
 }  // namespace
 
 size_t pack_scratch_bytes(long long R) {
@@ -377,15 +331,13 @@ size_t pack_scratch_bytes(long long R) {
 
 int launch_pack_index(const ac_psy_plan* p, const int16_t* codes, const int8_t* sf, int64_t* index, int64_t* total,
                       void* scratch, int B, int F, int C, hipStream_t s) {
-  const long long rows = (long long)B * F;
-  if (int st = check_rows(rows)) return st;
   const int M = p->M, N = p->N;
-  const int CG = std::max(1, std::min(C, kPackLdsBytes / (4 * M + 4)));
-  const int threads = std::min(kPackThreads, (N + 63) / 64 * 64);
-  hipLaunchKernelGGL(k_pack_sizes, dim3((unsigned)rows, (unsigned)((C + CG - 1) / CG)), dim3(threads),
-                     (size_t)4 * (M * CG + CG), s, codes, sf, index, p->d_qoff, p->d_qband, N, M, C, CG);
+  RowLaunch l;
+  if (int st = row_launch(p, B, F, C, lds_group(C, kPackLdsBytes, 4 * M + 4), &l)) return st;
+  hipLaunchKernelGGL(k_pack_sizes, l.grid(), dim3(l.threads), (size_t)4 * (M * l.CG + l.CG), s, codes, sf, index, p->d_qoff,
+                     p->d_qband, N, M, C, l.CG);
   AC_HIP_CHECK(hipGetLastError());
-  const long long R = rows * C, T = (R + kScanTile - 1) / kScanTile;
+  const long long R = l.rows * C, T = (R + kScanTile - 1) / kScanTile;
   if (T > 1) {
     int64_t* part = static_cast<int64_t*>(scratch);
     hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)T), dim3(kScanThreads), 0, s, index, part, (int64_t)R);
@@ -403,26 +355,22 @@ int launch_pack_index(const ac_psy_plan* p, const int16_t* codes, const int8_t* 
 
 int launch_pack(const ac_psy_plan* p, const int16_t* codes, const int8_t* sf, const int64_t* index, uint8_t* data, int B,
                 int F, int C, hipStream_t s) {
-  const long long rows = (long long)B * F;
-  if (int st = check_rows(rows)) return st;
   const int M = p->M, N = p->N;
-  const int CG = pack_group(N, M, C, false);
-  const int threads = std::min(kPackThreads, (N + 63) / 64 * 64);
-  hipLaunchKernelGGL(k_pack, dim3((unsigned)rows, (unsigned)((C + CG - 1) / CG)), dim3(threads),
-                     pack_lds_bytes(N, M, CG, false), s, codes, sf, index, data, p->d_qoff, p->d_qband, N, M, C, CG);
+  RowLaunch l;
+  if (int st = row_launch(p, B, F, C, pack_group(N, M, C, false), &l)) return st;
+  hipLaunchKernelGGL(k_pack, l.grid(), dim3(l.threads), pack_lds_bytes(N, M, l.CG, false), s, codes, sf, index, data,
+                     p->d_qoff, p->d_qband, N, M, C, l.CG);
   AC_HIP_CHECK(hipGetLastError());
   return AC_OK;
 }
 
 int launch_unpack(const ac_psy_plan* p, const uint8_t* data, int64_t nbytes, const int64_t* index, int16_t* codes, int8_t* sf,
                   int B, int F, int C, hipStream_t s) {
-  const long long rows = (long long)B * F;
-  if (int st = check_rows(rows)) return st;
   const int M = p->M, N = p->N;
-  const int CG = pack_group(N, M, C, true);
-  const int threads = std::min(kPackThreads, (N + 63) / 64 * 64);
-  hipLaunchKernelGGL(k_unpack, dim3((unsigned)rows, (unsigned)((C + CG - 1) / CG)), dim3(threads),
-                     pack_lds_bytes(N, M, CG, true), s, data, nbytes, index, codes, sf, p->d_qoff, p->d_qband, N, M, C, CG);
+  RowLaunch l;
+  if (int st = row_launch(p, B, F, C, pack_group(N, M, C, true), &l)) return st;
+  hipLaunchKernelGGL(k_unpack, l.grid(), dim3(l.threads), pack_lds_bytes(N, M, l.CG, true), s, data, nbytes, index, codes, sf,
+                     p->d_qoff, p->d_qband, N, M, C, l.CG);
   AC_HIP_CHECK(hipGetLastError());
   return AC_OK;
 }

@@ -1,7 +1,8 @@
-// Device helpers of the quantiser shared by its kernels (ac_quant.hip, ac_rate.hip) and the synthesis from codes
-// (ac_fast_inv_dev.h): one definition, so that every path quantises and dequantises bit for bit alike.  DESIGN.md section 8a has
-// the definition.
+// Device helpers of the quantiser shared by its kernels (ac_quant.hip, ac_pack.hip, ac_rate.hip, ac_clip_rate.hip) and the
+// synthesis from codes (ac_fast_inv_dev.h): one definition, so that every path quantises and dequantises bit for bit alike.
+// DESIGN.md section 8a has the definition.
 #pragma once
+#include <climits>
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
@@ -35,12 +36,26 @@ __device__ __forceinline__ float dequant(int code, int sf) {
   return qmul((float)code, __uint_as_float(st));
 }
 
+// code = clamp(rint(fp32(x * inv)), +-32767) for the inverse step r of the bin's band
+__device__ __forceinline__ int qcode(float x, float r) {
+  return (int)fminf(fmaxf(__builtin_rintf(qmul(x, r)), -32767.f), 32767.f);
+}
+// the code that is stored: 0 throughout a band with sf = -128, whose inverse step is kept as NaN
+__device__ __forceinline__ short code_or_zero(float x, float r) { return __builtin_isnan(r) ? (short)0 : (short)qcode(x, r); }
+// zz(q) = (q << 1) ^ (q >> 31): 0, -1, 1, -2, ... -> 0, 1, 2, 3, ...  For every int16 q this is the 16-bit form
+// ((q << 1) ^ (q >> 15)) & 0xffff of section 8b: q >> 15 and q >> 31 agree on a sign-extended int16, and zz(q) <= 65535
+__device__ __forceinline__ uint32_t zigzag(int q) { return (uint32_t)((q << 1) ^ (q >> 31)); }
+
 // float -> int key whose signed order is the float order (the map is its own inverse); NaN / Inf are flagged apart
 __device__ __forceinline__ int ordered_key(float v) {
   const int u = __float_as_int(v);
   return u >= 0 ? u : (u ^ 0x7fffffff);
 }
 __device__ __forceinline__ float key_value(int k) { return __int_as_float(k >= 0 ? k : (k ^ 0x7fffffff)); }
+// what a bin adds to its band's smallest-threshold key: INT_MIN marks a band that holds a NaN / Inf in X or thr
+__device__ __forceinline__ int thr_key(float x, float t) {
+  return (__builtin_isfinite(x) && __builtin_isfinite(t)) ? ordered_key(t) : INT_MIN;
+}
 
 // the largest s in [-127, 127] with fp32(step(s) * sqrt 3) <= m, else -127: a log2 estimate corrected against the criterion
 __device__ inline int scale_factor_of(float m) {

@@ -1,20 +1,13 @@
-// Device helpers shared by the rate-control kernels (ac_rate.hip, section 8c; ac_clip_rate.hip, section 8d): a band's packed
-// cost at an offset from its three statistics, and the run-wise segmented reduction that gathers them -- one definition, so
-// that the per-row and the per-clip search count a row's bits alike.
+// Device helpers shared by the rate-control kernels (ac_rate.hip, section 8c; ac_clip_rate.hip, section 8d): a band's three
+// statistics and the phase that gathers them (on the segmented reduction of ac_band_dev.h), a band's packed cost and scale
+// factor at an offset, and a row's bits at an offset -- one definition, so that the per-row and the per-clip search count a
+// row's bits alike.
 #pragma once
-#include <climits>
-
-#include "ac_quant_dev.h"
+#include "ac_band_dev.h"
 
 namespace ac {
 
 constexpr int kRateMaxOffset = 254;
-
-__device__ __forceinline__ int qcode(float x, float r) {
-  return (int)fminf(fmaxf(__builtin_rintf(qmul(x, r)), -32767.f), 32767.f);
-}
-// zz(q) of section 8b for |q| <= 32767
-__device__ __forceinline__ uint32_t zigzag(int q) { return (uint32_t)((q << 1) ^ (q >> 31)); }
 
 // A band's statistics once its sf0 is known: meta = (length << 8) | (sf0 & 0xff); 0 for an empty band, -1 for sf0 = -128
 // (both store nothing at any offset); kx, kn the ordered keys of the band's largest and smallest X
@@ -40,49 +33,81 @@ __device__ __forceinline__ int wave_sum(int v) {
   return v;
 }
 
-// the segmented reduction of k_quantize over one pass of the block: runs of equal band index along the wave
-struct BandRuns {
-  int key;        // band of the lane's bin, -1 past the last bin
-  bool head;      // the lane folds its run into the band's slot
-  bool same[6];   // lane + 2^k lies in the same run
-};
-
-__device__ __forceinline__ BandRuns band_runs(const uint16_t* __restrict__ band, int i, int N, int lane) {
-  BandRuns r;
-  const bool valid = i < N;
-  r.key = valid ? (int)band[i] : -1;
-  const int prev = __shfl_up(r.key, 1);
-  r.head = valid && (lane == 0 || prev != r.key);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    // (the shuffle outside the condition: under a divergent branch ds_bpermute would read 0 from the lanes it masks off)
-    const int d = 1 << k, kd = __shfl_down(r.key, d);
-    r.same[k] = (lane + d < 64) && kd == r.key;
+// bits_r(k) of a row from its bands' statistics: band j's meta, kx and kn at st[j * stride + {0, 1, 2} * plane] (the whole
+// wave calls; lanes take the bands)
+__device__ __forceinline__ int row_bits_at(const int* __restrict__ st, int stride, int plane, int M, int lane, int k) {
+  int acc = 0;
+  for (int j = lane; j < M; j += 64) {
+    const int* b = st + j * stride;
+    acc += band_bits(b[0], b[plane], b[2 * plane], k);
   }
-  return r;
+  return 5 * M + wave_sum(acc);
 }
 
+// a bin's x and thr folded into its band's slot: the smallest thr key and the largest and smallest X key
 __device__ __forceinline__ void fold(const BandRuns& r, bool valid, float x, float t, int* kt, int* kx, int* kn, int slot) {
   int vt = INT_MAX, vx = INT_MIN, vn = INT_MAX;
   if (valid) {
-    vt = (__builtin_isfinite(x) && __builtin_isfinite(t)) ? ordered_key(t) : INT_MIN;
+    vt = thr_key(x, t);
     vx = vn = ordered_key(x);
   }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const int d = 1 << k;
-    const int wt = __shfl_down(vt, d), wx = __shfl_down(vx, d), wn = __shfl_down(vn, d);
-    if (r.same[k]) {
-      vt = min(vt, wt);
-      vx = max(vx, wx);
-      vn = min(vn, wn);
-    }
-  }
+  vt = run_reduce(r, vt, MinOp());
+  vx = run_reduce(r, vx, MaxOp());
+  vn = run_reduce(r, vn, MinOp());
   if (r.head) {
     atomicMin(&kt[slot], vt);
     atomicMax(&kx[slot], vx);
     atomicMin(&kn[slot], vn);
   }
+}
+
+__device__ __forceinline__ void band_stats_init(int* kt, int* kx, int* kn, int slots) {
+  for (int s = threadIdx.x; s < slots; s += blockDim.x) {
+    kt[s] = INT_MAX;
+    kx[s] = INT_MIN;
+    kn[s] = INT_MAX;
+  }
+  __syncthreads();
+}
+
+// The band statistics phase of a row's channels c0 .. c0 + cg - 1 into kt, kx, kn [M][CG] (LDS): any N; X and thr are read
+// once and not kept.  CGT > 0: cg = CGT, a bin's loads of all its channels issued before the first fold.  Ends in a barrier.
+template <int CGT>
+__device__ __forceinline__ void band_stats(const float* __restrict__ X, const float* __restrict__ thr, size_t rowN,
+                                           const uint16_t* __restrict__ band, int N, int M, int C, int c0, int cg, int CG,
+                                           int* kt, int* kx, int* kn) {
+  band_stats_init(kt, kx, kn, M * CG);
+  const int lane = threadIdx.x & 63;
+  for (int base = 0; base < N; base += blockDim.x) {
+    const int i = base + (int)threadIdx.x;
+    const bool valid = i < N;
+    const BandRuns r = band_runs(band, i, N, lane);
+    if constexpr (CGT > 0) {
+      float x[CGT], t[CGT];
+#pragma unroll
+      for (int c = 0; c < CGT; ++c) {
+        x[c] = t[c] = 0.f;
+        if (valid) {
+          const size_t e = rowN + (size_t)i * C + c0 + c;
+          x[c] = X[e];
+          t[c] = thr[e];
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < CGT; ++c) fold(r, valid, x[c], t[c], kt, kx, kn, r.key * CG + c);
+    } else {
+      for (int c = 0; c < cg; ++c) {
+        float x = 0.f, t = 0.f;
+        if (valid) {
+          const size_t e = rowN + (size_t)i * C + c0 + c;
+          x = X[e];
+          t = thr[e];
+        }
+        fold(r, valid, x, t, kt, kx, kn, r.key * CG + c);
+      }
+    }
+  }
+  __syncthreads();
 }
 
 }  // namespace ac

@@ -338,6 +338,33 @@ class PsychoacousticModel:
             t = t.clone()
         return t
 
+    def _check_quant_inputs(self, mdct_amplitudes, masking_threshold):
+        """The checks every quantising method makes of X and thr [B, F, N, C] float32; returns them ready for the kernels."""
+        _host.require_float32(self.compute_dtype, "the quantiser")
+        X = self._check_quant_tensor(mdct_amplitudes, "mdct_amplitudes", torch.float32)
+        N = X.shape[2]
+        if N != self.filter_bands_n:
+            raise ValueError("axis 2 of mdct_amplitudes (%d) != filter_bands_n (%d)" % (N, self.filter_bands_n))
+        thr = self._check_quant_tensor(masking_threshold, "masking_threshold", torch.float32, X.shape, X.device)
+        return X, thr
+
+    @staticmethod
+    def _check_min_offset(min_offset):
+        if isinstance(min_offset, bool) or not isinstance(min_offset, (int, np.integer)):
+            raise TypeError("min_offset must be an int, got %s" % type(min_offset).__name__)
+        if not -254 <= int(min_offset) <= 254:
+            raise ValueError("min_offset (%d) outside [-254, 254]" % min_offset)
+
+    def _alloc_codes(self, X, rate=False):
+        """codes int16 [B, F, N, C] and sf int8 [B, F, M, C] for X; rate: also offset int16 and row bits int32 [B, F, C]."""
+        B, F, N, C = X.shape
+        out = (torch.empty((B, F, N, C), dtype=torch.int16, device=X.device),
+               torch.empty((B, F, self.bark_bands_n, C), dtype=torch.int8, device=X.device))
+        if rate:
+            out += (torch.empty((B, F, C), dtype=torch.int16, device=X.device),
+                    torch.empty((B, F, C), dtype=torch.int32, device=X.device))
+        return out
+
     def quantize(self, mdct_amplitudes, masking_threshold):
         """Perceptual quantiser: X, thr [B, F, N, C] float32 -> (codes int16 [B, F, N, C], sf int8 [B, F, M, C]).
 
@@ -345,14 +372,9 @@ class PsychoacousticModel:
         step * sqrt(3) <= the band's smallest threshold, so the error of a bin is at most thr / (2 sqrt 3), and the noise
         RMS at most the thr / 6 of :meth:`add_noise`; sf = -128 marks a band holding NaN / Inf (its codes are 0).  Not
         differentiable (:meth:`add_noise` is the differentiable stand-in); float32 only."""
-        _host.require_float32(self.compute_dtype, "the quantiser")
-        X = self._check_quant_tensor(mdct_amplitudes, "mdct_amplitudes", torch.float32)
+        X, thr = self._check_quant_inputs(mdct_amplitudes, masking_threshold)
         B, F, N, C = X.shape
-        if N != self.filter_bands_n:
-            raise ValueError("axis 2 of mdct_amplitudes (%d) != filter_bands_n (%d)" % (N, self.filter_bands_n))
-        thr = self._check_quant_tensor(masking_threshold, "masking_threshold", torch.float32, X.shape, X.device)
-        codes = torch.empty((B, F, N, C), dtype=torch.int16, device=X.device)
-        sf = torch.empty((B, F, self.bark_bands_n, C), dtype=torch.int8, device=X.device)
+        codes, sf = self._alloc_codes(X)
         with _host.on_device(X.device):
             _lib.check(self._lib.ac_quantize(self._plans.get(X.device), _host.ptr(X), _host.ptr(thr), _host.ptr(codes),
                                              _host.ptr(sf), B, F, C, _host.stream_ptr(X.device)))
@@ -390,16 +412,9 @@ class PsychoacousticModel:
         bands with NaN / Inf keep -128.  ``min_offset`` in [-254, 254]: 0 with an unlimited budget gives :meth:`quantize`,
         a fixed budget of 16N + 13M and a fixed ``min_offset`` is a constant-quality mode.  One launch; not
         differentiable; float32 only."""
-        _host.require_float32(self.compute_dtype, "the quantiser")
-        X = self._check_quant_tensor(mdct_amplitudes, "mdct_amplitudes", torch.float32)
+        X, thr = self._check_quant_inputs(mdct_amplitudes, masking_threshold)
         B, F, N, C = X.shape
-        if N != self.filter_bands_n:
-            raise ValueError("axis 2 of mdct_amplitudes (%d) != filter_bands_n (%d)" % (N, self.filter_bands_n))
-        thr = self._check_quant_tensor(masking_threshold, "masking_threshold", torch.float32, X.shape, X.device)
-        if isinstance(min_offset, bool) or not isinstance(min_offset, (int, np.integer)):
-            raise TypeError("min_offset must be an int, got %s" % type(min_offset).__name__)
-        if not -254 <= int(min_offset) <= 254:
-            raise ValueError("min_offset (%d) outside [-254, 254]" % min_offset)
+        self._check_min_offset(min_offset)
         per_row = None
         scalar = 0
         if isinstance(row_bits, torch.Tensor):
@@ -412,10 +427,7 @@ class PsychoacousticModel:
         else:
             raise TypeError("row_bits must be an int or an int32 tensor [B, F, C], got %s" % type(row_bits).__name__)
         dev = X.device
-        codes = torch.empty((B, F, N, C), dtype=torch.int16, device=dev)
-        sf = torch.empty((B, F, self.bark_bands_n, C), dtype=torch.int8, device=dev)
-        offset = torch.empty((B, F, C), dtype=torch.int16, device=dev)
-        bits = torch.empty((B, F, C), dtype=torch.int32, device=dev)
+        codes, sf, offset, bits = self._alloc_codes(X, rate=True)
         with _host.on_device(dev):
             _lib.check(self._lib.ac_quantize_budget(
                 self._plans.get(dev), _host.ptr(X), _host.ptr(thr), scalar, _host.ptr(per_row) if per_row is not None else None,
@@ -434,16 +446,9 @@ class PsychoacousticModel:
         over then lower the first rows of the clip (frame by frame, channel by channel) to k - 1 as far as they reach.
         ``clip_bits_out`` is the clip's length in ``pack()``'s data in bits; a clip that cannot meet its budget gets
         offset 254 and ``clip_bits_out`` above it.  No host synchronisation; not differentiable; float32 only."""
-        _host.require_float32(self.compute_dtype, "the quantiser")
-        X = self._check_quant_tensor(mdct_amplitudes, "mdct_amplitudes", torch.float32)
+        X, thr = self._check_quant_inputs(mdct_amplitudes, masking_threshold)
         B, F, N, C = X.shape
-        if N != self.filter_bands_n:
-            raise ValueError("axis 2 of mdct_amplitudes (%d) != filter_bands_n (%d)" % (N, self.filter_bands_n))
-        thr = self._check_quant_tensor(masking_threshold, "masking_threshold", torch.float32, X.shape, X.device)
-        if isinstance(min_offset, bool) or not isinstance(min_offset, (int, np.integer)):
-            raise TypeError("min_offset must be an int, got %s" % type(min_offset).__name__)
-        if not -254 <= int(min_offset) <= 254:
-            raise ValueError("min_offset (%d) outside [-254, 254]" % min_offset)
+        self._check_min_offset(min_offset)
         per_clip = None
         scalar = 0
         if isinstance(clip_bits, torch.Tensor):
@@ -457,10 +462,7 @@ class PsychoacousticModel:
         else:
             raise TypeError("clip_bits must be an int or an int64 tensor [B], got %s" % type(clip_bits).__name__)
         dev = X.device
-        codes = torch.empty((B, F, N, C), dtype=torch.int16, device=dev)
-        sf = torch.empty((B, F, self.bark_bands_n, C), dtype=torch.int8, device=dev)
-        offset = torch.empty((B, F, C), dtype=torch.int16, device=dev)
-        bits = torch.empty((B, F, C), dtype=torch.int32, device=dev)
+        codes, sf, offset, bits = self._alloc_codes(X, rate=True)
         clip_out = torch.empty((B,), dtype=torch.int64, device=dev)
         plan = self._plans.get(dev)
         nscratch = int(self._lib.ac_clip_budget_scratch_bytes(plan, B, F, C))

@@ -264,7 +264,10 @@ def test_scratch_bytes():
 
 @gpu
 @pytest.mark.parametrize("sr,N,M,C", [(48000, 1024, 64, 2), (48000, 1024, 64, 1), (48000, 960, 64, 6), (48000, 2048, 64, 1),
-                                      (48000, 64, 64, 2), (44100, 256, 48, 2)])
+                                      (48000, 64, 64, 2), (44100, 256, 48, 2),
+                                      # more than one channel group: groups of 4 and 3 channels; one channel each
+                                      # although C = 2
+                                      (48000, 1024, 600, 7), (48000, 256, 1400, 2)])
 def test_quantize_to_clip_budget_bit_exact(sr, N, M, C):
     """Per-clip budget tensors that mix never-binding, binding, exactly-the-floor and unmeetable budgets, on clips with
     NaN / Inf bands and saturated rows, from min_offset below, at and above 0; then a scalar budget.  At least three

@@ -64,6 +64,9 @@ def test_zigzag():
     np.testing.assert_array_equal(zz(q), [0, 1, 2, 3, 4, 65534, 65535, 65533])
     allq = np.arange(-32768, 32768).astype(np.int16)
     np.testing.assert_array_equal(unzz(zz(allq)), allq)
+    # the kernels' one zigzag is the 32-bit form: equal to the format's 16-bit form for every int16
+    q32 = allq.astype(np.int32)
+    np.testing.assert_array_equal(zz(allq), (q32 << 1) ^ (q32 >> 31))
     np.testing.assert_array_equal(bit_length([0, 1, 2, 3, 4, 65535]), [0, 1, 2, 2, 3, 16])
 
 
