@@ -258,6 +258,32 @@ def main():
         arrs["psy_thr_%s_d00" % name] = p.global_masking_threshold(Xc, t, 0.0)
     arrs["psy_thr_rand_d05"] = p.global_masking_threshold(gp["X_rand"], p.tonality(gp["X_rand"]), 0.5)
     save("precompute_float32_cases", **arrs)
+
+    # 8. alpha, the compression exponent of the spreading sum (psychoacoustic.py:14, 205-208, 223), away from its default
+    #    0.6: 0.3 (the largest amplification 1 / alpha), 0.8, and 1.0 (both powers are the identity).  Per model and alpha the
+    #    spreading matrix, a spectrum with a 1e-6 .. 1 envelope, one silent channel and one single-bin frame, the tonality and
+    #    the thresholds at drown 0 / 0.5.  A file and a stream of its own: the fixtures above keep their values.
+    rng8 = np.random.default_rng(8)
+    arrs = {}
+    for sr, Nf, M in ((48000, 1024, 64), (44100, 256, 48)):
+        env = np.logspace(-6, 0, Nf).reshape(1, 1, Nf, 1)
+        for alpha in (0.3, 0.8, 1.0):
+            tag0 = "%d_%d_%d_a%02d_" % (sr, Nf, M, round(alpha * 10))
+            Xa = (rng8.uniform(-1, 1, (1, 2, Nf, 2)) * env).astype(f32)
+            Xa[0, 1, :, 1] = 0.0                                     # a silent channel
+            Xa[0, 0, :, 1] = 0.0
+            Xa[0, 0, Nf // 10, 1] = 0.5                              # and a frame that holds a single bin
+            q64, q32 = psy(sr, Nf, M, f64, alpha=alpha), psy(sr, Nf, M, f32, alpha=alpha)
+            arrs[tag0 + "S"] = np.asarray(q64.spreading_matrix)
+            arrs[tag0 + "X"] = Xa
+            for tag, pm, dt in (("ref64", q64, f64), ("ref32", q32, f32)):
+                Xc = Xa.astype(dt)
+                t = pm.tonality(Xc)
+                arrs[tag0 + "t_" + tag] = t
+                for drown in (0.0, 0.5):
+                    arrs[tag0 + "thr_d%02d_%s" % (int(drown * 10), tag)] = pm.global_masking_threshold(Xc, t, drown)
+    arrs["alphas"] = np.array([0.3, 0.8, 1.0])
+    save("psy_alpha_cases", **arrs)
     return 0
 
 

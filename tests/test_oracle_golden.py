@@ -160,6 +160,36 @@ def test_psy_cases(golden, cfg, sr, N, M, dt, tag, tol):
                 assert rel_elem(thr, g[k2]) < tol
 
 
+@pytest.mark.parametrize("alpha", [0.3, 0.8, 1.0])
+@pytest.mark.parametrize("sr,N,M", [(48000, 1024, 64), (44100, 256, 48)])
+def test_psy_cases_at_other_alpha(golden, sr, N, M, alpha):
+    """The compression exponent of the spreading sum away from its default 0.6 (oracle/gen_golden.py 8: the reference's own
+    code at alpha 0.3 / 0.8 / 1.0): the oracle's spreading matrix at the tolerance of test_psy_tables, its tonality and
+    thresholds (drown 0 / 0.5, float64 and float32) at the tolerances of test_psy_cases.  Every GPU test of the masking
+    model at another alpha (test_psy_alpha.py) compares with this oracle."""
+    g = golden("psy_alpha_cases")
+    assert list(g["alphas"]) == [0.3, 0.8, 1.0]
+    tag0 = "%d_%d_%d_a%02d_" % (sr, N, M, round(alpha * 10))
+    p64 = PsychoOracle(sr, N, M, alpha=alpha, compute_dtype=np.float64)
+    np.testing.assert_allclose(p64.spreading64, g[tag0 + "S"], rtol=1e-13)
+    # (the matrix does depend on alpha: the default model's is elsewhere by far more than the tolerance)
+    assert rel_elem(PsychoOracle(sr, N, M, compute_dtype=np.float64).spreading64, g[tag0 + "S"]) > 0.1
+    X = g[tag0 + "X"]
+    assert X.shape == (1, 2, N, 2) and not X[0, 1, :, 1].any() and np.count_nonzero(X[0, 0, :, 1]) == 1
+    for dt, tag, tol in ((np.float64, "ref64", 1e-13), (np.float32, "ref32", 3e-6)):
+        p = PsychoOracle(sr, N, M, alpha=alpha, compute_dtype=dt)
+        t_ref = g[tag0 + "t_" + tag]
+        assert np.max(np.abs(p.tonality(X.astype(dt)) - t_ref)) < max(tol, 1e-6 if dt == np.float32 else 0)
+        t = t_ref.astype(dt)
+        for drown in (0.0, 0.5):
+            ref = g[tag0 + "thr_d%02d_%s" % (int(drown * 10), tag)]
+            for dense in (False, True):
+                assert rel_elem(p.global_masking_threshold(X.astype(dt), t, drown, dense=dense), ref) < tol
+    # a threshold of the default alpha is no neighbour of these
+    thr06 = PsychoOracle(sr, N, M, compute_dtype=np.float64).global_masking_threshold(X.astype(np.float64), g[tag0 + "t_ref64"], 0.0)
+    assert rel_elem(thr06, g[tag0 + "thr_d00_ref64"]) > 0.05
+
+
 @pytest.mark.parametrize("N", [960, 512, 128])
 def test_codec_cases_beside_the_powers_of_two(golden, N):
     """filters_n = 960 (no power of two) and 512 (bins overlap several Bark bands): transform, round trip, tonality and

@@ -21,7 +21,10 @@ import pytest
 import torch
 
 from conftest import rel_elem, tonality_err
-from psy_torch_reference import torch_masking_intensity, torch_psy_reference, torch_tonality_reference
+import psy_backward_checks as checks
+from psy_backward_checks import draw as _draw
+from psy_backward_checks import forced_generic as _forced_generic
+from psy_torch_reference import torch_psy_reference, torch_tonality_reference
 
 import audiocodec_amd
 from audiocodec_amd import _host, _lib
@@ -30,8 +33,7 @@ from oracle.audiocodec_oracle import PsychoOracle
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4          # forward parity bars of test_gpu_parity.py
-# (peak, rel-L2) per path; see the module docstring for the measured worst values
-BARS = {"fast": (6e-6, 2.5e-6), "generic": (4e-6, 2e-6), "float64": (5e-15, 1.6e-15), "bfloat16": (1.2e-2, 6.7e-3)}
+BARS = checks.BARS  # (peak, rel-L2) per path; see the module docstring for the measured worst values
 WORST = {}
 
 
@@ -47,106 +49,12 @@ def _require_gpu():
             print("  %-9s %.2e  %.2e" % (k, *WORST[k]))
 
 
-class _forced_generic:
-    """ac_set_force_generic(1) for the block: the generic kernels serve every call, forward and backward."""
-
-    def __init__(self, on=True):
-        self.on = on
-
-    def __enter__(self):
-        if self.on:
-            assert _lib.load().ac_set_force_generic(1) == 0
-
-    def __exit__(self, *exc):
-        _lib.load().ac_set_force_generic(0)
-
-
-def _errs(g, ref):
-    g, ref = g.detach().double(), ref.detach().double()
-    d = g - ref
-    peak = float(d.abs().max() / ref.abs().max())
-    l2 = float(torch.linalg.vector_norm(d) / torch.linalg.vector_norm(ref))
-    return peak, l2
-
-
-def _within(g, ref, path):
-    peak, l2 = _errs(g, ref)
-    return peak <= BARS[path][0] and l2 <= BARS[path][1]
-
-
 def _check(g, ref, path, guards=()):
-    """g within the bar of `path` of ref; every gradient of `guards` (a wrong reference) outside it."""
-    ref = ref.detach().double()
-    assert bool(torch.isfinite(g).all())
-    if float(ref.abs().max()) == 0.0:
-        assert float(g.abs().max()) == 0.0
-        return
-    peak, l2 = _errs(g, ref)
-    w = WORST.get(path, (0.0, 0.0))
-    WORST[path] = (max(w[0], peak), max(w[1], l2))
-    assert peak <= BARS[path][0] and l2 <= BARS[path][1], (path, peak, l2)
-    for bad in guards:
-        assert not _within(bad, ref, path), "the bar of %s does not reject a wrong reference" % path
-
-
-def _draw(B, F, N, C, g, dtype):
-    """A spectrum with a rising envelope, every |X| >= 1e-6 (no bin near the I > eps clamp)."""
-    env = torch.logspace(-3, 0, N, device="cuda", dtype=torch.float64).reshape(1, 1, N, 1)
-    u = torch.rand(B, F, N, C, device="cuda", generator=g, dtype=torch.float64)
-    s = torch.where(torch.rand(B, F, N, C, device="cuda", generator=g) < 0.5, -1.0, 1.0).double()
-    return (s * (0.999 * u + 0.001) * env).to(dtype)
-
-
-def _ref_grads(p, X, t_kernel, w, drown, S=None, rounded_t=False):
-    """Reference gradients at the kernel's inputs: d/dX of sum(w thr(X, t(X))), and of sum(w thr(X, t)) w.r.t. X and t."""
-    Xd = X.detach().double().requires_grad_(True)
-    td = torch_tonality_reference(Xd)
-    if rounded_t:        # the threshold kernel saw the ROUNDED tonality; its gradient path is td's
-        td = td + (t_kernel.detach().double() - td).detach()
-    (torch_psy_reference(p, Xd, td, drown, S) * w.double()).sum().backward()
-    Xd2 = X.detach().double().requires_grad_(True)
-    td2 = t_kernel.detach().double().requires_grad_(True)
-    (torch_psy_reference(p, Xd2, td2, drown, S) * w.double()).sum().backward()
-    return Xd.grad, Xd2.grad, td2.grad
-
-
-def _band_column_zeroed(p, X, t, drown):
-    """The spreading matrix with the column of the band that rises furthest above its quiet threshold zeroed."""
-    T = torch_masking_intensity(p, X.detach().double(), t.detach().double(), drown)
-    j = int((T / p.quiet_threshold_intensity.double().to(T.device)).mean(dim=(0, 1, 3)).argmax())
-    S = p.spreading_matrix.clone()
-    S[:, j] = 0
-    return S
+    checks.check(g, ref, path, BARS, WORST, guards)
 
 
 def _check_backward(p, X, drown, path, gen, rounded_t=False):
-    """The composed chain thr(X, t(X)), the threshold alone (grad_X, grad_t) and the tonality alone, each against the
-    float64 reference, with the sensitivity guards on the first two."""
-    B, F, N, C = X.shape
-    Xa = X.detach().clone().requires_grad_(True)
-    w = (torch.rand(B, F, N, C, device="cuda", generator=gen, dtype=torch.float64) + 0.5).to(X.dtype)
-    wt = (torch.rand(B, F, 1, C, device="cuda", generator=gen, dtype=torch.float64) * 2 - 1).to(X.dtype)
-    with _forced_generic(path != "fast" and p.is_fast()):
-        t = p.tonality(Xa)
-        (p.global_masking_threshold(Xa, t, drown) * w).sum().backward()
-        X2 = X.detach().clone().requires_grad_(True)
-        t2 = t.detach().clone().requires_grad_(True)
-        (p.global_masking_threshold(X2, t2, drown) * w).sum().backward()
-        X3 = X.detach().clone().requires_grad_(True)
-        (p.tonality(X3) * wt).sum().backward()
-    assert Xa.grad.dtype == X.dtype and t2.grad.dtype == X.dtype
-    gX, gX2, gt2 = _ref_grads(p, X, t, w, drown, rounded_t=rounded_t)
-    bX, bX2, bt2 = _ref_grads(p, X, t, w, drown + 0.05, rounded_t=rounded_t)
-    zX, zX2, zt2 = _ref_grads(p, X, t, w, drown, S=_band_column_zeroed(p, X, t, drown), rounded_t=rounded_t)
-    _check(Xa.grad, gX, path, guards=(bX, zX))
-    _check(X2.grad, gX2, path, guards=(bX2, zX2))
-    if drown == 1.0:     # the offset term vanishes: no gradient reaches the tonality, exactly
-        assert float(t2.grad.abs().max()) == 0.0 and float(gt2.abs().max()) == 0.0
-    else:
-        _check(t2.grad, gt2, path, guards=(bt2, zt2))
-    Xd = X.detach().double().requires_grad_(True)
-    (torch_tonality_reference(Xd) * wt.double()).sum().backward()
-    _check(X3.grad, Xd.grad, path)
+    checks.check_backward(p, X, drown, path, gen, BARS, WORST, rounded_t=rounded_t)
 
 
 # ---- B. the fast backward: every channel mode (CMODE 0 stereo / 1 strided pairs / 2 mono), both row widths (R 8 at
