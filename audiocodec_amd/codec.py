@@ -170,8 +170,9 @@ class AudioCodec:
         return StreamingMDCT(self.mdct, batches_n, channels_n, device=device, psy=self.psy)
 
     def decode(self, X, pcm16=False):
-        """X [B, K', N, C] -> x [B, (K'+1)*N, C]; ``pcm16=True`` returns ``torch.int16`` PCM
-        (clamp(round(32768 x)) applied inside the kernel's stores)."""
+        """X [B, K', N, C] -> x [B, (K'+1)*N, C]; ``pcm16=True`` returns ``torch.int16`` PCM, converted inside the kernel's
+        stores: ``pcm = 0 if x is NaN else clamp(rint(fp32(32768 * x)), -32768, 32767)`` (``rint`` rounds half to even; +-Inf
+        and products that overflow float32 go to the rail of their sign; a NaN sample decodes to silence)."""
         if not pcm16:
             return self.mdct.inverse_transform(X)
         X = _host.check_device_tensor(X, "X", self.compute_dtype, 4)
@@ -207,7 +208,10 @@ class AudioCodec:
 
     def decode_quantized(self, codes, sf, pcm16=False):
         """codes int16 [B, K', N, C], sf int8 [B, K', M, C] -> x [B, (K'+1)*N, C] (``torch.int16`` with ``pcm16=True``):
-        bit-equal to ``decode(psy.dequantize(codes, sf), pcm16)``.  float32 only."""
+        bit-equal to ``decode(psy.dequantize(codes, sf), pcm16)``.  The 16-bit store is :meth:`decode`'s:
+        ``pcm = 0 if x is NaN else clamp(rint(fp32(32768 * x)), -32768, 32767)`` -- overshoot of a lossy decode past full
+        scale stops at the rails, and a band marked non-representable (``sf = -128``, NaN when dequantised) decodes to
+        silence over the two blocks its frame covers.  float32 only."""
         _host.require_float32(self.compute_dtype, "decode_quantized")
         codes, sf = self.psy._check_codes(codes, sf)
         B, Kp, N, C = codes.shape

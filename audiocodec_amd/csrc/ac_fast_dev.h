@@ -391,13 +391,10 @@ __device__ __forceinline__ void store_row(float* __restrict__ r0, float* __restr
   }
 }
 
-// ---- the same rows in 2-byte storage: 16-bit PCM (x = pcm / 32768; pcm = clamp(round(32768 x))) or bfloat16 ----------
+// ---- the same rows in 2-byte storage: 16-bit PCM (x = pcm / 32768; pcm = to_pcm16(x), ac_internal.h) or bfloat16 ------
 typedef short s4 __attribute__((ext_vector_type(4)));
 typedef short s2 __attribute__((ext_vector_type(2)));
 constexpr float kPcmScale = 1.0f / 32768.0f;
-__device__ __forceinline__ short to_pcm16(float v) {
-  return (short)__float2int_rn(fminf(fmaxf(v * 32768.0f, -32768.0f), 32767.0f));
-}
 struct Pcm16Fmt {
   static __device__ __forceinline__ float dec(short h) { return (float)h * kPcmScale; }
   static __device__ __forceinline__ s2 enc2(float a, float b) { return s2{to_pcm16(a), to_pcm16(b)}; }

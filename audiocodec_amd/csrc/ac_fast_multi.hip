@@ -193,7 +193,7 @@ __device__ __forceinline__ void store_half(float* r0, float* r1, bool has1, int 
   }
 }
 
-// the same movers for 16-bit PCM rows (x = pcm / 32768 on the way in, clamp(round(32768 x)) on the way out)
+// the same movers for 16-bit PCM rows (x = pcm / 32768 on the way in, to_pcm16(x) on the way out)
 template <int CMODE, int LB>
 __device__ __forceinline__ void load_rowm(const int16_t* r0, const int16_t* r1, bool has1, int l, v4f (&v)[8]) {
   if (CMODE == 0) {

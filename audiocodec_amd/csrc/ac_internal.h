@@ -90,6 +90,14 @@ __device__ __forceinline__ float db_of(float v, int norm) {
   if (norm) dB = fmaxf((dB + 20.f) * (1.0f / 140.f), 0.f);
   return dB;
 }
+// the 16-bit PCM store of every synthesis kernel (ac_fast_dev.h, ac_wave_v.h):
+// pcm = 0 if x is NaN else clamp(rint(fp32(32768 x)), -32768, 32767), rint = round half to even; +-Inf and products that
+// overflow float32 go to the rail of their sign.  (fmaxf(NaN, -32768) is -32768: without the select a NaN sample would
+// store full-scale negative; the select leaves every other result as it was)
+__device__ __forceinline__ short to_pcm16(float v) {
+  const float r = fminf(fmaxf(v * 32768.0f, -32768.0f), 32767.0f);
+  return (short)__float2int_rn(v != v ? 0.0f : r);
+}
 #endif
 
 typedef __bf16 bf16_t;   // storage type of the AC_BF16 tensors (device code converts with v_cvt_pk_bf16_f32)

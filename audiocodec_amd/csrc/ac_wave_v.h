@@ -59,7 +59,7 @@ struct RowPair {
       return v4f_t{has1 ? s0.x : s0.y, s0.y, has1 ? s1.x : s1.y, s1.y};
     }
   }
-  // the same rows as 16-bit PCM (x = pcm / 32768 on the way in, clamp(round(32768 x)) on the way out, as the wave-level
+  // the same rows as 16-bit PCM (x = pcm / 32768 on the way in, to_pcm16(x) on the way out, as the wave-level
   // kernels of ac_fast_dev.h do): 8 / 4 bytes per access
   __device__ __forceinline__ v4f_t load2(const int16_t* a, const int16_t* b, int m) const {
     static_assert(LAY <= 1, "16-bit PCM: stereo or mono rows");
@@ -78,7 +78,7 @@ struct RowPair {
     static_assert(LAY <= 1, "16-bit PCM: stereo or mono rows");
     typedef short s4_t __attribute__((ext_vector_type(4)));
     typedef short s2_t __attribute__((ext_vector_type(2)));
-    auto enc = [](float f) { return (short)__float2int_rn(fminf(fmaxf(f * 32768.0f, -32768.0f), 32767.0f)); };
+    auto enc = [](float f) { return to_pcm16(f); };   // (ac_internal.h: the one definition)
     if constexpr (LAY == 0) {
       __builtin_nontemporal_store(s4_t{enc(v.x), enc(v.y), enc(v.z), enc(v.w)}, reinterpret_cast<s4_t*>(a + 2 * m));
     } else {

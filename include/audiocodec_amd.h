@@ -233,10 +233,12 @@ AC_API int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
                        void* stream);
 
 /* 16-bit PCM at the boundary (extension; the reference takes float PCM in [-1, 1] only, mdctransformer.py:104):
- * x = pcm / 32768 on the way in, pcm = clamp(round(32768 x), -32768, 32767) on the way out, fused into the kernels'
- * loads / stores, so a frame moves 2 bytes per sample instead of 4.  Served by the wave-level kernels (filters_n 64 ... 2048
- * in powers of two, 'vorbis' / 'sine' window; below 1024 mono / stereo) and by the LDS-FFT tier at filters_n 120, 240, 480,
- * 960, 1920, 576, 1152 (mono / stereo, any window); AC_EUNSUPPORTED otherwise.  Shapes as the float32 entry points. */
+ * x = pcm / 32768 on the way in; on the way out pcm = 0 if x is NaN else clamp(rint(fp32(32768 x)), -32768, 32767), rint
+ * round half to even (+-Inf and products that overflow float32 go to the rail of their sign; a NaN sample is silence).  Both
+ * are fused into the kernels' loads / stores, so a frame moves 2 bytes per sample instead of 4.  Served by the wave-level
+ * kernels (filters_n 64 ... 2048 in powers of two, 'vorbis' / 'sine' window; below 1024 mono / stereo) and by the LDS-FFT
+ * tier at filters_n 120, 240, 480, 960, 1920, 576, 1152 (mono / stereo, any window); AC_EUNSUPPORTED otherwise.  Shapes as
+ * the float32 entry points. */
 AC_API int ac_mdct_forward_pcm16(const ac_mdct_plan* plan, const int16_t* x, float* X, int B, int K, int C, void* stream);
 AC_API int ac_mdct_inverse_pcm16(const ac_mdct_plan* plan, const float* X, int16_t* x, int B, int Kp, int C, void* stream);
 AC_API int ac_encode_fused_pcm16(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const int16_t* x, float* X, float* t,
