@@ -328,6 +328,14 @@ class StreamingMDCT:
     frame ``i`` with the stored aliased half of the previous frame.  With a masking model (``psy``)
     :meth:`encode_chunk` also returns tonality and threshold of the chunk's frames -- bit for bit what the one-shot
     ``AudioCodec.encode`` gives for those frames.
+
+    Streams: every chunk call only enqueues on its stream -- the current one, or ``stream=`` -- and never touches the
+    default stream or waits for the device.  Creating the object may block the host and leaves the float32 state zeroed;
+    the float64 state is allocated by the first float64 chunk call and zeroed on that call's stream, ahead of its
+    kernels.  Results a chunk call allocates itself (``out=None``) are allocated under the stream the work runs on, so
+    torch's allocator hands their memory on in that stream's order; a caller that consumes them on another stream
+    orders that itself (an event, and ``record_stream``).  The overlap state is carried from call to call: calls on one
+    object are ordered by the caller (one stream, or events between streams).
     """
 
     def __init__(self, mdct: MDCTransformer, batches_n, channels_n, device=None, psy: PsychoacousticModel = None):
@@ -376,8 +384,13 @@ class StreamingMDCT:
             raise ValueError("%s lives on %s but the stream's state lives on %s" % (name, x.device, self.device))
         return x
 
-    def _out(self, out, name, shape, like):
+    def _out(self, out, name, shape, like, stream=None):
         if out is None:
+            # the allocator's pool (and reuse order) of the stream the work runs on; no test can assert this (only a reuse of
+            # freed memory by another stream's work would show it): the class docstring states the rule
+            if stream is not None:
+                with torch.cuda.stream(stream):
+                    return torch.empty(shape, dtype=like.dtype, device=like.device)
             return torch.empty(shape, dtype=like.dtype, device=like.device)
         if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != like.dtype \
                 or out.device != like.device or not out.is_contiguous() or out.data_ptr() % 16 != 0:
@@ -397,7 +410,7 @@ class StreamingMDCT:
         if (B, C) != (self.B, self.C) or S % N != 0:
             raise ValueError("x_chunk must be [%d, k*%d, %d], got %s" % (self.B, N, self.C, tuple(x.shape)))
         k = S // N
-        X = self._out(out, "out", (B, k, N, C), x)
+        X = self._out(out, "out", (B, k, N, C), x, stream)
         with _host.on_device(x.device):
             _lib.check(self._lib.ac_stream_encode_typed(self._handle, None, _host.ptr(x), _host.ptr(X), None, None, 0.0,
                                                         self.mdct._dtype_id, k, self._stream(stream)))
@@ -416,9 +429,9 @@ class StreamingMDCT:
             raise ValueError("x_chunk must be [%d, k*%d, %d], got %s" % (self.B, N, self.C, tuple(x.shape)))
         k = S // N
         o = out if out is not None else (None, None, None)
-        X = self._out(o[0], "out[0]", (B, k, N, C), x)
-        t = self._out(o[1], "out[1]", (B, k, 1, C), x)
-        thr = self._out(o[2], "out[2]", (B, k, N, C), x)
+        X = self._out(o[0], "out[0]", (B, k, N, C), x, stream)
+        t = self._out(o[1], "out[1]", (B, k, 1, C), x, stream)
+        thr = self._out(o[2], "out[2]", (B, k, N, C), x, stream)
         with _host.on_device(x.device):
             _lib.check(self._lib.ac_stream_encode_typed(self._handle, self.psy._plan(x.device), _host.ptr(x), _host.ptr(X),
                                                         _host.ptr(t), _host.ptr(thr), float(drown), self.mdct._dtype_id, k,
@@ -545,7 +558,7 @@ class StreamingMDCT:
         if (B, C, N) != (self.B, self.C, self.mdct.filters_n):
             raise ValueError("X_chunk must be [%d, k, %d, %d], got %s" % (self.B, self.mdct.filters_n, self.C,
                                                                          tuple(X.shape)))
-        x = self._out(out, "out", (B, k * N, C), X)
+        x = self._out(out, "out", (B, k * N, C), X, stream)
         with _host.on_device(X.device):
             _lib.check(self._lib.ac_stream_inverse_typed(self._handle, _host.ptr(X), _host.ptr(x), self.mdct._dtype_id, k,
                                                          self._stream(stream)))

@@ -32,6 +32,16 @@ static int upload(const std::vector<T>& h, T** d) {
   return AC_OK;
 }
 
+// Creation calls upload tables and zero state with the synchronous runtime calls.  Those go to the null stream, a queue that
+// nothing orders with a caller's non-blocking streams, and a hipMemset of device memory is allowed to return before the
+// device has run it (as CUDA's is).  The plan builders and ac_stream_create end with this wait, so that what they enqueued
+// is in place before any first use on any stream; creation may block the host.
+static hipError_t creation_sync() { return hipStreamSynchronize(nullptr); }
+static int creation_done() {
+  AC_HIP_CHECK(creation_sync());
+  return AC_OK;
+}
+
 static int check_device(int device) {
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
@@ -253,6 +263,7 @@ static int mdct_plan_build(int N, int window, int precompute, const FoldCoef& c,
     st = fast_mdct_plan_init(p);
     if (!st) p->fast = 1;
   }
+  if (!st) st = creation_done();
   if (st) {
     ac_mdct_plan_destroy(p);
     return st;
@@ -447,6 +458,7 @@ static int psy_plan_build(int N, int M, double sample_rate, double alpha, int de
       st = AC_EUNSUPPORTED;
     }
   }
+  if (!st) st = creation_done();
   if (st) {
     ac_psy_plan_destroy(p);
     return st;
@@ -749,6 +761,7 @@ int ac_stream_create(const ac_mdct_plan* plan, int B, int C, ac_stream** out) {
   if (e == hipSuccess) e = hipMemset(s->d_prev_tmp, 0, nb);
   if (e == hipSuccess) e = hipMemset(s->d_tail, 0, nt);
   if (e == hipSuccess) e = hipMemset(s->d_tail_tmp, 0, nt);
+  if (e == hipSuccess) e = creation_sync();   // (the zeroing has run before any chunk call can)
   if (e != hipSuccess) {
     set_error("stream state allocation failed: %s", hipGetErrorString(e));
     ac_stream_destroy(s);
@@ -1279,16 +1292,18 @@ int ac_encode_fused_typed(const ac_mdct_plan* mdct, const ac_psy_plan* psy, cons
 // ---- streaming on bfloat16 tensors: the wave-level kernels (filters_n 1024 / 2048, mono / stereo) with the conversion in
 // their loads and stores; the state stays float32 (a bfloat16 block is exact in it, the aliased half is kept unrounded),
 // so chunked results equal the one-shot *_typed calls bit for bit
-// float64 streams: the state in double (allocated by the first float64 call), the float64 kernels (O(N^2), any even size)
-static int stream_state64(ac_stream* s) {
+// float64 streams: the state in double (allocated by the first float64 call), the float64 kernels (O(N^2), any even size).
+// The state is zeroed on the CALL's stream, ahead of the chunk's kernels in the same queue: a synchronous hipMemset would
+// go to the null stream, which nothing orders with a caller's non-blocking stream.
+static int stream_state64(ac_stream* s, hipStream_t hs) {
   if (s->d_prev64) return AC_OK;
   const size_t nb = (size_t)s->B * s->N * s->C * sizeof(double), nt = (size_t)s->B * s->C * (s->N / 2) * sizeof(double);
   hipError_t e = hipMalloc((void**)&s->d_prev64, nb);
   if (e == hipSuccess) e = hipMalloc((void**)&s->d_tail64, nt);
   if (e == hipSuccess) e = hipMalloc((void**)&s->d_tail64_tmp, nt);
-  if (e == hipSuccess) e = hipMemset(s->d_prev64, 0, nb);
-  if (e == hipSuccess) e = hipMemset(s->d_tail64, 0, nt);
-  if (e == hipSuccess) e = hipMemset(s->d_tail64_tmp, 0, nt);
+  if (e == hipSuccess) e = hipMemsetAsync(s->d_prev64, 0, nb, hs);
+  if (e == hipSuccess) e = hipMemsetAsync(s->d_tail64, 0, nt, hs);
+  if (e == hipSuccess) e = hipMemsetAsync(s->d_tail64_tmp, 0, nt, hs);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     set_error("float64 stream state allocation failed: %s", hipGetErrorString(e));
@@ -1331,7 +1346,7 @@ int ac_stream_encode_typed(ac_stream* s, const ac_psy_plan* psy, const void* x_c
   DeviceGuard guard(s->device);
   hipStream_t hs = (hipStream_t)stream;
   if (dtype == AC_F64) {   // analysis with the stored block -1, the new state = the chunk's last block, the model on the chunk
-    st = stream_state64(s);
+    st = stream_state64(s, hs);
     if (st) return st;
     const double* xd = static_cast<const double*>(x_chunk);
     st = launch_fwd_f64_stream(p, xd, static_cast<double*>(X), s->d_prev64, s->B, k, k, s->C, hs);
@@ -1366,7 +1381,7 @@ int ac_stream_inverse_typed(ac_stream* s, const void* X_chunk, void* x, int dtyp
   AC_REQUIRE_ALIGNED(X_chunk, x);
   DeviceGuard guard(s->device);
   if (dtype == AC_F64) {
-    st = stream_state64(s);
+    st = stream_state64(s, (hipStream_t)stream);
     if (!st) st = launch_inv_f64_stream(s->plan, static_cast<const double*>(X_chunk), static_cast<double*>(x), s->d_tail64, s->d_tail64_tmp,
                                         s->B, k, k, s->C, (hipStream_t)stream);
     if (st) return st;

@@ -322,6 +322,12 @@ AC_API int ac_quantize_clip_budget(const ac_psy_plan* psy, const float* X, const
  * Analysis state: the last input block per (b,c) [B,N,C]; synthesis state: the aliased second half of
  * the last DCT-IV output per (b,c) [B,C,N/2].  A fresh/reset stream starts from zero state, so the
  * concatenation of chunk outputs equals the one-shot transform frame for frame.
+ * Streams: ac_stream_create allocates the float32 state, zeroes it and waits for the zeroing (it may block the host, as the
+ * plan builders may for their uploads): nothing a creation call enqueued can be overtaken by a later call on any stream.  The float64 state (ac_stream_*_typed with AC_F64) is allocated by the
+ * first float64 chunk call -- the one allocation a chunk call makes, of the library's own memory -- and zeroed with
+ * hipMemsetAsync on THAT call's stream, ahead of its kernels; nothing goes to the null stream.  ac_stream_reset zeroes the
+ * state on its stream.  The state is carried from call to call: the caller orders the calls on one ac_stream (one HIP
+ * stream, or events between streams), as it orders the chunks themselves.
  * ---------------------------------------------------------------------------------------- */
 AC_API int ac_stream_create(const ac_mdct_plan* plan, int B, int C, ac_stream** out);
 AC_API int ac_stream_reset(ac_stream* s, void* stream);
