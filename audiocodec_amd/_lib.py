@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("AUDIOCODEC_AMD_LIB") or os.path.join(_HERE, "lib", "l
 
 AC_OK = 0
 AC_EINVAL, AC_EHIP, AC_ENOMEM, AC_ENODEV, AC_EUNSUPPORTED = -1, -2, -3, -4, -5
+AC_EMIT_NOISY, AC_EMIT_DB_NORM, AC_EMIT_CODES = 1, 2, 4   # flags of ac_encode_fused_ex
 WINDOW_IDS = {"vorbis": 0, "sine": 1}   # anything else -> 2 (rectangular), mdctransformer.py:199-211
 WINDOW_RECT = 2
 
@@ -106,6 +107,7 @@ PROTOTYPES = {
     "ac_decode_quantized": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                     c_void_p]),
     "ac_decode_quantized_launches": (c_int, [c_void_p, c_void_p, c_int]),
+    "ac_encode_quantized_launches": (c_int, [c_void_p, c_void_p, c_int]),
     "ac_pack_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ac_pack_index": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ac_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

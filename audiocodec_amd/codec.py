@@ -193,10 +193,33 @@ class AudioCodec:
         X, _, thr = self.encode(x, drown)
         return X, thr
 
+    def encode_quantized_launches(self, channels_n=2, device=None):
+        """Launches :meth:`encode_quantized` takes for float32 PCM of ``channels_n`` channels
+        (``ac_encode_quantized_launches``): 1 = the fused encode quantises the frame in its registers (filters_n = 1024, mono /
+        stereo, spreading ``"f32"`` or ``"bf16x2_mfma"``), 2 = :meth:`encode`, then the quantiser."""
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return int(self._lib.ac_encode_quantized_launches(self.mdct._plan(dev), self.psy._plan(dev), int(channels_n)))
+
     def encode_quantized(self, x, drown=0.0):
         """:meth:`encode`, then :meth:`PsychoacousticModel.quantize` on its X and threshold: x [B, K*N, C] (float or
-        ``torch.int16`` PCM) -> (codes int16 [B, K+1, N, C], sf int8 [B, K+1, M, C]).  Two launches; X, tonality and
-        threshold are temporaries.  float32 only, not differentiable."""
+        ``torch.int16`` PCM) -> (codes int16 [B, K+1, N, C], sf int8 [B, K+1, M, C]).  One launch that writes only codes and
+        scale factors where :meth:`encode_quantized_launches` is 1 and ``x`` is float32 (``ac_encode_fused_ex`` with
+        ``AC_EMIT_CODES``: the same values, bit for bit); elsewhere two launches with X, tonality and threshold as
+        temporaries.  float32 only, not differentiable."""
+        if (self.compute_dtype == torch.float32 and isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.is_cuda
+                and x.dim() == 3 and not (x.requires_grad and torch.is_grad_enabled())
+                and x.shape[1] % self.filters_n == 0
+                and self.encode_quantized_launches(x.shape[2], x.device) == 1):
+            x = _host.check_device_tensor(x, "x", torch.float32, 3)
+            B, S, C = x.shape
+            K = S // self.filters_n
+            codes = torch.empty((B, K + 1, self.filters_n, C), dtype=torch.int16, device=x.device)
+            sf = torch.empty((B, K + 1, self.psy.bark_bands_n, C), dtype=torch.int8, device=x.device)
+            with _host.on_device(x.device):
+                _lib.check(self._lib.ac_encode_fused_ex(
+                    self.mdct._plan(x.device), self.psy._plan(x.device), _host.ptr(x), None, None, None, float(drown),
+                    _lib.AC_EMIT_CODES, _host.ptr(codes), _host.ptr(sf), 0, B, K, C, _host.stream_ptr(x.device)))
+            return codes, sf
         X, thr = self._encode_for_quantizer(x, drown, "encode_quantized")
         return self.psy.quantize(X, thr)
 

@@ -698,10 +698,57 @@ int ac_encode_fused(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const floa
                     float drown, int B, int K, int C, void* stream) {
   return encode_fused(mdct, psy, x, false, X, t, thr, drown, B, K, C, stream);
 }
+static int check_quant(const ac_psy_plan* psy, int B, int F, int C);
+// whether AC_EMIT_CODES is one launch (k_fwd_fast_q); AC_ENCODE_QUANT_NOFUSE=1 sends every configuration down the two
+// launches (A/B measurements: read per call, so that one process can time both forms)
+static bool encode_quantized_fuses(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C) {
+  const char* e = getenv("AC_ENCODE_QUANT_NOFUSE");
+  if (e && atoi(e) == 1) return false;
+  return !g_force_generic && wave_level(mdct, C, 0, 1) && psy_fast_serves(psy, C) && fast_encode_quant_serves(mdct, psy, C);
+}
+
+int ac_encode_quantized_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C) {
+  if (!mdct || !psy || mdct->N != psy->N || mdct->device != psy->device || C < 1) return 0;
+  return encode_quantized_fuses(mdct, psy, C) ? 1 : 2;
+}
+
+// ac_encode_fused_ex with AC_EMIT_CODES
+static int encode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
+                            float drown, int16_t* codes, int8_t* sf, int B, int K, int C, void* stream) {
+  AC_REQUIRE(mdct != nullptr && psy != nullptr, "plan is NULL");
+  AC_REQUIRE(mdct->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", mdct->N, psy->N);
+  AC_REQUIRE(mdct->device == psy->device, "plans live on different devices");
+  int st = check_dims(B, K, C);
+  if (!st) st = check_quant(psy, B, K + 1, C);
+  if (st) return st;
+  if (B == 0 || C == 0) return AC_OK;
+  AC_REQUIRE(codes != nullptr && sf != nullptr, "AC_EMIT_CODES without its output tensors (codes, sf)");
+  if (encode_quantized_fuses(mdct, psy, C)) {
+    AC_REQUIRE(x != nullptr || K == 0, "NULL tensor pointer");
+    AC_REQUIRE_ALIGNED(x, X, thr, codes, sf);
+    DeviceGuard guard(mdct->device);
+    return launch_fwd_fast_quant(mdct, psy, x, X, t, thr, drown, codes, sf, B, K, K + 1, C, (hipStream_t)stream);
+  }
+  AC_REQUIRE(X != nullptr && t != nullptr && thr != nullptr,
+             "AC_EMIT_CODES: X, t and thr are required as intermediates where ac_encode_quantized_launches() returns 2");
+  AC_REQUIRE_ALIGNED(codes, sf);
+  st = encode_fused(mdct, psy, x, false, X, t, thr, drown, B, K, C, stream);
+  if (st) return st;
+  DeviceGuard guard(psy->device);
+  return launch_quantize(psy, X, thr, codes, sf, B, K + 1, C, (hipStream_t)stream);
+}
+
 int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
-                       float drown, int flags, float* noisy, float* db_norm, uint64_t seed, int B, int K, int C,
+                       float drown, int flags, void* noisy_v, void* db_norm_v, uint64_t seed, int B, int K, int C,
                        void* stream) {
-  AC_REQUIRE((flags & ~(AC_EMIT_NOISY | AC_EMIT_DB_NORM)) == 0, "unknown flags %#x", flags);
+  AC_REQUIRE((flags & ~(AC_EMIT_NOISY | AC_EMIT_DB_NORM | AC_EMIT_CODES)) == 0, "unknown flags %#x", flags);
+  if (flags & AC_EMIT_CODES) {
+    AC_REQUIRE(flags == AC_EMIT_CODES, "AC_EMIT_CODES excludes the other flags (got %#x)", flags);
+    return encode_quantized(mdct, psy, x, X, t, thr, drown, static_cast<int16_t*>(noisy_v), static_cast<int8_t*>(db_norm_v), B, K,
+                            C, stream);
+  }
+  float* noisy = static_cast<float*>(noisy_v);
+  float* db_norm = static_cast<float*>(db_norm_v);
   AC_REQUIRE(!(flags & AC_EMIT_NOISY) || noisy != nullptr || B == 0 || C == 0, "AC_EMIT_NOISY without an output tensor");
   AC_REQUIRE(!(flags & AC_EMIT_DB_NORM) || db_norm != nullptr || B == 0 || C == 0, "AC_EMIT_DB_NORM without an output tensor");
   float* o_noisy = (flags & AC_EMIT_NOISY) ? noisy : nullptr;

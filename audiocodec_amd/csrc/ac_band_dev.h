@@ -75,6 +75,21 @@ __device__ inline uint64_t block_scan(uint64_t v, uint64_t* total, uint64_t* sc)
   return before + x - v;
 }
 
+// a band's scale factor from its smallest key: 0 for an empty band, -128 for a band that holds a NaN / Inf (key INT_MIN), else
+// the criterion's.  FLAT: the search runs for every lane and the special cases select afterwards, so that it is not nested
+// under their lane masks (the fused encode's frame loop has no scalar registers for them); the value is the same
+template <bool FLAT = false>
+__device__ __forceinline__ int band_scale_factor(bool empty, int kmin) {
+  if constexpr (FLAT) {
+    const int s = scale_factor_of(key_value(kmin));
+    return empty ? 0 : kmin == INT_MIN ? -128 : s;
+  } else {
+    if (empty) return 0;
+    if (kmin == INT_MIN) return -128;
+    return scale_factor_of(key_value(kmin));
+  }
+}
+
 // a band's scale factor q into sf and its inverse step into the LDS slot the codes loop reads: NaN for sf = -128
 __device__ __forceinline__ void store_sf(int q, int8_t* __restrict__ sf, float* inv) {
   *sf = (int8_t)q;

@@ -3,10 +3,6 @@
 // threshold).  They share one object because they share instantiations of fwd_fast_body and psy_stage: these have internal
 // linkage, the compiler's interprocedural passes look at all callers of such a function in the module before it is
 // inlined, and apart the three families get other register allocations for 18 kernels than together (DESIGN_LOG.md 9).
-#include <cmath>
-#include <cstdlib>
-
-#include "ac_fast.h"
 #include "ac_fast_fwd_dev.h"
 #include "ac_fast_inv_dev.h"
 
@@ -154,68 +150,6 @@ static void launch_fwd_R(const FwdArgs& a, bool psy, int spread, int C, unsigned
   else if (C == 1) hipLaunchKernelGGL((k_fwd_fast<R, 2, false, AC_WAVES, IOF>), dim3(grid), blk, 0, s, a);
   else hipLaunchKernelGGL((k_fwd_fast<R, 1, false, AC_WAVES, IOF>), dim3(grid), blk, 0, s, a);
   }
-}
-
-// arguments and grid of the one-frame-per-wave analysis kernels (filters_n 1024 / 2048)
-static int prep_fwd_fast(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, int iof, float* X, float* t,
-                         float* thr, float drown, const float* prev_block, int B, int Kin, int F, int C, float* state_out,
-                         float* noisy, float* dbn, uint64_t seed, FwdArgs& a, unsigned& grid) {
-  // combinations no kernel is instantiated for (ac_api.hip routes them elsewhere; refuse rather than launch nothing)
-  if ((iof == 2 && C > 2) || (psy && p->N == Geo<16>::FN && (C == 1 || (iof == 1 && C > 2)))) {
-    set_error("internal: no wave-level analysis kernel for filters_n = %d, %d channels, io format %d%s", p->N, C, iof,
-              psy ? ", fused masking model" : "");
-    return AC_EUNSUPPORTED;
-  }
-  a.x = x;
-  a.X = X;
-  a.t = t;
-  a.thr = thr;
-  a.prev_block = prev_block;
-  a.state_out = state_out;
-  a.noisy = noisy;
-  a.dbn = dbn;
-  a.noise_key = mix64(seed);
-  if ((noisy || dbn) && !fast_epilogue_supported(p, psy, iof, C)) {
-    set_error("internal: no fused element-wise epilogue for this configuration");
-    return AC_EUNSUPPORTED;
-  }
-  a.tab = p->d_fast;
-  if (psy) a.psy = psy_params(psy, drown);
-  else a.psy = PsyParams{nullptr, 0.f, 0.f, 0.f};
-  a.B = B;
-  a.Kin = Kin;
-  a.F = F;
-  a.C = C;
-  a.nsig = (long long)B * C;
-  a.npairs = (C == 2) ? (long long)B : (a.nsig + 1) / 2;
-  a.nframes = a.npairs * F;
-  {
-    const double ang = -3.14159265358979323846 / (4.0 * p->N), sc = (double)p->N * 1.4142135623730951;   // 1 / (1 / (N sqrt 2))
-    a.pre_re = (float)(std::cos(ang) * sc);
-    a.pre_im = (float)(std::sin(ang) * sc);
-  }
-  // tuning hooks (read once): AC_XCD=1 groups consecutive workgroups per XCD; AC_FWD_T = frames per wave, workgroups
-  // dispatched in order (default 4: measured 0.603 ms against 0.615 ms for persistent waves, B = 256, K = 468 -- fresh
-  // workgroups keep the window of memory in flight contiguous); AC_FWD_T=0 = persistent waves, AC_WG_PER_CU per CU
-  static const int xcd = [] { const char* e = getenv("AC_XCD"); return e ? atoi(e) : 0; }();
-  static const int wgcu = [] { const char* e = getenv("AC_WG_PER_CU"); return e ? atoi(e) : 3; }();
-  static const int tper = [] { const char* e = getenv("AC_FWD_T"); return e ? atoi(e) : 4; }();
-  a.xcd = xcd;
-  const int nw = psy ? AC_WAVES_PSY : AC_WAVES;
-  // small launches (a streaming chunk of one clip): fewer frames per wave, so that the frames spread over the chip
-  // instead of queueing behind each other in a few workgroups
-  int tper_eff = tper;
-  while (tper_eff > 1 && a.nframes < (long long)nw * tper_eff * p->cus * 2) tper_eff >>= 1;
-  a.T = tper_eff;
-  if (tper > 0) {
-    // workgroups in eights (XCDs): ceil(ceil(nframes / per) / 8) = ceil(nframes / (8 per))
-    const long long per8 = 8ll * nw * tper_eff;
-    const int st = grid_for((a.nframes + per8 - 1) / per8 * 8, 1, &grid);
-    if (st) return st;
-  } else {
-    grid = persistent_grid(p->cus, wgcu, a.nframes, nw);
-  }
-  return AC_OK;
 }
 
 int launch_fwd_fast(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, int iof, float* X, float* t,

@@ -1,6 +1,11 @@
 // Analysis of the wave-level kernels for filters_n = 1024 / 2048 (ac_fast_dev.h), with the fused masking model: the
-// body and the k_fwd_fast template.  Instantiated in ac_fast_fwd.hip, which also runs the body in k_duplex_fast.
+// body and the k_fwd_fast template.  Instantiated in ac_fast_fwd.hip, which also runs the body in k_duplex_fast, and in
+// ac_fast_fwd_q.hip (k_fwd_fast_q: the body with the quantiser as its last stage, ac_fast_quant_dev.h).
 #pragma once
+#include <cmath>
+#include <cstdlib>
+
+#include "ac_fast.h"
 #include "ac_fast_psy_dev.h"
 
 namespace ac {
@@ -54,11 +59,16 @@ constexpr int fwd_lds_bytes() {
   return NW * (PSY ? WAVE_LDS_PSY : WAVE_LDS) + (fwd_nopre<R, PSY, SPREAD>() ? Geo<R>::I_LDS_NOPRE : Geo<R>::I_LDS) * 4 +
          (PSY ? PsyGeo<R>::PSY_LDS + mf_lds(SPREAD) : 0);
 }
+struct NoQuant {};
 // the kernel's body: workgroup `bid` of `nblocks` (the kernel below passes blockIdx.x / gridDim.x; the streaming duplex
 // kernel runs it on the first part of its grid), lds = fwd_lds_bytes() bytes of LDS, 16-byte aligned
-template <int R, int CMODE, bool PSY, int NW, int IOF = 0, int SPREAD = 0, bool EPI = false>
-__device__ __forceinline__ void fwd_fast_body(const FwdArgs& a, char* lds, const int bid, const int nblocks) {
+// QUANT other than NoQuant (QuantStage, ac_fast_quant_dev.h): the frame's last stage is qz.frame() -- the masking model
+// with the quantiser behind it -- and a.X, a.t, a.thr may each be null (not written)
+template <int R, int CMODE, bool PSY, int NW, int IOF = 0, int SPREAD = 0, bool EPI = false, class QUANT = NoQuant>
+__device__ __forceinline__ void fwd_fast_body(const FwdArgs& a, char* lds, const int bid, const int nblocks, QUANT qz = QUANT()) {
   static_assert(!EPI || (PSY && CMODE == 0 && IOF == 0), "the element-wise epilogues ride on the stereo float32 fused encode");
+  constexpr bool QNT = !std::is_same<QUANT, NoQuant>::value;
+  static_assert(!QNT || (PSY && !EPI && IOF == 0 && R == 8), "the quantiser rides on the float32 fused encode at 8 points per lane");
   using G = Geo<R>;
   constexpr int WSTRIDE = PSY ? WAVE_LDS_PSY : WAVE_LDS;
   constexpr bool NOPRE = fwd_nopre<R, PSY, SPREAD>();
@@ -75,6 +85,7 @@ __device__ __forceinline__ void fwd_fast_body(const FwdArgs& a, char* lds, const
   if constexpr (!EPI) load_p1<R>(a.tab, lane, p1);
   PsyLane<R> pc;
   if (PSY) pc = load_psy_lane<R>(a.psy.tab, lane, (uint32_t)(wave * WSTRIDE));
+  if constexpr (QNT) qz.init(lane);
   int g = bid;
   if (a.xcd) g = (g & 7) * (nblocks >> 3) + (g >> 3);
   const int C = a.C;
@@ -124,7 +135,7 @@ __device__ __forceinline__ void fwd_fast_body(const FwdArgs& a, char* lds, const
       }
     }
     if (a.Kin == 0 && !(decltype(which)::value == 1 && fn == 0 && xstate)) {   // no PCM at all: any mapped address
-      s0 = s1 = reinterpret_cast<const pcm_t*>(a.X);
+      s0 = s1 = reinterpret_cast<const pcm_t*>(QNT ? static_cast<const void*>(a.tab) : static_cast<const void*>(a.X));
       ok = false;
     }
     if constexpr (IOF != 0) load_row_h<typename RowFmt<IOF>::type, CMODE, R>(s0, s1, C, q.has1, lane, dst);
@@ -245,6 +256,8 @@ __device__ __forceinline__ void fwd_fast_body(const FwdArgs& a, char* lds, const
     if constexpr (IOF == 2) {
       int16_t* Xh = reinterpret_cast<int16_t*>(a.X);
       store_row_h<Bf16Fmt, CMODE, R>(Xh + o0, Xh + o1, C, pq.has1, lane, row);
+    } else if constexpr (QNT) {
+      if (a.X) store_row<CMODE, R>(a.X + o0, a.X + o1, C, pq.has1, lane, row);
     } else {
       store_row<CMODE, R>(a.X + o0, a.X + o1, C, pq.has1, lane, row);
     }
@@ -264,7 +277,9 @@ __device__ __forceinline__ void fwd_fast_body(const FwdArgs& a, char* lds, const
       ++pair;
     }
     --left;
-    if constexpr (PSY) {
+    if constexpr (PSY && QNT) {
+      qz.frame(a, row, lds, buf, pimg, pc, lane, pq, o0, o1, t0, t1);
+    } else if constexpr (PSY) {
       v2f tt;
       v4f th[R];
       if constexpr (IOF == 2) {
@@ -318,6 +333,68 @@ template <int R, int CMODE, bool PSY, int NW, int IOF = 0, int SPREAD = 0, bool 
 __global__ __launch_bounds__(NW * 64, (wpe<R, CMODE, PSY, SPREAD>())) void k_fwd_fast(FwdArgs a) {
   __shared__ __attribute__((aligned(16))) char lds[fwd_lds_bytes<R, PSY, NW, SPREAD>()];
   fwd_fast_body<R, CMODE, PSY, NW, IOF, SPREAD, EPI>(a, lds, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// (host) arguments and grid of the one-frame-per-wave analysis kernels (filters_n 1024 / 2048)
+int prep_fwd_fast(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, int iof, float* X, float* t,
+                  float* thr, float drown, const float* prev_block, int B, int Kin, int F, int C, float* state_out,
+                  float* noisy, float* dbn, uint64_t seed, FwdArgs& a, unsigned& grid) {
+  // combinations no kernel is instantiated for (ac_api.hip routes them elsewhere; refuse rather than launch nothing)
+  if ((iof == 2 && C > 2) || (psy && p->N == Geo<16>::FN && (C == 1 || (iof == 1 && C > 2)))) {
+    set_error("internal: no wave-level analysis kernel for filters_n = %d, %d channels, io format %d%s", p->N, C, iof,
+              psy ? ", fused masking model" : "");
+    return AC_EUNSUPPORTED;
+  }
+  a.x = x;
+  a.X = X;
+  a.t = t;
+  a.thr = thr;
+  a.prev_block = prev_block;
+  a.state_out = state_out;
+  a.noisy = noisy;
+  a.dbn = dbn;
+  a.noise_key = mix64(seed);
+  if ((noisy || dbn) && !fast_epilogue_supported(p, psy, iof, C)) {
+    set_error("internal: no fused element-wise epilogue for this configuration");
+    return AC_EUNSUPPORTED;
+  }
+  a.tab = p->d_fast;
+  if (psy) a.psy = psy_params(psy, drown);
+  else a.psy = PsyParams{nullptr, 0.f, 0.f, 0.f};
+  a.B = B;
+  a.Kin = Kin;
+  a.F = F;
+  a.C = C;
+  a.nsig = (long long)B * C;
+  a.npairs = (C == 2) ? (long long)B : (a.nsig + 1) / 2;
+  a.nframes = a.npairs * F;
+  {
+    const double ang = -3.14159265358979323846 / (4.0 * p->N), sc = (double)p->N * 1.4142135623730951;   // 1 / (1 / (N sqrt 2))
+    a.pre_re = (float)(std::cos(ang) * sc);
+    a.pre_im = (float)(std::sin(ang) * sc);
+  }
+  // tuning hooks (read once): AC_XCD=1 groups consecutive workgroups per XCD; AC_FWD_T = frames per wave, workgroups
+  // dispatched in order (default 4: measured 0.603 ms against 0.615 ms for persistent waves, B = 256, K = 468 -- fresh
+  // workgroups keep the window of memory in flight contiguous); AC_FWD_T=0 = persistent waves, AC_WG_PER_CU per CU
+  static const int xcd = [] { const char* e = getenv("AC_XCD"); return e ? atoi(e) : 0; }();
+  static const int wgcu = [] { const char* e = getenv("AC_WG_PER_CU"); return e ? atoi(e) : 3; }();
+  static const int tper = [] { const char* e = getenv("AC_FWD_T"); return e ? atoi(e) : 4; }();
+  a.xcd = xcd;
+  const int nw = psy ? AC_WAVES_PSY : AC_WAVES;
+  // small launches (a streaming chunk of one clip): fewer frames per wave, so that the frames spread over the chip
+  // instead of queueing behind each other in a few workgroups
+  int tper_eff = tper;
+  while (tper_eff > 1 && a.nframes < (long long)nw * tper_eff * p->cus * 2) tper_eff >>= 1;
+  a.T = tper_eff;
+  if (tper > 0) {
+    // workgroups in eights (XCDs): ceil(ceil(nframes / per) / 8) = ceil(nframes / (8 per))
+    const long long per8 = 8ll * nw * tper_eff;
+    const int st = grid_for((a.nframes + per8 - 1) / per8 * 8, 1, &grid);
+    if (st) return st;
+  } else {
+    grid = persistent_grid(p->cus, wgcu, a.nframes, nw);
+  }
+  return AC_OK;
 }
 
 }  // namespace

@@ -146,6 +146,10 @@ struct NoEmit {
   __device__ __forceinline__ void begin() {}
   __device__ __forceinline__ void operator()(int, const v4f&) {}
 };
+template <class E, class = void>
+struct emit_pins_products : std::false_type {};
+template <class E>
+struct emit_pins_products<E, std::void_t<decltype(E::pin_products)>> : std::true_type {};
 // EMIT: begin() once the masking model has its per-entry values, then (i, threshold of granule 64 i + lane) as each granule
 // of the threshold row comes out of the entry lookup (the kernels with element-wise epilogues consume it there instead of
 // holding the whole row)
@@ -251,7 +255,17 @@ __device__ __forceinline__ void psy_stage(const v4f (&xq)[R], char* lds0, char* 
     acc = spread_mfma<SPREAD>(Q, reinterpret_cast<const char*>(pimg) + P::PSY_LDS, lane);
   }
   const v4f bc1 = pc.bc1;
-  const v2f offset = (1.0f - pp.drown) * (t * bc1.x + 9.0f * t + 5.5f);                        // (:185-191)
+  // t beta + 9 t: the kernels round 9 t and fuse t beta into the sum.  An EMIT that declares pin_products (the quantising
+  // encode, whose thresholds must be k_fwd_fast's to the last bit) pins that choice: left to -ffp-contract=fast, its
+  // instance rounds t beta and fuses 9 t
+  v2f offset;
+  if constexpr (emit_pins_products<typename std::remove_reference<EMIT>::type>::value) {
+    v2f t9 = 9.0f * t;
+    asm("" : "+v"(t9));
+    offset = (1.0f - pp.drown) * (t * bc1.x + t9 + 5.5f);
+  } else {
+    offset = (1.0f - pp.drown) * (t * bc1.x + 9.0f * t + 5.5f);                                // (:185-191)
+  }
   const v2f fac = exp2v(offset * (-pp.alpha * 0.33219280948873623f));                          // 10^(-alpha O / 10)
   const v2f T = exp2v(pp.inv_alpha * log2v(maxv(fac * acc, kEps)));                             // (:208)
   v2f G = maxv(T, pc.bc0[0].w);                                                                 // (:144)

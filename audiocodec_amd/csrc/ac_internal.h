@@ -258,6 +258,12 @@ int launch_fwd_fast(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x
                     float* state_out = nullptr, float* noisy = nullptr, float* dbn = nullptr, uint64_t seed = 0);
 // noisy / dbn (either may be null): the element-wise epilogues of ac_encode_fused_ex, where fast_epilogue_supported()
 bool fast_epilogue_supported(const ac_mdct_plan* p, const ac_psy_plan* psy, int iof, int C);
+// the fused encode that quantises in the same launch (k_fwd_fast_q, ac_fast_fwd_q.hip): float32 PCM, filters_n = 1024, mono /
+// stereo, f32 or split-bf16 spreading.  codes int16 [B,F,N,C] and sf int8 [B,F,M,C] equal launch_quantize on launch_fwd_fast's
+// X and thr bit for bit; X, t and thr may each be null (not written)
+bool fast_encode_quant_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);
+int launch_fwd_fast_quant(const ac_mdct_plan* p, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
+                          float drown, int16_t* codes, int8_t* sf, int B, int Kin, int F, int C, hipStream_t s);
 int launch_inv_fast(const ac_mdct_plan* p, const float* X, void* x, int iof, const float* tail_in, float* tail_out,
                     int B, int Kp, int nblk, int C, hipStream_t s);
 // synthesis straight from quantised spectra (codes int16 [B,Kp,N,C], sf int8 [B,Kp,M,C]; ac_quant.hip), filters_n 1024 /

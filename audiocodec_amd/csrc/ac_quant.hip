@@ -54,10 +54,7 @@ __global__ __launch_bounds__(kQuantThreads) void k_quantize(const float* __restr
   int8_t* sfrow = sf + row * (size_t)M * C + c0;
   for (int s = threadIdx.x; s < M * cg; s += blockDim.x) {
     const int j = s / cg, c = s - j * cg;
-    int q;
-    if (off[j] == off[j + 1]) q = 0;                 // empty band
-    else if (kmin[j * CG + c] == INT_MIN) q = -128;  // NaN / Inf in the band
-    else q = scale_factor_of(key_value(kmin[j * CG + c]));
+    const int q = band_scale_factor(off[j] == off[j + 1], kmin[j * CG + c]);
     store_sf(q, &sfrow[(size_t)j * C + c], &inv[j * CG + c]);
   }
   __syncthreads();

@@ -226,11 +226,24 @@ AC_API int ac_encode_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
  *   AC_EMIT_NOISY    noisy   [B,K+1,N,C] = X + thr * Normal(0, 1/6): the values ac_add_noise(X, thr, seed) gives, bit for bit;
  *   AC_EMIT_DB_NORM  db_norm [B,K+1,N,C] = amplitude_to_dB_norm(X): the values ac_amplitude_to_db(X, norm = 1) gives.
  * One launch for stereo float32 input on the wave-level kernels at filters_n = 1024; elsewhere the encode followed by
- * the two element-wise kernels.  flags = 0 is ac_encode_fused. */
-enum { AC_EMIT_NOISY = 1, AC_EMIT_DB_NORM = 2 };
+ * the two element-wise kernels.  flags = 0 is ac_encode_fused.
+ *   AC_EMIT_CODES    the quantising encode; exclusive with the other two flags.  The two output arguments are then read as
+ *     int16_t* codes [B,K+1,N,C] and int8_t* sf [B,K+1,M,C] (seed is ignored): what ac_quantize gives on the X and thr of
+ *     ac_encode_fused, bit for bit.  X, t and thr are each optional: NULL = not produced.  Where
+ *     ac_encode_quantized_launches returns 1 this is ONE launch that quantises the frame while it is in registers and writes
+ *     no float tensor the caller did not ask for; where it returns 2 the call runs the encode followed by the quantiser and
+ *     needs X, t and thr as its intermediates (AC_EINVAL when one of them is NULL).
+ * out0 / out1: float* noisy, float* db_norm under AC_EMIT_NOISY / AC_EMIT_DB_NORM; int16_t* codes, int8_t* sf under
+ * AC_EMIT_CODES. */
+enum { AC_EMIT_NOISY = 1, AC_EMIT_DB_NORM = 2, AC_EMIT_CODES = 4 };
 AC_API int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
-                       float drown, int flags, float* noisy, float* db_norm, uint64_t seed, int B, int K, int C,
+                       float drown, int flags, void* out0, void* out1, uint64_t seed, int B, int K, int C,
                        void* stream);
+/* Launches of ac_encode_fused_ex with AC_EMIT_CODES on tensors of C channels: 1 = the fused kernel (filters_n = 1024 on the
+ * wave-level kernels, mono / stereo float32, the f32 or split-bf16 spreading product), 2 = encode + quantiser (everything
+ * else, and every configuration while AC_ENCODE_QUANT_NOFUSE=1 is set in the environment: read per call).  0 for NULL or
+ * inconsistent plans.  The results do not depend on it. */
+AC_API int ac_encode_quantized_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C);
 
 /* 16-bit PCM at the boundary (extension; the reference takes float PCM in [-1, 1] only, mdctransformer.py:104):
  * x = pcm / 32768 on the way in; on the way out pcm = 0 if x is NaN else clamp(rint(fp32(32768 x)), -32768, 32767), rint

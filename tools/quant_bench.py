@@ -1,7 +1,9 @@
 """Quantiser at the bench workload (B = 256 clips, stereo, K = 468 blocks, filters_n 1024): quantize, the fused synthesis
 from codes (float32 and 16-bit PCM out) and decode() -- all allocating their results -- on the same process's tensors, timed
-with HIP events; decode_into() (a caller-owned output) for reference.
-python tools/quant_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5]"""
+with HIP events; decode_into() (a caller-owned output) for reference.  The quantising encode in its two forms -- encode() +
+quantize() (AC_ENCODE_QUANT_NOFUSE=1, two launches) and the one launch of k_fwd_fast_q -- beside encode(): bytes = PCM in +
+codes + sf out; then the two forms alternating over --rounds rounds, with the spread of the rounds.
+python tools/quant_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7]"""
 import argparse
 import os
 import sys
@@ -33,13 +35,13 @@ def main():
     ap.add_argument("--channels", type=int, default=2)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
     B, K, N, C = a.clips, a.blocks, a.filters, a.channels
     codec = audiocodec_amd.AudioCodec(48000, N)
     M = codec.psy.bark_bands_n
     x = (torch.rand((B, K * N, C), device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * 2 - 1)
     X, _, thr = codec.encode(x)
-    del x
     codes, sf = codec.psy.quantize(X, thr)
     F = K + 1
     nbin = B * F * N * C
@@ -48,7 +50,19 @@ def main():
     out_f = torch.empty((B, (F + 1) * N, C), dtype=torch.float32, device="cuda")
     print("quant_bench: B=%d K=%d N=%d C=%d M=%d  decode_quantized launches=%d  %s"
           % (B, K, N, C, M, codec.decode_quantized_launches(C), torch.cuda.get_device_name()))
+    enc_b = B * K * N * C * 4 + code_b + sf_b
+
+    def two_launches():
+        os.environ["AC_ENCODE_QUANT_NOFUSE"] = "1"   # (read per call)
+        try:
+            return codec.encode_quantized(x)
+        finally:
+            del os.environ["AC_ENCODE_QUANT_NOFUSE"]
+
     rows = [
+        ("encode", lambda: codec.encode(x), enc_b),
+        ("encode + quantize (two launches)", two_launches, enc_b),
+        ("encode_quantized (one launch)", lambda: codec.encode_quantized(x), enc_b),
         ("quantize", lambda: codec.psy.quantize(X, thr), nbin * 8 + code_b + sf_b),
         ("decode_quantized f32", lambda: codec.decode_quantized(codes, sf), code_b + sf_b + pcm_f32),
         ("decode_quantized pcm16", lambda: codec.decode_quantized(codes, sf, pcm16=True), code_b + sf_b + pcm_i16),
@@ -60,8 +74,24 @@ def main():
     for name, fn, nbytes in rows:
         ms = timed(fn, a.steps, a.warmup)
         res[name] = ms
-        print("%-24s %8.3f ms  %6.3f GB  %6.2f TB/s" % (name, ms, nbytes / 1e9, nbytes / ms / 1e9))
+        print("%-34s %8.3f ms  %6.3f GB  %6.2f TB/s" % (name, ms, nbytes / 1e9, nbytes / ms / 1e9))
     print("decode_quantized f32 / decode f32 = %.3f" % (res["decode_quantized f32"] / res["decode f32"]))
+    if a.rounds < 1:
+        return
+    # the two forms of the quantising encode and encode(), alternating in this process
+    names = ("encode", "encode + quantize (two launches)", "encode_quantized (one launch)")
+    fns = dict((n, f) for n, f, _ in rows[:3])
+    runs = dict((n, []) for n in names)
+    for _ in range(a.rounds):
+        for n in names:
+            runs[n].append(timed(fns[n], a.steps, 1))
+    med = {}
+    for n in names:
+        v = sorted(runs[n])
+        med[n] = v[len(v) // 2]
+        print("%-34s median %.3f ms  min %.3f  max %.3f  (%d alternating rounds of %d)" % (n, med[n], v[0], v[-1], len(v), a.steps))
+    print("one launch / two launches = %.3f   one launch / encode = %.3f"
+          % (med[names[2]] / med[names[1]], med[names[2]] / med[names[0]]))
 
 
 if __name__ == "__main__":
