@@ -114,6 +114,8 @@ PROTOTYPES = {
     "ac_unpack": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ac_quantize_budget": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_int, c_int, c_int, c_void_p]),
+    "ac_psy_plan_with_row_budget": (c_int, [c_void_p, c_int, c_int, POINTER(c_void_p)]),
+    "ac_psy_plan_row_budget": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
     "ac_clip_budget_scratch_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "ac_quantize_clip_budget": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -9,6 +9,7 @@ and SURVEY.md section 0 item 3 defines them as thin compositions of the referenc
 
 from __future__ import annotations
 
+import copy
 import ctypes
 import math
 
@@ -32,7 +33,24 @@ class AudioCodec:
                                        spreading=spreading)
         self.filters_n = int(filters_n)
         self.compute_dtype = self.mdct.compute_dtype
+        self.row_bits = None      # the row budget of a codec made by with_row_budget() / with_bitrate()
         self._lib = _lib.load()
+
+    def with_row_budget(self, row_bits, min_offset=0):
+        """A codec at a constant bitrate: it shares ``mdct`` with this one and carries
+        ``psy.with_row_budget(row_bits, min_offset)``.  On it :meth:`encode_quantized` and :meth:`encode_packed` give the
+        codes and scale factors of ``encode_quantized_budget(x, row_bits, min_offset)`` -- in one launch where
+        :meth:`encode_quantized_launches` is 1 -- and ``row_bits`` holds the budget.  :meth:`encode`, the ``decode*``
+        methods, the explicit ``*_budget`` methods and autograd behave as on this codec.  ``row_bits``: an int, at least
+        5 * bark_bands_n; ``min_offset`` in [-254, 254]; float32 only."""
+        new = copy.copy(self)
+        new.psy = self.psy.with_row_budget(row_bits, min_offset)
+        new.row_bits = int(row_bits)
+        return new
+
+    def with_bitrate(self, bits_per_second, min_offset=0):
+        """:meth:`with_row_budget` at :meth:`row_bits_for_bitrate` of a per-channel bitrate."""
+        return self.with_row_budget(self.row_bits_for_bitrate(bits_per_second), min_offset)
 
     def encode_launches(self, channels_n=2, device=None):
         """How many kernel launches :meth:`encode` takes for float32 tensors of ``channels_n`` channels on ``device``
@@ -205,7 +223,8 @@ class AudioCodec:
         ``torch.int16`` PCM) -> (codes int16 [B, K+1, N, C], sf int8 [B, K+1, M, C]).  One launch that writes only codes and
         scale factors where :meth:`encode_quantized_launches` is 1 and ``x`` is float32 (``ac_encode_fused_ex`` with
         ``AC_EMIT_CODES``: the same values, bit for bit); elsewhere two launches with X, tonality and threshold as
-        temporaries.  float32 only, not differentiable."""
+        temporaries.  On a codec made by :meth:`with_row_budget` / :meth:`with_bitrate` the quantiser is
+        ``quantize_to_budget`` at the codec's budget, in the same number of launches.  float32 only, not differentiable."""
         if (self.compute_dtype == torch.float32 and isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.is_cuda
                 and x.dim() == 3 and not (x.requires_grad and torch.is_grad_enabled())
                 and x.shape[1] % self.filters_n == 0

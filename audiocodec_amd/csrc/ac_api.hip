@@ -467,6 +467,30 @@ static int psy_plan_build(int N, int M, double sample_rate, double alpha, int de
   return AC_OK;
 }
 
+// `plan` with a row budget, as a plan of its own: the same constants, built again for the same device (it owns its tables)
+int ac_psy_plan_with_row_budget(const ac_psy_plan* plan, int row_bits, int kmin, ac_psy_plan** out) {
+  AC_REQUIRE(out != nullptr, "out is NULL");
+  *out = nullptr;
+  AC_REQUIRE(plan != nullptr, "plan is NULL");
+  AC_REQUIRE(kmin >= -254 && kmin <= 254, "kmin (%d) outside [-254, 254]", kmin);
+  AC_REQUIRE(row_bits >= 5 * plan->M, "row_bits (%d) below 5 * bark_bands_n = %d, the length of a row that stores no band",
+             row_bits, 5 * plan->M);
+  ac_psy_plan* p = nullptr;
+  const int st = psy_plan_build(plan->N, plan->M, plan->sample_rate, plan->alpha, plan->device, plan->spread, plan->pre, &p);
+  if (st) return st;
+  p->row_bits = row_bits;
+  p->kmin = kmin;
+  *out = p;
+  return AC_OK;
+}
+
+int ac_psy_plan_row_budget(const ac_psy_plan* plan, int* row_bits, int* kmin) {
+  AC_REQUIRE(plan != nullptr, "plan is NULL");
+  if (row_bits) *row_bits = plan->row_bits;
+  if (kmin) *kmin = plan->row_bits ? plan->kmin : 0;
+  return AC_OK;
+}
+
 int ac_psy_plan_destroy(ac_psy_plan* p) {
   if (!p) return AC_OK;
   DeviceGuard guard(p->device);
@@ -699,6 +723,13 @@ int ac_encode_fused(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const floa
   return encode_fused(mdct, psy, x, false, X, t, thr, drown, B, K, C, stream);
 }
 static int check_quant(const ac_psy_plan* psy, int B, int F, int C);
+// the quantiser of a plan: at the plan's row budget where it has one (no offset or row-bits tensor to fill), else k_quantize
+static int quantize_of_plan(const ac_psy_plan* psy, const float* X, const float* thr, int16_t* codes, int8_t* sf, int B, int F,
+                            int C, hipStream_t s) {
+  if (psy->row_bits)
+    return launch_quantize_budget(psy, X, thr, psy->row_bits, nullptr, psy->kmin, codes, sf, nullptr, nullptr, B, F, C, s);
+  return launch_quantize(psy, X, thr, codes, sf, B, F, C, s);
+}
 // whether AC_EMIT_CODES is one launch (k_fwd_fast_q); AC_ENCODE_QUANT_NOFUSE=1 sends every configuration down the two
 // launches (A/B measurements: read per call, so that one process can time both forms)
 static bool encode_quantized_fuses(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C) {
@@ -727,6 +758,9 @@ static int encode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, co
     AC_REQUIRE(x != nullptr || K == 0, "NULL tensor pointer");
     AC_REQUIRE_ALIGNED(x, X, thr, codes, sf);
     DeviceGuard guard(mdct->device);
+    if (psy->row_bits)
+      return launch_fwd_fast_quant_budget(mdct, psy, x, X, t, thr, drown, psy->row_bits, psy->kmin, codes, sf, B, K, K + 1, C,
+                                          (hipStream_t)stream);
     return launch_fwd_fast_quant(mdct, psy, x, X, t, thr, drown, codes, sf, B, K, K + 1, C, (hipStream_t)stream);
   }
   AC_REQUIRE(X != nullptr && t != nullptr && thr != nullptr,
@@ -735,7 +769,7 @@ static int encode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, co
   st = encode_fused(mdct, psy, x, false, X, t, thr, drown, B, K, C, stream);
   if (st) return st;
   DeviceGuard guard(psy->device);
-  return launch_quantize(psy, X, thr, codes, sf, B, K + 1, C, (hipStream_t)stream);
+  return quantize_of_plan(psy, X, thr, codes, sf, B, K + 1, C, (hipStream_t)stream);
 }
 
 int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
@@ -1047,7 +1081,7 @@ int ac_quantize(const ac_psy_plan* psy, const float* X, const float* thr, int16_
   AC_REQUIRE(X != nullptr && thr != nullptr && codes != nullptr && sf != nullptr, "NULL tensor pointer");
   AC_REQUIRE_ALIGNED(X, thr, codes, sf);
   DeviceGuard guard(psy->device);
-  return launch_quantize(psy, X, thr, codes, sf, B, F, C, (hipStream_t)stream);
+  return quantize_of_plan(psy, X, thr, codes, sf, B, F, C, (hipStream_t)stream);
 }
 
 int ac_dequantize(const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, float* X, int B, int F, int C, void* stream) {

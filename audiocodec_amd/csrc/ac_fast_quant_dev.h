@@ -11,15 +11,24 @@
 // own (no two lanes of a step do so for the same band).  Run heads fold into 64 x 2 integer slots with ds_min.  The slots,
 // and the inverse steps behind them, live in the wave's 8 KB intensity image, which the masking model is done with once the
 // entry table (the first 1 KB of the region) is written.
+//
+// BUDGET (k_fwd_fast_qb, instantiated in ac_fast_fwd_qb.hip): rate control in the same launch.  Behind
+// the masking model the wave adds the other two statistics of ac_rate_dev.h -- the largest and smallest X key per band and
+// signal, reduced from the row in registers over the same runs into two more slot arrays -- and, lane j holding band j's
+// meta word and extremes, bisects [kmin, 254] once per signal of the pair as k_quantize_budget does: band_bits per lane,
+// wave_sum for the row.  codes and sf equal k_quantize_budget on the X and thr of k_fwd_fast bit for bit.
 #pragma once
 #include "ac_band_dev.h"
 #include "ac_fast_fwd_dev.h"
+#include "ac_rate_dev.h"
 
 namespace ac {
 namespace {
 
 constexpr int QSLOT_OFF = 4096;           // [64 bands][2 signals] int: smallest threshold key of the band
 constexpr int QINV_OFF = QSLOT_OFF + 512; // [64 bands][2 signals] float: inverse step, NaN for sf = -128
+constexpr int QKX_OFF = QINV_OFF + 512;   // [64 bands][2 signals] int: largest X key of the band (BUDGET)
+constexpr int QKN_OFF = QKX_OFF + 512;    // [64 bands][2 signals] int: smallest X key of the band (BUDGET)
 
 struct QuantOut {
   int16_t* codes;            // [B, F, N, C]
@@ -28,8 +37,16 @@ struct QuantOut {
   const int32_t* off;        // ac_psy_plan::d_qoff: band offsets [M + 1]
 };
 
-template <int R, int CMODE, int SPREAD>
-struct QuantStage {
+// the plan's row budget (ac_psy_plan_with_row_budget) and what the search keeps per lane
+struct QuantBudget {
+  int row_bits, kmin;
+  uint32_t len;   // one register for all three: bins of band `lane` in bits 0-10; above them row_bits (lane 0; at most 2^20,
+                  // beyond any row's length) and kmin + 254 (lane 1)
+};
+struct NoQuantBudget {};
+
+template <int R, int CMODE, int SPREAD, bool BUDGET = false>
+struct QuantStage : std::conditional<BUDGET, QuantBudget, NoQuantBudget>::type {
   static_assert(CMODE == 0 || CMODE == 2, "quantised spectra: mono / stereo");
   static constexpr int M = 64;   // lane j = band j
   QuantOut q;
@@ -61,6 +78,10 @@ struct QuantStage {
     codes_l = q.codes + (CMODE == 0 ? 4 : 2) * lane;
     sf_l = q.sf + (CMODE == 0 ? 2 : 1) * lane;
     asm volatile("" : "+v"(codes_l), "+v"(sf_l), "+v"(pp.alpha), "+v"(pp.inv_alpha), "+v"(pp.drown));
+    if constexpr (BUDGET) {
+      const uint32_t hi = lane == 0 ? (uint32_t)min(this->row_bits, 1 << 20) : (uint32_t)(this->kmin + kRateMaxOffset);
+      this->len = (uint32_t)(q.off[lane + 1] - q.off[lane]) | (hi << 11);
+    }
   }
   __device__ __forceinline__ BandRuns runs(int i) const {
     // (unpacked inside the frame loop: hoisted, the masks of eight steps would not fit the scalar registers)
@@ -114,6 +135,50 @@ struct QuantStage {
     }
   };
 
+  // BUDGET: the largest and smallest X key per band and signal of the frame in `row` into the slots at QKX_OFF / QKN_OFF
+  // (initialised by the caller), folded over the runs as Emit folds the threshold keys
+  __device__ __forceinline__ void extremes(const v4f (&row)[R], char* buf) const {
+    int* kxs = reinterpret_cast<int*>(buf + QKX_OFF);
+    int* kns = reinterpret_cast<int*>(buf + QKN_OFF);
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const v4f x = row[i];
+      const uint32_t w = in_loop(bw[i]);
+      const int je = (int)(w & 0xffffu), jo = (int)(w >> 16);
+      const int ke0 = ordered_key(x.x), ke1 = ordered_key(x.y), ko0 = ordered_key(x.z), ko1 = ordered_key(x.w);
+      const bool split = jo != je;
+      const BandRuns r = runs(i);
+      const int x0 = run_reduce(r, split ? ke0 : max(ke0, ko0), MaxOp());
+      const int x1 = run_reduce(r, split ? ke1 : max(ke1, ko1), MaxOp());
+      const int n0 = run_reduce(r, split ? ke0 : min(ke0, ko0), MinOp());
+      const int n1 = run_reduce(r, split ? ke1 : min(ke1, ko1), MinOp());
+      if (r.head) {
+        atomicMax(&kxs[2 * je], x0);
+        atomicMax(&kxs[2 * je + 1], x1);
+        atomicMin(&kns[2 * je], n0);
+        atomicMin(&kns[2 * je + 1], n1);
+      }
+      if (split) {
+        atomicMax(&kxs[2 * jo], ko0);
+        atomicMax(&kxs[2 * jo + 1], ko1);
+        atomicMin(&kns[2 * jo], ko0);
+        atomicMin(&kns[2 * jo + 1], ko1);
+      }
+    }
+  }
+  // BUDGET: the row's offset -- the smallest k in [kmin, 254] whose bits fit row_bits, else 254: the interval rule of
+  // k_quantize_budget (ac_rate.hip).  Lane j holds band j's meta word and extremes; every value of the search is wave-uniform
+  static __device__ __forceinline__ int row_offset(int meta, int kx, int kn, int row_bits, int kmin) {
+    int lo = kmin, hi = kRateMaxOffset;
+    while (lo < hi) {
+      const int mid = lo + ((hi - lo) >> 1);
+      const int bits = 5 * M + __builtin_amdgcn_readfirstlane(wave_sum(band_bits(meta, kx, kn, mid)));
+      if (bits <= row_bits) hi = mid;
+      else lo = mid + 1;
+    }
+    return lo;
+  }
+
   // the masking model on the frame in `row`, then scale factors (lane j: band j) and codes
   __device__ __forceinline__ void frame(const FwdArgs& a, const v4f (&row)[R], char* lds, char* buf, const uint32_t* pimg,
                                         const PsyLane<R>& pc, int lane, const Pair& pq, size_t o0, size_t o1, size_t t0,
@@ -139,9 +204,29 @@ struct QuantStage {
       *tp0 = tt.x;
       if (pq.has1) *tp1 = tt.y;
     }
+    if constexpr (BUDGET) {
+      *reinterpret_cast<int2*>(buf + QKX_OFF + 8 * lane) = make_int2(INT_MIN, INT_MIN);
+      *reinterpret_cast<int2*>(buf + QKN_OFF + 8 * lane) = make_int2(INT_MAX, INT_MAX);
+    }
     wave_sync();
     float* inv = reinterpret_cast<float*>(buf + QINV_OFF);
-    {
+    if constexpr (BUDGET) {
+      extremes(row, buf);
+      wave_sync();
+      const int2 kt = *reinterpret_cast<const int2*>(buf + QSLOT_OFF + 8 * lane);
+      const int2 kx = *reinterpret_cast<const int2*>(buf + QKX_OFF + 8 * lane);
+      const int2 kn = *reinterpret_cast<const int2*>(buf + QKN_OFF + 8 * lane);
+      const uint32_t lk = in_loop(this->len);
+      const int L = (int)(lk & 0x7ffu);
+      const int m0 = band_meta<true>(L, kt.x), m1 = band_meta<true>(L, kt.y);
+      const int rb = __builtin_amdgcn_readlane((int)(lk >> 11), 0), k0 = __builtin_amdgcn_readlane((int)(lk >> 11), 1) - kRateMaxOffset;
+      const int off0 = row_offset(m0, kx.x, kn.x, rb, k0);
+      store_sf(band_sf(m0, off0), f0, &inv[2 * lane]);
+      if (CMODE == 0 || pq.has1) {
+        const int off1 = row_offset(m1, kx.y, kn.y, rb, k0);
+        store_sf(band_sf(m1, off1), f1, &inv[2 * lane + 1]);
+      }
+    } else {
       const int2 k = *reinterpret_cast<const int2*>(buf + QSLOT_OFF + 8 * lane);
       const bool none = in_loop(empty) != 0;
       const int q0 = band_scale_factor<true>(none, k.x), q1 = band_scale_factor<true>(none, k.y);
@@ -178,6 +263,22 @@ __global__ __launch_bounds__(AC_WAVES_PSY * 64, 2) void k_fwd_fast_q(FwdArgs a, 
   a.state_out = nullptr;
   a.noisy = a.dbn = nullptr;
   fwd_fast_body<8, CMODE, true, AC_WAVES_PSY, 0, SPREAD, false, QuantStage<8, CMODE, SPREAD>>(a, lds, (int)blockIdx.x, (int)gridDim.x, qz);
+}
+
+// ... with the row budget of the plan met in the same launch (QuantStage's BUDGET form)
+template <int CMODE, int SPREAD>
+__global__ __launch_bounds__(AC_WAVES_PSY * 64, 2) void k_fwd_fast_qb(FwdArgs a, QuantOut q, int row_bits, int kmin) {
+  __shared__ __attribute__((aligned(16))) char lds[fwd_lds_bytes<8, true, AC_WAVES_PSY, SPREAD>()];
+  QuantStage<8, CMODE, SPREAD, true> qz;
+  qz.q = q;
+  qz.pp = a.psy;
+  qz.row_bits = row_bits;
+  qz.kmin = kmin;
+  a.C = CMODE == 0 ? 2 : 1;
+  a.prev_block = nullptr;
+  a.state_out = nullptr;
+  a.noisy = a.dbn = nullptr;
+  fwd_fast_body<8, CMODE, true, AC_WAVES_PSY, 0, SPREAD, false, QuantStage<8, CMODE, SPREAD, true>>(a, lds, (int)blockIdx.x, (int)gridDim.x, qz);
 }
 
 }  // namespace

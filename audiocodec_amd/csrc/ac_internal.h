@@ -170,6 +170,9 @@ struct ac_psy_plan {
   // read as one 32-bit word per bin pair by the fused synthesis from codes)
   int32_t* d_qoff = nullptr;
   uint16_t* d_qband = nullptr;
+  // row budget of a plan made by ac_psy_plan_with_row_budget (row_bits = 0: none): what ac_quantize and the quantising
+  // encode meet, as ac_quantize_budget(row_bits, NULL, kmin) does
+  int row_bits = 0, kmin = 0;
 };
 
 struct ac_stream {
@@ -264,6 +267,11 @@ bool fast_epilogue_supported(const ac_mdct_plan* p, const ac_psy_plan* psy, int 
 bool fast_encode_quant_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);
 int launch_fwd_fast_quant(const ac_mdct_plan* p, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
                           float drown, int16_t* codes, int8_t* sf, int B, int Kin, int F, int C, hipStream_t s);
+// ... at a row budget (k_fwd_fast_qb, ac_fast_fwd_qb.hip; the same plans and shapes): codes and sf equal
+// launch_quantize_budget(row_bits, nullptr, kmin) on launch_fwd_fast's X and thr bit for bit
+int launch_fwd_fast_quant_budget(const ac_mdct_plan* p, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
+                                 float drown, int row_bits, int kmin, int16_t* codes, int8_t* sf, int B, int Kin, int F, int C,
+                                 hipStream_t s);
 int launch_inv_fast(const ac_mdct_plan* p, const float* X, void* x, int iof, const float* tail_in, float* tail_out,
                     int B, int Kp, int nblk, int C, hipStream_t s);
 // synthesis straight from quantised spectra (codes int16 [B,Kp,N,C], sf int8 [B,Kp,M,C]; ac_quant.hip), filters_n 1024 /
@@ -358,7 +366,7 @@ int launch_quantize(const ac_psy_plan* p, const float* X, const float* thr, int1
                     hipStream_t s);
 int launch_dequantize(const ac_psy_plan* p, const int16_t* codes, const int8_t* sf, float* X, int B, int F, int C, hipStream_t s);
 // rate control (ac_rate.hip): the quantiser at the smallest offset in [kmin, 254] whose packed row fits the row's budget
-// (row_budget [B,F,C] int32, or the scalar budget where it is NULL) -> codes, sf, offset int16 [B,F,C], row_bits (or NULL)
+// (row_budget [B,F,C] int32, or the scalar budget where it is NULL) -> codes, sf, offset int16 [B,F,C] (or NULL), row_bits (or NULL)
 int launch_quantize_budget(const ac_psy_plan* p, const float* X, const float* thr, int budget, const int32_t* row_budget,
                            int kmin, int16_t* codes, int8_t* sf, int16_t* offset, int32_t* row_bits, int B, int F, int C,
                            hipStream_t s);

@@ -2,7 +2,7 @@
 // raised by one offset k, the smallest k in [kmin, 254] whose packed row (section 8b) fits the row's bit budget.
 //
 //   k_quantize_budget  X, thr [B,F,N,C] float32, budget -> codes int16 [B,F,N,C], sf int8 [B,F,M,C], offset int16 [B,F,C],
-//                      row bits int32 [B,F,C]
+//                      row bits int32 [B,F,C] (either of the last two may be null: ac_quantize on a plan with a row budget)
 //
 // One workgroup per (clip, frame) row and group of channels, as k_quantize, in three phases:
 //   1. per (band, channel) the smallest thr key and the largest and smallest X key: band_stats (ac_rate_dev.h, shared with
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(kRateThreads) void k_quantize_budget(
     }
     const int bits = row_bits_at(kt + c, CG, slots, M, lane, lo);
     if (lane == 0) {
-      offset[rc] = (int16_t)lo;
+      if (offset) offset[rc] = (int16_t)lo;
       if (row_bits) row_bits[rc] = bits;
     }
     for (int j = lane; j < M; j += 64) {

@@ -10,9 +10,16 @@ namespace ac {
 constexpr int kRateMaxOffset = 254;
 
 // A band's statistics once its sf0 is known: meta = (length << 8) | (sf0 & 0xff); 0 for an empty band, -1 for sf0 = -128
-// (both store nothing at any offset); kx, kn the ordered keys of the band's largest and smallest X
+// (both store nothing at any offset); kx, kn the ordered keys of the band's largest and smallest X.  FLAT as in
+// band_scale_factor: the sf0 search runs for every lane and the special cases select afterwards; the value is the same
+template <bool FLAT = false>
 __device__ __forceinline__ int band_meta(int L, int kt) {
-  return L == 0 ? 0 : kt == INT_MIN ? -1 : (L << 8) | (scale_factor_of(key_value(kt)) & 0xff);
+  if constexpr (FLAT) {
+    const int s = scale_factor_of(key_value(kt));
+    return L == 0 ? 0 : kt == INT_MIN ? -1 : (L << 8) | (s & 0xff);
+  } else {
+    return L == 0 ? 0 : kt == INT_MIN ? -1 : (L << 8) | (scale_factor_of(key_value(kt)) & 0xff);
+  }
 }
 __device__ __forceinline__ int band_bits(int meta, int kx, int kn, int k) {
   if (meta <= 0) return 0;

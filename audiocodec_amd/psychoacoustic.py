@@ -8,6 +8,7 @@ library (host side), the per-frame model runs in hand-written HIP kernels.
 
 from __future__ import annotations
 
+import copy
 import ctypes
 
 import numpy as np
@@ -152,6 +153,37 @@ class PsychoacousticModel:
         mode = -1 if spreading is None else self.SPREADING[spreading]   # -1: the library's default for the plan
         create = lambda dev, out: lib.ac_psy_plan_create_pre(N, M, sr, al, dev, mode, pre, out)   # noqa: E731
         self._plans = _host.PlanCache(self, create, lib.ac_psy_plan_destroy)
+        self._row_budget = None
+        self._base = None
+
+    def with_row_budget(self, row_bits, min_offset=0):
+        """A model with the same constants whose plans carry a row budget (``ac_psy_plan_with_row_budget``; DESIGN.md
+        section 8c): on it :meth:`quantize` gives the codes and scale factors of
+        ``quantize_to_budget(X, thr, row_bits, min_offset)``, and a codec built around it encodes at that budget in its fused
+        launch.  Everything else is unchanged, :meth:`quantize_to_budget` and :meth:`quantize_to_clip_budget` (which obey
+        their own arguments) included.  Called on a budgeted model it replaces the budget.  ``row_bits``: an int, at least
+        5 * bark_bands_n; ``min_offset`` in [-254, 254]; float32 only."""
+        _host.require_float32(self.compute_dtype, "the quantiser")
+        if isinstance(row_bits, bool) or not isinstance(row_bits, (int, np.integer)):
+            raise TypeError("row_bits must be an int, got %s" % type(row_bits).__name__)
+        if not 5 * self.bark_bands_n <= int(row_bits) <= 2 ** 31 - 1:
+            raise ValueError("row_bits (%d) below 5 * bark_bands_n = %d, the length of a row that stores no band, or "
+                             "above int32" % (row_bits, 5 * self.bark_bands_n))
+        self._check_min_offset(min_offset)
+        base = self._base if self._base is not None else self
+        R, kmin, lib = int(row_bits), int(min_offset), self._lib
+        new = copy.copy(base)
+        new._base = base          # (the derived plans are built from the base model's: it stays alive with this one)
+        new._row_budget = (R, kmin)
+        create = lambda dev, out: lib.ac_psy_plan_with_row_budget(   # noqa: E731
+            base._plans.get(torch.device("cuda", dev)), R, kmin, out)
+        new._plans = _host.PlanCache(new, create, lib.ac_psy_plan_destroy)
+        return new
+
+    @property
+    def row_budget(self):
+        """``(row_bits, min_offset)`` of a model made by :meth:`with_row_budget`, else None."""
+        return self._row_budget
 
     def _plan(self, device):
         return self._plans.get(device)
@@ -370,7 +402,8 @@ class PsychoacousticModel:
 
         Per scale-factor band (:attr:`scale_band_offsets`) and (clip, frame, channel) a step 2^(sf/4) with
         step * sqrt(3) <= the band's smallest threshold, so the error of a bin is at most thr / (2 sqrt 3), and the noise
-        RMS at most the thr / 6 of :meth:`add_noise`; sf = -128 marks a band holding NaN / Inf (its codes are 0).  Not
+        RMS at most the thr / 6 of :meth:`add_noise`; sf = -128 marks a band holding NaN / Inf (its codes are 0).  On a model
+        made by :meth:`with_row_budget`: the codes and sf of :meth:`quantize_to_budget` at that budget.  Not
         differentiable (:meth:`add_noise` is the differentiable stand-in); float32 only."""
         X, thr = self._check_quant_inputs(mdct_amplitudes, masking_threshold)
         B, F, N, C = X.shape

@@ -47,8 +47,8 @@ extern "C" {
 #define AC_VERSION 171 /* 0.1.8 + the quantiser (int16 codes, int8 per-band scale factors: ac_quantize, ac_dequantize,
                           * ac_decode_quantized[_launches], ac_psy_scale_bands_host), its packed bitstream (ac_pack_index,
                           * ac_pack, ac_unpack, ac_pack_scratch_bytes) and its rate control (ac_quantize_budget, per clip
-                          * ac_quantize_clip_budget, ac_clip_budget_scratch_bytes); additions
-                          * only, so the number stays.
+                          * ac_quantize_clip_budget, ac_clip_budget_scratch_bytes; in the plan: ac_psy_plan_with_row_budget,
+                          * ac_psy_plan_row_budget); additions only, so the number stays.
                           * 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
                           * with a 5-smooth half up to 8192, float32); masking model for general band layouts up to 4096 bins.
                           * 0.1.7: only the ac_* entry points are exported; ac_stream_settle (home buffers for the streaming state);
@@ -312,6 +312,23 @@ AC_API int ac_unpack(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes
 AC_API int ac_quantize_budget(const ac_psy_plan* psy, const float* X, const float* thr, int row_bits,
                               const int32_t* row_bits_per_row, int kmin, int16_t* codes, int8_t* sf, int16_t* offset,
                               int32_t* row_bits_out, int B, int F, int C, void* stream);
+
+/* A plan at a row budget: the budget travels in the plan, so that the entry points that quantise from sf0 serve a codec that
+ * IS at a bitrate, the fused encode among them.  ac_psy_plan_with_row_budget: a plan of its own with the N, M, sample rate,
+ * alpha, precompute type, spreading form and device of `plan`; it owns its device tables, is destroyed with
+ * ac_psy_plan_destroy, and its creation may block the host as the other plan builders may.  row_bits >= 5M and kmin in
+ * [-254, 254], AC_EINVAL otherwise; deriving from a derived plan replaces the budget.  Every entry point treats the derived
+ * plan exactly as `plan`, except the two that quantise from sf0:
+ *   ac_quantize(derived, X, thr, codes, sf, ...) writes the codes and sf ac_quantize_budget(plan, X, thr, row_bits, NULL,
+ *     kmin, ...) writes, bit for bit;
+ *   ac_encode_fused_ex(..., derived, ..., AC_EMIT_CODES, ...) gives that on the X and thr of ac_encode_fused, under the X / t /
+ *     thr rules of AC_EMIT_CODES: ONE launch that meets the budget while the frame is in registers where
+ *     ac_encode_quantized_launches returns 1, the encode followed by the budgeted quantiser where it returns 2.
+ * ac_quantize_budget and ac_quantize_clip_budget obey their own arguments on any plan.  Dequantise, pack, unpack and decode
+ * need nothing: the offset is in the scale factors.
+ * ac_psy_plan_row_budget: the budget of a plan into *row_bits and *kmin (either may be NULL); 0, 0 for a plan without one. */
+AC_API int ac_psy_plan_with_row_budget(const ac_psy_plan* plan, int row_bits, int kmin, ac_psy_plan** out);
+AC_API int ac_psy_plan_row_budget(const ac_psy_plan* plan, int* row_bits, int* kmin);
 
 /* Rate control per clip (extension): one budget for the F*C rows of a clip, r = f*C + c.  With bits_r(k)
  * of ac_quantize_budget, len_r(k) = 32 * ceil(bits_r(k) / 32) is a row's packed length with its padding and total_b(k) the sum

@@ -2,8 +2,10 @@
 from codes (float32 and 16-bit PCM out) and decode() -- all allocating their results -- on the same process's tensors, timed
 with HIP events; decode_into() (a caller-owned output) for reference.  The quantising encode in its two forms -- encode() +
 quantize() (AC_ENCODE_QUANT_NOFUSE=1, two launches) and the one launch of k_fwd_fast_q -- beside encode(): bytes = PCM in +
-codes + sf out; then the two forms alternating over --rounds rounds, with the spread of the rounds.
-python tools/quant_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7]"""
+codes + sf out; then the two forms alternating over --rounds rounds, with the spread of the rounds.  Likewise at a row budget
+(--row-bits): encode_quantized_budget() -- encode() + k_quantize_budget, two launches -- against
+encode_quantized() of the codec with_row_budget(), the one launch of k_fwd_fast_qb.
+python tools/quant_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7] [--row-bits 1365]"""
 import argparse
 import os
 import sys
@@ -36,10 +38,12 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--row-bits", type=int, default=1365)
     a = ap.parse_args()
     B, K, N, C = a.clips, a.blocks, a.filters, a.channels
     codec = audiocodec_amd.AudioCodec(48000, N)
     M = codec.psy.bark_bands_n
+    cbr = codec.with_row_budget(a.row_bits)
     x = (torch.rand((B, K * N, C), device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * 2 - 1)
     X, _, thr = codec.encode(x)
     codes, sf = codec.psy.quantize(X, thr)
@@ -63,6 +67,8 @@ def main():
         ("encode", lambda: codec.encode(x), enc_b),
         ("encode + quantize (two launches)", two_launches, enc_b),
         ("encode_quantized (one launch)", lambda: codec.encode_quantized(x), enc_b),
+        ("encode_quantized_budget (two launches)", lambda: codec.encode_quantized_budget(x, a.row_bits), enc_b),
+        ("cbr.encode_quantized (%d launch)" % cbr.encode_quantized_launches(C), lambda: cbr.encode_quantized(x), enc_b),
         ("quantize", lambda: codec.psy.quantize(X, thr), nbin * 8 + code_b + sf_b),
         ("decode_quantized f32", lambda: codec.decode_quantized(codes, sf), code_b + sf_b + pcm_f32),
         ("decode_quantized pcm16", lambda: codec.decode_quantized(codes, sf, pcm16=True), code_b + sf_b + pcm_i16),
@@ -74,24 +80,33 @@ def main():
     for name, fn, nbytes in rows:
         ms = timed(fn, a.steps, a.warmup)
         res[name] = ms
-        print("%-34s %8.3f ms  %6.3f GB  %6.2f TB/s" % (name, ms, nbytes / 1e9, nbytes / ms / 1e9))
+        print("%-40s %8.3f ms  %6.3f GB  %6.2f TB/s" % (name, ms, nbytes / 1e9, nbytes / ms / 1e9))
     print("decode_quantized f32 / decode f32 = %.3f" % (res["decode_quantized f32"] / res["decode f32"]))
     if a.rounds < 1:
         return
     # the two forms of the quantising encode and encode(), alternating in this process
     names = ("encode", "encode + quantize (two launches)", "encode_quantized (one launch)")
-    fns = dict((n, f) for n, f, _ in rows[:3])
-    runs = dict((n, []) for n in names)
-    for _ in range(a.rounds):
+    fns = dict((n, f) for n, f, _ in rows[:5])
+
+    def alternate(names):
+        runs = dict((n, []) for n in names)
+        for _ in range(a.rounds):
+            for n in names:
+                runs[n].append(timed(fns[n], a.steps, 1))
+        med = {}
         for n in names:
-            runs[n].append(timed(fns[n], a.steps, 1))
-    med = {}
-    for n in names:
-        v = sorted(runs[n])
-        med[n] = v[len(v) // 2]
-        print("%-34s median %.3f ms  min %.3f  max %.3f  (%d alternating rounds of %d)" % (n, med[n], v[0], v[-1], len(v), a.steps))
+            v = sorted(runs[n])
+            med[n] = v[len(v) // 2]
+            print("%-40s median %.3f ms  min %.3f  max %.3f  (%d alternating rounds of %d)" % (n, med[n], v[0], v[-1], len(v), a.steps))
+        return med
+
+    med = alternate(names)
     print("one launch / two launches = %.3f   one launch / encode = %.3f"
           % (med[names[2]] / med[names[1]], med[names[2]] / med[names[0]]))
+    # ... and the two forms of the encode at a row budget
+    names = tuple(n for n, _, _ in rows[3:5])
+    med = alternate(names)
+    print("row budget %d: cbr.encode_quantized / encode_quantized_budget = %.3f" % (a.row_bits, med[names[1]] / med[names[0]]))
 
 
 if __name__ == "__main__":
