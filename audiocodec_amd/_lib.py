@@ -108,6 +108,7 @@ PROTOTYPES = {
                                     c_void_p]),
     "ac_decode_quantized_launches": (c_int, [c_void_p, c_void_p, c_int]),
     "ac_encode_quantized_launches": (c_int, [c_void_p, c_void_p, c_int]),
+    "ac_decode_packed_launches": (c_int, [c_void_p, c_void_p, c_int]),
     "ac_pack_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ac_pack_index": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ac_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
@@ -120,6 +121,11 @@ PROTOTYPES = {
     "ac_quantize_clip_budget": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
 }
+
+class PackedRows(ctypes.Structure):
+    """``ac_packed_rows``: what ``ac_decode_quantized`` takes for ``codes`` when ``sf`` is NULL."""
+    _fields_ = [("data", c_void_p), ("nbytes", ctypes.c_int64), ("index", c_void_p)]
+
 
 _lock = threading.Lock()
 _lib = None

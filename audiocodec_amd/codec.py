@@ -330,11 +330,36 @@ class AudioCodec:
         data, index = self.psy.pack(codes, sf)
         return data, index, offset
 
+    def decode_packed_launches(self, channels_n=2, device=None):
+        """Launches :meth:`decode_packed` takes for ``channels_n`` channels (``ac_decode_packed_launches``): 1 = the
+        synthesis reads the bitstream itself (filters_n = 1024, bark_bands_n = 64, mono / stereo), else 1 +
+        :meth:`decode_quantized_launches`: :meth:`PsychoacousticModel.unpack`, then :meth:`decode_quantized`
+        (everywhere while ``AC_DECODE_PACKED_NOFUSE=1`` is set: read per call)."""
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return int(self._lib.ac_decode_packed_launches(self.mdct._plan(dev), self.psy._plan(dev), int(channels_n)))
+
     def decode_packed(self, data, index, pcm16=False):
-        """:meth:`PsychoacousticModel.unpack`, then :meth:`decode_quantized`: data uint8 [nbytes], index int64
-        [B, K', C] -> x [B, (K'+1)*N, C] (``torch.int16`` with ``pcm16=True``); bit-equal to ``decode_quantized`` on the
-        codes that were packed.  float32 only."""
+        """data uint8 [nbytes], index int64 [B, K', C] -> x [B, (K'+1)*N, C] (``torch.int16`` with ``pcm16=True``);
+        bit-equal to ``decode_quantized(*psy.unpack(data, index), pcm16)``, that is to ``decode_quantized`` on the codes
+        that were packed.  One launch that reads the bitstream in the synthesis -- no codes or scale factors are
+        allocated -- where :meth:`decode_packed_launches` is 1; :meth:`PsychoacousticModel.unpack`, then
+        :meth:`decode_quantized` elsewhere.  ``index`` may hold any row starts (a slice of frames, channels in another
+        order, a strided view), and damaged rows read as :meth:`PsychoacousticModel.unpack` reads them.  float32 only."""
         _host.require_float32(self.compute_dtype, "decode_packed")
+        if (isinstance(data, torch.Tensor) and isinstance(index, torch.Tensor) and data.is_cuda and index.dim() == 3
+                and index.shape[1] >= 1 and self.decode_packed_launches(index.shape[2], data.device) == 1):
+            data = self.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
+            index = self.psy._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
+            B, Kp, C = index.shape
+            dev = data.device
+            x = torch.empty((B, (Kp + 1) * self.filters_n, C), dtype=torch.int16 if pcm16 else torch.float32, device=dev)
+            rows = _lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr())
+            with _host.on_device(dev):
+                _lib.check(self._lib.ac_decode_quantized(
+                    self.mdct._plan(dev), self.psy._plan(dev), ctypes.addressof(rows), None,
+                    None if pcm16 else _host.ptr(x), _host.ptr(x) if pcm16 else None, None, B, Kp, C,
+                    _host.stream_ptr(dev)))
+            return x
         codes, sf = self.psy.unpack(data, index)
         return self.decode_quantized(codes, sf, pcm16)
 

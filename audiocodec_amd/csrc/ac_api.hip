@@ -1145,6 +1145,19 @@ int ac_decode_quantized_launches(const ac_mdct_plan* mdct, const ac_psy_plan* ps
   return decode_quantized_fuses(mdct, C) ? 1 : 2;
 }
 
+// whether packed rows are decoded in one launch (k_inv_fast_p); AC_DECODE_PACKED_NOFUSE=1 sends every configuration down
+// ac_unpack + ac_decode_quantized (A/B measurements: read per call, so that one process can time both forms)
+static bool decode_packed_fuses(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C) {
+  const char* e = getenv("AC_DECODE_PACKED_NOFUSE");
+  if (e && atoi(e) == 1) return false;
+  return decode_quantized_fuses(mdct, C) && fast_inv_packed_serves(mdct, psy, C);
+}
+
+int ac_decode_packed_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C) {
+  if (!mdct || !psy || mdct->N != psy->N || mdct->device != psy->device || C < 1) return 0;
+  return decode_packed_fuses(mdct, psy, C) ? 1 : 1 + ac_decode_quantized_launches(mdct, psy, C);
+}
+
 int ac_decode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, float* x,
                         int16_t* pcm16, float* scratch, int B, int Kp, int C, void* stream) {
   AC_REQUIRE(mdct != nullptr && psy != nullptr, "plan is NULL");
@@ -1154,8 +1167,26 @@ int ac_decode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const 
   if (st) return st;
   AC_REQUIRE((x != nullptr) != (pcm16 != nullptr), "exactly one of x (float32) and pcm16 must be given");
   if (B == 0 || C == 0) return AC_OK;
-  AC_REQUIRE(Kp == 0 || (codes != nullptr && sf != nullptr), "NULL tensor pointer");
   void* out = x ? static_cast<void*>(x) : static_cast<void*>(pcm16);
+  if (sf == nullptr && codes != nullptr) {   // codes addresses one ac_packed_rows: the rows of the packed bitstream
+    const ac_packed_rows rows = *reinterpret_cast<const ac_packed_rows*>(codes);
+    if (!decode_packed_fuses(mdct, psy, C)) {
+      set_error("sf is NULL (packed rows), and no kernel decodes packed rows in one launch for filters_n = %d, bark_bands_n "
+                "= %d, %d channels here (ac_decode_packed_launches() != 1): unpack them with ac_unpack and pass codes and sf",
+                mdct->N, psy->M, C);
+      return AC_EUNSUPPORTED;
+    }
+    AC_REQUIRE(rows.nbytes >= 0, "negative nbytes (%lld)", (long long)rows.nbytes);
+    AC_REQUIRE(Kp == 0 || rows.index != nullptr, "NULL tensor pointer");
+    AC_REQUIRE(rows.data != nullptr || rows.nbytes == 0, "data is NULL");
+    AC_REQUIRE_ALIGNED(rows.data, rows.index, out);
+    DeviceGuard guard(mdct->device);
+    if (Kp >= 1)
+      return launch_inv_fast_packed(mdct, psy, rows.data, rows.nbytes, rows.index, out, pcm16 != nullptr, B, Kp, C,
+                                    (hipStream_t)stream);
+    return mdct_inverse(mdct, nullptr, out, pcm16 != nullptr, B, Kp, C, stream);
+  }
+  AC_REQUIRE(Kp == 0 || (codes != nullptr && sf != nullptr), "NULL tensor pointer");
   AC_REQUIRE_ALIGNED(codes, sf, out);
   DeviceGuard guard(mdct->device);
   hipStream_t s = (hipStream_t)stream;

@@ -1,11 +1,13 @@
 // Synthesis of the wave-level kernels for filters_n = 1024 / 2048 (ac_fast_dev.h): the body shared by k_inv_fast,
-// k_inv_fast_q (instantiated in ac_fast_inv.hip) and k_duplex_fast (ac_fast_fwd.hip), and prep_inv_fast(), the host
-// code that fills its arguments for both objects (InvArgs has internal linkage, so no function can pass it between them).
+// k_inv_fast_q (instantiated in ac_fast_inv.hip), k_inv_fast_p (ac_fast_inv_p.hip) and k_duplex_fast (ac_fast_fwd.hip), and
+// prep_inv_fast(), the host code that fills its arguments for these objects (InvArgs has internal linkage, so no function
+// can pass it between them).
 #pragma once
 #include <cstdlib>
 
 #include "ac_fast.h"
 #include "ac_fast_dev.h"
+#include "ac_fast_inv_p_dev.h"
 
 namespace ac {
 namespace {
@@ -67,10 +69,12 @@ struct QuantRows {
 
 template <int R, int CMODE, int NW, int IOF = 0>
 __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const int bid, const int nblocks,
-                                              const QuantRows* qr = nullptr) {
+                                              const QuantRows* qr = nullptr, const PackedRows* pr = nullptr) {
   using G = Geo<R>;
   constexpr bool QUANT = IOF >= 3;
-  constexpr int OIOF = QUANT ? IOF - 3 : IOF;   // format of the PCM side
+  constexpr bool PACKED = IOF >= 5;   // (IOF 5 / 6) the quantised spectra come as rows of the packed bitstream
+  static_assert(!PACKED || R == 8, "packed rows: filters_n = 1024");
+  constexpr int OIOF = PACKED ? IOF - 5 : QUANT ? IOF - 3 : IOF;   // format of the PCM side
   constexpr int FH = G::FH;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   load_tables<NW, WAVE_LDS, G::I_LDS, 0>(lds, a.tab + G::I_TOTAL, nullptr);
@@ -98,17 +102,23 @@ __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const
   const spec_t* X0 = reinterpret_cast<const spec_t*>(a.X) + row_off(pq.b0, a.Kp, 0, blk, pq.c0);   // frame 0 of the two signals
   const spec_t* X1 = reinterpret_cast<const spec_t*>(a.X) + row_off(pq.b1, a.Kp, 0, blk, pq.c1);
   // what a loaded frame is held as until it is transformed: float32 rows, or the raw codes and scale factors (QUANT)
-  using hold_t = typename std::conditional<QUANT, QGran, v4f>::type;
+  using hold_t = typename std::conditional<PACKED, PGran, typename std::conditional<QUANT, QGran, v4f>::type>::type;
   // (QUANT) the bands of the lane's bin pairs, the same in every frame: held in registers by the 1024-filter kernel; the
   // 2048-filter one (no registers to spare, and no frame in flight ahead) reads them with the frame
   constexpr bool BW_REGS = QUANT && R == 8;
   uint32_t bw[BW_REGS ? R : 1];
-  if constexpr (BW_REGS) {
+  if constexpr (PACKED) {
+    load_bw_p<R>(*pr, lane, bw);
+  } else if constexpr (BW_REGS) {
 #pragma unroll
     for (int i = 0; i < R; ++i) bw[i] = qr->band32[64 * i + lane];
   }
+  // (PACKED) the wave's band records of the rows of frames n0-1 .. n1-1, filled by parse_strip_p below
+  uint32_t* rec = reinterpret_cast<uint32_t*>(lds + NW * WAVE_LDS + G::TAB_LDS + (PACKED ? wave * P_REC_BYTES : 0));
   auto load_frame = [&](int n, const spec_t* r0, const spec_t* r1, hold_t (&dst)[R]) {
-    if constexpr (QUANT) {
+    if constexpr (PACKED) {
+      load_row_p<R>(*pr, rec, n - (n0 - 1), bw, has1, dst);
+    } else if constexpr (QUANT) {
       const size_t mc = (size_t)qr->M * C;
       const int8_t* sf0 = qr->sf + row_off(pq.b0, a.Kp, n, mc, pq.c0);
       const int8_t* sf1 = qr->sf + row_off(pq.b1, a.Kp, n, mc, pq.c1);
@@ -158,6 +168,12 @@ __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const
     carry[r] = v2f{0.f, 0.f};
     now0[r] = v2f{0.f, 0.f};
   }
+  if constexpr (PACKED) {
+    // slot 0 is frame n0-1, read only by a wave that transforms it itself
+    if (valid)
+      parse_strip_p(*pr, pq.b0, pq.b1, pq.c0, pq.c1, a.Kp, C, n0 - 1, (left && !deferred) ? 0 : 1, min(n1, a.Kp) - (n0 - 1),
+                    has1, lane, buf, rec);
+  }
   if (valid) {
     hold_t ahead[R];
     if (left && !deferred) {
@@ -166,7 +182,13 @@ __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const
       load_frame(n0 - 1, X0 + (size_t)(n0 - 1) * blk, X1 + (size_t)(n0 - 1) * blk, row);
       if (AHEAD && n0 < a.Kp) load_frame(n0, X0 + (size_t)n0 * blk, X1 + (size_t)n0 * blk, ahead);
       v2f dummy[R];
-      if constexpr (QUANT) {
+      if constexpr (PACKED) {
+        QGran g[R];
+        v4f frm[R];
+        extract_row_p<R>(rec, 0, bw, has1, row, g);
+        dequant_frame<R>(g, frm);
+        idct_frame<R>(frm, buf, tab, p1, lane, dummy, carry);
+      } else if constexpr (QUANT) {
         v4f frm[R];
         dequant_frame<R>(row, frm);
         idct_frame<R>(frm, buf, tab, p1, lane, dummy, carry);
@@ -190,7 +212,13 @@ __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const
       v2f now[R], nxt[R];
       if (n < a.Kp) {
         if (!AHEAD) load_frame(n, X0 + (size_t)n * blk, X1 + (size_t)n * blk, ahead);
-        if constexpr (QUANT) {   // (the frame's loads were issued one frame earlier: the waits land here)
+        if constexpr (PACKED) {
+          QGran g[R];
+          v4f frm[R];
+          extract_row_p<R>(rec, n - (n0 - 1), bw, has1, ahead, g);
+          dequant_frame<R>(g, frm);
+          idct_frame<R>(frm, buf, tab, p1, lane, now, nxt);
+        } else if constexpr (QUANT) {   // (the frame's loads were issued one frame earlier: the waits land here)
           v4f frm[R];
           dequant_frame<R>(ahead, frm);
           idct_frame<R>(frm, buf, tab, p1, lane, now, nxt);
@@ -258,6 +286,15 @@ __global__ __launch_bounds__(NW * 64, 2) void k_inv_fast_q(InvArgs a, QuantRows 
   static_assert(IOF == 3 || IOF == 4, "quantised spectra");
   __shared__ __attribute__((aligned(16))) char lds[NW * WAVE_LDS + Geo<R>::TAB_LDS];
   inv_fast_body<R, CMODE, NW, IOF>(a, lds, (int)blockIdx.x, (int)gridDim.x, &qr);
+}
+
+// the same synthesis reading rows of the packed bitstream (IOF 5 / 6, filters_n = 1024 with 64 bands, mono / stereo): the band
+// records of a wave's strip live behind the tables.  Strips of at most P_SLOTS - 1 blocks (launch_inv_fast_packed sees to it)
+template <int R, int CMODE, int NW, int IOF>
+__global__ __launch_bounds__(NW * 64, 2) void k_inv_fast_p(InvArgs a, PackedRows pr) {
+  static_assert(R == 8 && (IOF == 5 || IOF == 6), "packed rows");
+  __shared__ __attribute__((aligned(16))) char lds[NW * WAVE_LDS + Geo<R>::TAB_LDS + NW * P_REC_BYTES];
+  inv_fast_body<R, CMODE, NW, IOF>(a, lds, (int)blockIdx.x, (int)gridDim.x, nullptr, &pr);
 }
 
 // arguments and grid of the one-frame-per-wave synthesis kernels (filters_n 1024 / 2048)

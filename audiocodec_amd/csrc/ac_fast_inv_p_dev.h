@@ -1,0 +1,211 @@
+// The third spectrum source of the wave-level synthesis (inv_fast_body, ac_fast_inv_dev.h): rows of the packed bitstream
+// (ac_pack.hip), read where k_inv_fast_q reads codes and scale factors.  filters_n = 1024 with
+// bark_bands_n = 64 only: a row has as many bands as a wave has lanes.
+//
+//   parse_strip_p  once per strip, before the frame loop: the header words (5M width bits + 8M scale-factor bits = 26 words)
+//                  of every row the strip reads -- at most P_SLOTS frames x 2 signals -- are loaded in one round trip into
+//                  the wave's FFT buffer; lane j reads band j's width, a wave-wide scan of (stored bands << 16 | code bits)
+//                  gives its sf field and the bit position of its codes, and the lane leaves the band's record
+//                  (first code bit << 13 | sf byte << 5 | width) in the wave's record region of LDS.
+//   load_row_p     in place of load_row_q, one frame ahead: bins 2q and 2q+1 of a granule are adjacent fields of the row
+//                  (a band's codes follow the band before it), so one two-dword window at the first field's bit covers both.
+//   extract_row_p  where the frame is dequantised: shift, mask, un-zigzag -> the QGran load_row_q would have loaded from
+//                  ac_unpack's codes and sf.
+//
+// Row semantics are ac_unpack's (k_unpack): a width of 17 .. 30 reads as 31; width 31 gives codes 0 and sf -128, width 0 sf 0;
+// bits outside [0, nbytes) read as 0 and are never loaded; a row start may be any int64.  A row whose words all lie inside
+// data at a 4-byte phase takes plain dword loads; any other row (the last one of data, damaged input) takes p_load_word.
+#pragma once
+#include "ac_fast_dev.h"
+
+namespace ac {
+namespace {
+
+struct PackedRows {
+  const uint8_t* data;
+  int64_t nbytes;
+  const int64_t* index;    // [B, Kp, C]
+  const uint32_t* band32;  // [N/2]: bands of bins 2q | 2q+1 << 16
+  const int32_t* off;      // [M + 1]: first bin of every band
+};
+
+constexpr int P_M = 64;                       // bands of a row = lanes of a wave
+constexpr int P_SLOTS = 4;                    // frames a strip reads: at most 3 output blocks and the frame before them
+constexpr int P_ROWS = 2 * P_SLOTS;           // row r = 2 slot + signal
+constexpr int P_HDR_WORDS = (13 * P_M) / 32;  // words that can hold widths and scale factors
+constexpr int P_REC_BYTES = P_ROWS * (P_M * 4 + 16);   // per wave: the records [P_ROWS][64], then (start lo, hi, fast, -) per row
+
+struct PGran {   // the two-dword window of a granule, per signal
+  uint32_t lo0, hi0, lo1, hi1;
+};
+
+__device__ __forceinline__ bool p_stores(uint32_t w) { return w - 1u < 16u; }   // widths 1 .. 16 store an sf and codes
+__device__ __forceinline__ int16_t p_unzigzag(uint32_t z) { return (int16_t)((z >> 1) ^ (0u - (z & 1u))); }
+// the little-endian word at byte a of data; bytes outside [0, nbytes) read as 0 (never loaded) -- as in ac_pack.hip
+__device__ __forceinline__ uint32_t p_load_word(const uint8_t* __restrict__ data, int64_t nbytes, int64_t a) {
+  if (a >= 0 && a + 4 <= nbytes && (a & 3) == 0) return *reinterpret_cast<const uint32_t*>(data + a);
+  uint32_t r = 0;
+  for (int k = 0; k < 4; ++k) {
+    const int64_t e = a + k;
+    if (e >= 0 && e < nbytes) r |= (uint32_t)data[e] << (8 * k);
+  }
+  return r;
+}
+// the w-bit field at bit p of the staged header st (w <= 16)
+__device__ __forceinline__ uint32_t p_get_bits(const uint32_t* st, uint32_t p, uint32_t w) {
+  const uint32_t q = p >> 5, sh = p & 31;
+  const uint32_t lo = st[q], hi = sh + w > 32 ? st[q + 1] : 0u;
+  return __builtin_amdgcn_alignbit(hi, lo, sh) & ((1u << w) - 1u);
+}
+// first bit of the field of the bin d bins into the band of record rec (a band that stores nothing takes no bits)
+__device__ __forceinline__ uint32_t p_pos(uint32_t rec, uint32_t d) {
+  const uint32_t w = rec & 31u;
+  return (rec >> 13) + (p_stores(w) ? w * d : 0u);
+}
+
+// The records of the rows of frames base + slot, slot in [slot_lo, slot_hi), of the wave's two signals.  buf: the wave's FFT
+// buffer (free before the frame loop); rec: the wave's record region.
+__device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0, long long b1, int c0, int c1, int Kp, int C,
+                                              int base, int slot_lo, int slot_hi, bool has1, int lane, char* buf,
+                                              uint32_t* rec) {
+  uint32_t* st = reinterpret_cast<uint32_t*>(buf);   // [P_ROWS][P_HDR_WORDS]
+  uint32_t* info = rec + P_ROWS * P_M;
+  const int sig = lane >> 5, k = lane & 31;          // half a wave per row: slot t, signal sig
+#pragma unroll
+  for (int t = 0; t < P_SLOTS; ++t) {
+    if (t >= slot_lo && t < slot_hi && (sig == 0 || has1) && k < P_HDR_WORDS) {
+      const int r = 2 * t + sig;
+      const long long b = sig ? b1 : b0;
+      const int c = sig ? c1 : c0;
+      int64_t a = pr.index[((size_t)b * (size_t)Kp + (size_t)(base + t)) * (size_t)C + (size_t)c];
+      // a row start beyond the buffer reads nothing; clamping it keeps start + 4 k from overflowing
+      a = a > pr.nbytes ? pr.nbytes : (a < -(1ll << 40) ? -(1ll << 40) : a);
+      st[r * P_HDR_WORDS + k] = p_load_word(pr.data, pr.nbytes, a + 4ll * k);
+      if (k == 0) {
+        info[4 * r] = (uint32_t)(uint64_t)a;
+        info[4 * r + 1] = (uint32_t)((uint64_t)a >> 32);
+      }
+    }
+  }
+  wave_sync();
+  const uint32_t len = (uint32_t)(pr.off[lane + 1] - pr.off[lane]);   // bins of the lane's band
+#pragma unroll 1
+  for (int r = 2 * slot_lo; r < 2 * slot_hi; ++r) {
+    if ((r & 1) && !has1) continue;
+    const uint32_t* sr = st + r * P_HDR_WORDS;
+    uint32_t w = p_get_bits(sr, 5u * lane, 5);
+    if (w > 16) w = 31;   // 17 .. 30: damaged, read as a non-finite band
+    const uint32_t v = p_stores(w) ? (1u << 16) | (w * len) : 0u;   // (code bits of a row <= 16 N = 2^14)
+    uint32_t incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d *= 2) {
+      const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
+      if (lane >= d) incl += up;
+    }
+    const uint32_t ex = incl - v;
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    const uint32_t cbase = 5u * P_M + 8u * (total >> 16);   // first code bit
+    uint32_t sfb = 0;
+    if (w == 31) sfb = 0x80u;
+    else if (p_stores(w)) sfb = p_get_bits(sr, 5u * P_M + 8u * (ex >> 16), 8);
+    rec[r * P_M + lane] = ((cbase + (ex & 0xffffu)) << 13) | (sfb << 5) | w;
+    if (lane == 0) {
+      // plain loads where every word a window of this row can touch -- its ceil(bits / 32) words and two more -- is in data
+      const int64_t a = (int64_t)((uint64_t)info[4 * r] | ((uint64_t)info[4 * r + 1] << 32));
+      const int64_t nw = (int64_t)((cbase + (total & 0xffffu) + 31u) >> 5);
+      info[4 * r + 2] = (a >= 0 && (a & 3) == 0 && a + 4 * (nw + 2) <= pr.nbytes) ? 1u : 0u;
+    }
+  }
+  wave_sync();
+}
+
+// bw[i]: band of bin 2q | band of bin 2q+1 << 6 | (2q - first bin of its band) << 12, q = 64 i + lane
+template <int R>
+__device__ __forceinline__ void load_bw_p(const PackedRows& pr, int lane, uint32_t (&bw)[R]) {
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const int q = 64 * i + lane;
+    const uint32_t b = pr.band32[q], j0 = b & 0xffffu, j1 = b >> 16;
+    bw[i] = j0 | (j1 << 6) | ((uint32_t)(2 * q - pr.off[j0]) << 12);
+  }
+}
+
+// the window loads of row r: only loads, LDS reads and address arithmetic
+template <int R>
+__device__ __forceinline__ void load_sig_p(const PackedRows& pr, const uint32_t* rec, int r, const uint32_t (&bw)[R],
+                                           uint32_t (&lo)[R], uint32_t (&hi)[R]) {
+  const uint32_t* info = rec + P_ROWS * P_M;
+  const uint32_t* rr = rec + r * P_M;
+  const uint32_t a_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)info[4 * r]);
+  const uint32_t a_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)info[4 * r + 1]);
+  const int64_t a = (int64_t)((uint64_t)a_lo | ((uint64_t)a_hi << 32));
+  if (__builtin_amdgcn_readfirstlane((int)info[4 * r + 2])) {
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(pr.data + a);
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const uint32_t wi = p_pos(rr[bw[i] & 63u], bw[i] >> 12) >> 5;
+      lo[i] = row[wi];
+      hi[i] = row[wi + 1];
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const uint32_t wi = p_pos(rr[bw[i] & 63u], bw[i] >> 12) >> 5;
+      lo[i] = p_load_word(pr.data, pr.nbytes, a + 4ll * wi);
+      hi[i] = p_load_word(pr.data, pr.nbytes, a + 4ll * wi + 4);
+    }
+  }
+}
+// issues the window loads of the frame in `slot`, one frame ahead as load_row_q
+template <int R>
+__device__ __forceinline__ void load_row_p(const PackedRows& pr, const uint32_t* rec, int slot, const uint32_t (&bw)[R],
+                                           bool has1, PGran (&g)[R]) {
+  uint32_t lo[R], hi[R];
+  load_sig_p<R>(pr, rec, 2 * slot, bw, lo, hi);
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    g[i].lo0 = lo[i];
+    g[i].hi0 = hi[i];
+    g[i].lo1 = g[i].hi1 = 0u;
+  }
+  if (has1) {
+    load_sig_p<R>(pr, rec, 2 * slot + 1, bw, lo, hi);
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      g[i].lo1 = lo[i];
+      g[i].hi1 = hi[i];
+    }
+  }
+}
+
+// the two fields of a window -> codes of bins 2q, 2q+1 (low, high half) and their scale-factor bytes (bits 0-7, 16-23)
+__device__ __forceinline__ void extract_sig_p(const uint32_t* rr, uint32_t bwi, uint32_t lo, uint32_t hi, uint32_t& codes,
+                                              uint32_t& sfs) {
+  const uint32_t r0 = rr[bwi & 63u], r1 = rr[(bwi >> 6) & 63u];
+  const uint32_t w0 = r0 & 31u, w1 = r1 & 31u;
+  const uint32_t e0 = p_stores(w0) ? w0 : 0u, e1 = p_stores(w1) ? w1 : 0u;
+  const uint32_t sh = p_pos(r0, bwi >> 12) & 31u;
+  const uint64_t win = (uint64_t)lo | ((uint64_t)hi << 32);
+  // bin 2q+1 follows bin 2q: in the same band, or first of the next one that holds bins
+  const uint32_t z0 = (uint32_t)(win >> sh) & ((1u << e0) - 1u);
+  const uint32_t z1 = (uint32_t)(win >> (sh + e0)) & ((1u << e1) - 1u);
+  codes = (uint32_t)(uint16_t)p_unzigzag(z0) | ((uint32_t)(uint16_t)p_unzigzag(z1) << 16);
+  sfs = ((r0 >> 5) & 0xffu) | (((r1 >> 5) & 0xffu) << 16);
+}
+// the loaded windows -> the raw codes and scale-factor bytes of the frame, in load_row_q's order
+template <int R>
+__device__ __forceinline__ void extract_row_p(const uint32_t* rec, int slot, const uint32_t (&bw)[R], bool has1,
+                                              const PGran (&g)[R], QGran (&out)[R]) {
+  const uint32_t* rr0 = rec + 2 * slot * P_M;
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    uint32_t c0, f0, c1 = 0u, f1 = 0u;
+    extract_sig_p(rr0, bw[i], g[i].lo0, g[i].hi0, c0, f0);
+    if (has1) extract_sig_p(rr0 + P_M, bw[i], g[i].lo1, g[i].hi1, c1, f1);
+    out[i].code = s4{(short)(c0 & 0xffffu), (short)(c1 & 0xffffu), (short)(c0 >> 16), (short)(c1 >> 16)};
+    out[i].sfw = f0 | (f1 << 8);
+  }
+}
+
+}  // namespace
+}  // namespace ac

@@ -279,6 +279,11 @@ int launch_inv_fast(const ac_mdct_plan* p, const float* X, void* x, int iof, con
 bool fast_inv_quant_serves(const ac_mdct_plan* p, int C);
 int launch_inv_fast_quant(const ac_mdct_plan* p, const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, void* x,
                           bool pcm16, int B, int Kp, int C, hipStream_t s);
+// ... and from rows of the packed bitstream (k_inv_fast_p, ac_fast_inv_p.hip): filters_n = 1024 with 64 bands, mono / stereo;
+// data [nbytes], index [B,Kp,C]; bit-equal to launch_inv_fast_quant on launch_unpack's output, damaged rows included
+bool fast_inv_packed_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);
+int launch_inv_fast_packed(const ac_mdct_plan* p, const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes,
+                           const int64_t* index, void* x, bool pcm16, int B, int Kp, int C, hipStream_t s);
 int launch_psy_fast(const ac_psy_plan* p, const float* X, const float* t_in, float* t_out, float* thr, float drown,
                     int B, int F, int C, hipStream_t s, int iof = 0);
 // streaming duplex: the analysis of a chunk of k_fwd blocks (psy: with the fused masking model) and the synthesis of a

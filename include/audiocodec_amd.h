@@ -46,7 +46,8 @@ extern "C" {
 
 #define AC_VERSION 171 /* 0.1.8 + the quantiser (int16 codes, int8 per-band scale factors: ac_quantize, ac_dequantize,
                           * ac_decode_quantized[_launches], ac_psy_scale_bands_host), its packed bitstream (ac_pack_index,
-                          * ac_pack, ac_unpack, ac_pack_scratch_bytes) and its rate control (ac_quantize_budget, per clip
+                          * ac_pack, ac_unpack, ac_pack_scratch_bytes; decoded in one launch: ac_packed_rows,
+                          * ac_decode_packed_launches) and its rate control (ac_quantize_budget, per clip
                           * ac_quantize_clip_budget, ac_clip_budget_scratch_bytes; in the plan: ac_psy_plan_with_row_budget,
                           * ac_psy_plan_row_budget); additions only, so the number stays.
                           * 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
@@ -269,7 +270,20 @@ AC_API int ac_encode_fused_pcm16(const ac_mdct_plan* mdct, const ac_psy_plan* ps
  *   dequantised spectra, codes [B,Kp,N,C] -> x [B,(Kp+1)*N,C]; bit-equal to ac_dequantize followed by the inverse.
  *   scratch [B,Kp,N,C] float32 receives the dequantised spectra where ac_decode_quantized_launches returns 2 and may be
  *   NULL where it returns 1 (filters_n 1024 / 2048 on the wave-level kernels, mono / stereo: one launch that dequantises in
- *   its loads).  mdct and psy must share filters_n and device. */
+ *   its loads).  mdct and psy must share filters_n and device.
+ *   With sf == NULL, codes addresses one ac_packed_rows (a host struct of device pointers, read during the call): the rows of
+ *   the packed bitstream (below) at index [B,Kp,C], contiguous, are decoded in ONE launch that reads the bitstream where the
+ *   synthesis above reads codes and sf -- bit-equal to ac_unpack followed by ac_decode_quantized, with ac_unpack's reading
+ *   of damaged rows and of row starts outside data.  Served where ac_decode_packed_launches returns 1; AC_EUNSUPPORTED
+ *   elsewhere (unpack the rows with ac_unpack and pass codes and sf).  scratch is not used.  codes == NULL stays an error.
+ * ac_decode_packed_launches: 1 where that form is served (float32 plans on the wave-level kernels, filters_n = 1024,
+ *   bark_bands_n = 64, mono / stereo), else 1 + ac_decode_quantized_launches: ac_unpack, then ac_decode_quantized (also
+ *   everywhere while AC_DECODE_PACKED_NOFUSE=1 is set in the environment: read per call).  0 for NULL or mismatched plans. */
+typedef struct ac_packed_rows {
+  const uint8_t* data;  /* [nbytes] the bitstream (device) */
+  int64_t nbytes;
+  const int64_t* index; /* [B,Kp,C] byte offset of every row in data (device); any int64 */
+} ac_packed_rows;
 AC_API int ac_quantize(const ac_psy_plan* psy, const float* X, const float* thr, int16_t* codes, int8_t* sf, int B, int F,
                        int C, void* stream);
 AC_API int ac_dequantize(const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, float* X, int B, int F, int C,
@@ -277,6 +291,7 @@ AC_API int ac_dequantize(const ac_psy_plan* psy, const int16_t* codes, const int
 AC_API int ac_decode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf,
                                float* x, int16_t* pcm16, float* scratch, int B, int Kp, int C, void* stream);
 AC_API int ac_decode_quantized_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C);
+AC_API int ac_decode_packed_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C);
 
 /* Packed bitstream of quantised spectra (extension).  A row is one (b, f, c) of codes [B,F,N,C] and
  * sf [B,F,M,C]; bit p of a row is bit p % 32 of its little-endian 32-bit word p / 32; fields are written LSB first:

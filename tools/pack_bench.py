@@ -1,8 +1,11 @@
 """Packed bitstream at the bench workload (B = 256 clips, stereo, K = 468 blocks, filters_n 1024, uniform input in [-1, 1]):
 pack_index + pack (the C ABI on caller-owned buffers, and psy.pack() with its read of the byte count), unpack, and
 decode_packed against decode_quantized, timed with HIP events.  Algorithmic bytes: codes + sf + packed bytes, each once (pack_index alone:
-codes + sf + the index; a decoder: its input + the PCM it writes).
-python tools/pack_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5]"""
+codes + sf + the index; a decoder: its input + the PCM it writes).  Then decode_packed in its two forms -- the one launch of
+k_inv_fast_p and unpack + decode_quantized (AC_DECODE_PACKED_NOFUSE=1, read per call) -- and decode_quantized, float32 and
+16-bit PCM out, alternating over --rounds rounds of --round-steps calls with the spread of the rounds; the two forms'
+outputs are compared bit for bit first.
+python tools/pack_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7] [--round-steps 30]"""
 import argparse
 import ctypes
 import os
@@ -36,6 +39,8 @@ def main():
     ap.add_argument("--channels", type=int, default=2)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--round-steps", type=int, default=30)
     a = ap.parse_args()
     B, K, N, C = a.clips, a.blocks, a.filters, a.channels
     codec = audiocodec_amd.AudioCodec(48000, N)
@@ -50,8 +55,10 @@ def main():
     samples = B * F * N * C
     code_b, sf_b, pk_b, ix_b = codes.numel() * 2, sf.numel(), data.numel(), rows * 8
     pcm_f32 = B * (F + 1) * N * C * 4
-    print("pack_bench: B=%d K=%d N=%d C=%d M=%d  rows=%d  decode_quantized launches=%d  %s"
-          % (B, K, N, C, M, rows, codec.decode_quantized_launches(C), torch.cuda.get_device_name()))
+    pcm_i16 = pcm_f32 // 2
+    print("pack_bench: B=%d K=%d N=%d C=%d M=%d  rows=%d  decode_quantized launches=%d  decode_packed launches=%d  %s"
+          % (B, K, N, C, M, rows, codec.decode_quantized_launches(C), codec.decode_packed_launches(C),
+             torch.cuda.get_device_name()))
     print("size: codes+sf %.1f MB -> packed %.1f MB (%.2fx smaller)  bits/sample %.3f (%.3f with the 8-byte index per row)"
           % ((code_b + sf_b) / 1e6, pk_b / 1e6, (code_b + sf_b) / pk_b, 8.0 * pk_b / samples, 8.0 * (pk_b + ix_b) / samples))
     print("widest code: %d" % int(codes.abs().max()))
@@ -79,6 +86,19 @@ def main():
     def unpack_into():
         _lib.check(lib.ac_unpack(plan, p(data), pk_b, p(index), p(out_c), p(out_s), B, F, C, s))
 
+    def composition(pcm16):
+        os.environ["AC_DECODE_PACKED_NOFUSE"] = "1"   # (read per call)
+        try:
+            return codec.decode_packed(data, index, pcm16=pcm16)
+        finally:
+            del os.environ["AC_DECODE_PACKED_NOFUSE"]
+
+    for pcm16 in (False, True):   # the two forms give the same bits at the timed size
+        one, two = codec.decode_packed(data, index, pcm16=pcm16), composition(pcm16)
+        assert one.dtype == two.dtype and torch.equal(one.view(torch.int16), two.view(torch.int16)), "the two forms differ"
+        del one, two
+    print("decode_packed: the one launch and unpack + decode_quantized agree bit for bit (float32 and 16-bit PCM)")
+
     rows_t = [
         ("pack_index", pack_index, code_b + sf_b + ix_b),
         ("pack_index + pack", pack_both, code_b + sf_b + pk_b),
@@ -94,6 +114,32 @@ def main():
         res[name] = ms
         print("%-24s %8.3f ms  %6.3f GB  %6.2f TB/s" % (name, ms, nbytes / 1e9, nbytes / ms / 1e9))
     print("decode_packed / decode_quantized = %.3f" % (res["decode_packed f32"] / res["decode_quantized f32"]))
+    if a.rounds < 1:
+        return
+    # the two forms of decode_packed and decode_quantized, alternating in this process
+    forms = [
+        ("decode_packed f32 (%d launch)" % codec.decode_packed_launches(C), lambda: codec.decode_packed(data, index),
+         pk_b + ix_b + pcm_f32),
+        ("unpack + decode_quantized f32", lambda: composition(False), pk_b + ix_b + 2 * (code_b + sf_b) + pcm_f32),
+        ("decode_quantized f32", lambda: codec.decode_quantized(codes, sf), code_b + sf_b + pcm_f32),
+        ("decode_packed pcm16 (%d launch)" % codec.decode_packed_launches(C),
+         lambda: codec.decode_packed(data, index, pcm16=True), pk_b + ix_b + pcm_i16),
+        ("unpack + decode_quantized pcm16", lambda: composition(True), pk_b + ix_b + 2 * (code_b + sf_b) + pcm_i16),
+        ("decode_quantized pcm16", lambda: codec.decode_quantized(codes, sf, pcm16=True), code_b + sf_b + pcm_i16),
+    ]
+    runs = dict((n, []) for n, _, _ in forms)
+    for _ in range(a.rounds):
+        for n, fn, _ in forms:
+            runs[n].append(timed(fn, a.round_steps, 1))
+    med = {}
+    for n, _, nbytes in forms:
+        v = sorted(runs[n])
+        med[n] = v[len(v) // 2]
+        print("%-34s median %.3f ms  min %.3f  max %.3f  %6.3f GB  %5.2f TB/s  (%d alternating rounds of %d)"
+              % (n, med[n], v[0], v[-1], nbytes / 1e9, nbytes / med[n] / 1e9, len(v), a.round_steps))
+    for k in (0, 3):
+        print("%s: one launch / composition = %.3f   one launch / decode_quantized = %.3f"
+              % ("pcm16" if k else "f32", med[forms[k][0]] / med[forms[k + 1][0]], med[forms[k][0]] / med[forms[k + 2][0]]))
 
 
 if __name__ == "__main__":
