@@ -302,6 +302,75 @@ class AudioCodec:
         data, index = self.psy.pack(codes, sf)
         return data, index, offset
 
+    # ---- fixed-stride packed rows at a bitrate (extension; DESIGN.md section 8b, "packed rows") ------------------
+    @property
+    def row_bytes(self):
+        """Bytes of a row's slot in :meth:`encode_packed_rows`' data: ceil(row_bits / 32) * 4; None without a row budget."""
+        return None if self.row_bits is None else (self.row_bits + 31) // 32 * 4
+
+    def encode_packed_rows_launches(self, channels_n=2, device=None):
+        """Library launches :meth:`encode_packed_rows` takes for float32 PCM of ``channels_n`` channels
+        (``ac_encode_packed_launches``): 1 = the fused encode packs the frame's rows itself (where
+        :meth:`encode_quantized_launches` is 1, bark_bands_n = 64 and the budget is at most ``_lib.AC_PACK_ROWS_MAX_BITS``),
+        else :meth:`encode_launches` + 2: the encode, the budgeted quantiser and the packer (everywhere while
+        ``AC_ENCODE_PACKED_NOFUSE=1`` is set: read per call).  0 on a codec without a row budget."""
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return int(self._lib.ac_encode_packed_launches(self.mdct._plan(dev), self.psy._plan(dev), int(channels_n)))
+
+    def encode_packed_rows(self, x, drown=0.0):
+        """On a codec made by :meth:`with_bitrate` / :meth:`with_row_budget`: x [B, K*N, C] -> (data uint8
+        [B*(K+1)*C*row_bytes], index int64 [B, K+1, C], fits bool [B, K+1, C]) -- every row in a slot of :attr:`row_bytes`
+        bytes, ``index[b, f, c] = ((b*(K+1) + f)*C + c) * row_bytes``.  A slot holds the bytes
+        :meth:`PsychoacousticModel.pack` writes for the row's codes and scale factors of :meth:`encode_quantized`, then zero
+        bytes; a row longer than its slot (offset 254 reached with the budget unmet) is stored as the marked row -- every
+        width 31, ``fits`` False -- and decodes as bands the quantiser could not represent.  :meth:`decode_packed` and
+        :meth:`PsychoacousticModel.unpack` read ``(data, index)`` as they are.  One launch where
+        :meth:`encode_packed_rows_launches` is 1, else the composition of the encode, ``quantize_to_budget`` and the packer:
+        the same bytes.  The size of ``data`` is known before the call: it never synchronises with the device, only
+        enqueues on the current stream, and can be captured in a graph.  float32 only, not differentiable."""
+        _host.require_float32(self.compute_dtype, "encode_packed_rows")
+        if self.row_bits is None:
+            raise ValueError("encode_packed_rows needs a codec with a row budget: make one with with_bitrate() or "
+                             "with_row_budget()")
+        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+            raise ValueError("x requires a gradient: quantisation is not differentiable -- use encode() and "
+                             "psy.add_noise(), its differentiable stand-in")
+        x = _host.check_device_tensor(x, "x", torch.float32, 3)
+        B, S, C = x.shape
+        N = self.filters_n
+        if S % N != 0:
+            raise ValueError("samples_n (%d) is not a multiple of filters_n (%d)" % (S, N))
+        K = S // N
+        F, dev, rb = K + 1, x.device, self.row_bytes
+        rows = B * F * C
+        index = (torch.arange(rows, dtype=torch.int64, device=dev) * rb).view(B, F, C)
+        if rows == 0:
+            return (torch.empty((0,), dtype=torch.uint8, device=dev), index, torch.empty((B, F, C), dtype=torch.bool, device=dev))
+        mdct, psy = self.mdct._plan(dev), self.psy._plan(dev)
+        if self._lib.ac_encode_packed_launches(mdct, psy, C) == 1:
+            data = torch.empty((rows * rb,), dtype=torch.uint8, device=dev)
+            fits = torch.empty((B, F, C), dtype=torch.bool, device=dev)
+            out = _lib.PackedOut(data.data_ptr(), rb, fits.data_ptr())
+            with _host.on_device(dev):
+                _lib.check(self._lib.ac_encode_fused_ex(mdct, psy, _host.ptr(x), None, None, None, float(drown),
+                                                        _lib.AC_EMIT_PACKED, ctypes.addressof(out), None, 0, B, K, C,
+                                                        _host.stream_ptr(dev)))
+            return data, index, fits
+        # the composition: encode_quantized_budget's codes, scale factors and row lengths (on plain allocations: nothing
+        # here may wait for the device), rows longer than their slot marked, then the packer at the fixed row starts
+        X = torch.empty((B, F, N, C), dtype=torch.float32, device=dev)
+        t = torch.empty((B, F, 1, C), dtype=torch.float32, device=dev)
+        thr = torch.empty_like(X)
+        self.encode_into(x, X, t, thr, drown)
+        codes, sf, _, bits = self.psy.quantize_to_budget(X, thr, self.row_bits, self.psy.row_budget[1])
+        fits = bits <= 8 * rb
+        sf.masked_fill_(~fits.unsqueeze(2), -128)   # width 31 follows whatever the codes are
+        data = torch.zeros((rows * rb,), dtype=torch.uint8, device=dev)
+        with _host.on_device(dev):
+            _lib.check(self._lib.ac_pack(psy, _host.ptr(codes), _host.ptr(sf), _host.ptr(index), _host.ptr(data), B, F, C,
+                                         _host.stream_ptr(dev)))
+        return data, index, fits
+
     # ---- rate control per clip (extension; DESIGN.md section 8d) ------------------------------------------------
     def clip_bits_for_bitrate(self, bits_per_second, frames_n, channels_n):
         """The clip budget of a per-channel bitrate: frames_n * channels_n rows of :meth:`row_bits_for_bitrate` bits each,

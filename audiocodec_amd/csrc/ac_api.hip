@@ -772,10 +772,60 @@ static int encode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, co
   return quantize_of_plan(psy, X, thr, codes, sf, B, K + 1, C, (hipStream_t)stream);
 }
 
+// whether AC_EMIT_PACKED is one launch (k_fwd_fast_qp); AC_ENCODE_PACKED_NOFUSE=1 sends every configuration down the
+// composition (A/B measurements: read per call, so that one process can time both forms)
+static bool encode_packed_fuses(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C) {
+  const char* e = getenv("AC_ENCODE_PACKED_NOFUSE");
+  if (e && atoi(e) == 1) return false;
+  return encode_quantized_fuses(mdct, psy, C) && fast_encode_pack_serves(mdct, psy, C);
+}
+
+int ac_encode_packed_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C) {
+  if (!mdct || !psy || mdct->N != psy->N || mdct->device != psy->device || C < 1 || !psy->row_bits) return 0;
+  return encode_packed_fuses(mdct, psy, C) ? 1 : ac_encode_launches(mdct, psy, C) + 2;
+}
+
+// ac_encode_fused_ex with AC_EMIT_PACKED
+static int encode_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, const float* X, const float* t,
+                              const float* thr, float drown, const ac_packed_out* out, const void* out1, int B, int K, int C,
+                              void* stream) {
+  AC_REQUIRE(mdct != nullptr && psy != nullptr, "plan is NULL");
+  AC_REQUIRE(mdct->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", mdct->N, psy->N);
+  AC_REQUIRE(mdct->device == psy->device, "plans live on different devices");
+  int st = check_dims(B, K, C);
+  if (!st) st = check_quant(psy, B, K + 1, C);
+  if (st) return st;
+  AC_REQUIRE(psy->row_bits != 0, "AC_EMIT_PACKED needs a plan with a row budget (ac_psy_plan_with_row_budget)");
+  AC_REQUIRE(X == nullptr && t == nullptr && thr == nullptr, "AC_EMIT_PACKED writes no X, t or thr: they must be NULL");
+  AC_REQUIRE(out1 == nullptr, "AC_EMIT_PACKED takes one ac_packed_out as out0: out1 must be NULL");
+  AC_REQUIRE(out != nullptr, "AC_EMIT_PACKED without its ac_packed_out");
+  const ac_packed_out po = *out;
+  const int64_t row_bytes = (int64_t)((psy->row_bits + 31) / 32) * 4;
+  AC_REQUIRE(po.row_bytes == row_bytes, "row_bytes (%lld) is not the plan's ceil(%d / 32) * 4 = %lld", (long long)po.row_bytes,
+             psy->row_bits, (long long)row_bytes);
+  if (B == 0 || C == 0) return AC_OK;
+  if (!encode_packed_fuses(mdct, psy, C)) {
+    set_error("AC_EMIT_PACKED: no kernel encodes to packed rows in one launch for filters_n = %d, bark_bands_n = %d, %d "
+              "channels, row budget %d here (ac_encode_packed_launches() != 1): use the composition -- ac_encode_fused, "
+              "ac_quantize_budget, then ac_pack at row starts r * row_bytes into zero-filled data",
+              mdct->N, psy->M, C, psy->row_bits);
+    return AC_EUNSUPPORTED;
+  }
+  AC_REQUIRE(po.data != nullptr && po.fits != nullptr && (x != nullptr || K == 0), "NULL tensor pointer");
+  AC_REQUIRE_ALIGNED(x, po.data);
+  DeviceGuard guard(mdct->device);
+  return launch_fwd_fast_pack_rows(mdct, psy, x, drown, po.data, row_bytes, po.fits, B, K, K + 1, C, (hipStream_t)stream);
+}
+
 int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
                        float drown, int flags, void* noisy_v, void* db_norm_v, uint64_t seed, int B, int K, int C,
                        void* stream) {
-  AC_REQUIRE((flags & ~(AC_EMIT_NOISY | AC_EMIT_DB_NORM | AC_EMIT_CODES)) == 0, "unknown flags %#x", flags);
+  AC_REQUIRE((flags & ~(AC_EMIT_NOISY | AC_EMIT_DB_NORM | AC_EMIT_CODES | AC_EMIT_PACKED)) == 0, "unknown flags %#x", flags);
+  if (flags & AC_EMIT_PACKED) {
+    AC_REQUIRE(flags == AC_EMIT_PACKED, "AC_EMIT_PACKED excludes the other flags (got %#x)", flags);
+    return encode_packed_rows(mdct, psy, x, X, t, thr, drown, static_cast<const ac_packed_out*>(noisy_v), db_norm_v, B, K, C,
+                              stream);
+  }
   if (flags & AC_EMIT_CODES) {
     AC_REQUIRE(flags == AC_EMIT_CODES, "AC_EMIT_CODES excludes the other flags (got %#x)", flags);
     return encode_quantized(mdct, psy, x, X, t, thr, drown, static_cast<int16_t*>(noisy_v), static_cast<int8_t*>(db_norm_v), B, K,

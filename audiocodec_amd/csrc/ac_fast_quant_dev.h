@@ -17,6 +17,8 @@
 // signal, reduced from the row in registers over the same runs into two more slot arrays -- and, lane j holding band j's
 // meta word and extremes, bisects [kmin, 254] once per signal of the pair as k_quantize_budget does: band_bits per lane,
 // wave_sum for the row.  codes and sf equal k_quantize_budget on the X and thr of k_fwd_fast bit for bit.
+//
+// PackStage (ac_fast_fwd_qp_dev.h; k_fwd_fast_qp) derives from the BUDGET form and packs the rows behind the search.
 #pragma once
 #include "ac_band_dev.h"
 #include "ac_fast_fwd_dev.h"

@@ -272,6 +272,14 @@ int launch_fwd_fast_quant(const ac_mdct_plan* p, const ac_psy_plan* psy, const f
 int launch_fwd_fast_quant_budget(const ac_mdct_plan* p, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
                                  float drown, int row_bits, int kmin, int16_t* codes, int8_t* sf, int B, int Kin, int F, int C,
                                  hipStream_t s);
+// ... straight to fixed-stride packed rows (k_fwd_fast_qp, ac_fast_fwd_qp.hip; the same plans and shapes, a plan with a row
+// budget of at most kPackRowsMaxBits): data [B F C row_bytes] and fits [B,F,C] are all it writes; row r = (b F + f) C + c at
+// byte r row_bytes holds what launch_pack writes for launch_fwd_fast_quant_budget's codes and sf, zero-padded, or the marked
+// row (every width 31) where that is longer than the slot
+constexpr int kPackRowsMaxBits = AC_PACK_ROWS_MAX_BITS;
+bool fast_encode_pack_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);
+int launch_fwd_fast_pack_rows(const ac_mdct_plan* p, const ac_psy_plan* psy, const float* x, float drown, uint8_t* data,
+                              int64_t row_bytes, uint8_t* fits, int B, int Kin, int F, int C, hipStream_t s);
 int launch_inv_fast(const ac_mdct_plan* p, const float* X, void* x, int iof, const float* tail_in, float* tail_out,
                     int B, int Kp, int nblk, int C, hipStream_t s);
 // synthesis straight from quantised spectra (codes int16 [B,Kp,N,C], sf int8 [B,Kp,M,C]; ac_quant.hip), filters_n 1024 /

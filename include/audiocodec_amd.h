@@ -234,9 +234,28 @@ AC_API int ac_encode_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
  *     ac_encode_quantized_launches returns 1 this is ONE launch that quantises the frame while it is in registers and writes
  *     no float tensor the caller did not ask for; where it returns 2 the call runs the encode followed by the quantiser and
  *     needs X, t and thr as its intermediates (AC_EINVAL when one of them is NULL).
+ *   AC_EMIT_PACKED   the encode at the plan's row budget (ac_psy_plan_with_row_budget) straight to fixed-stride packed rows,
+ *     in ONE launch; exclusive with the other three flags.  out0 addresses one ac_packed_out (a host struct of device
+ *     pointers, read during the call); out1, X, t and thr must be NULL and seed is ignored.  With row_bytes =
+ *     ceil(row_bits / 32) * 4 (the struct's row_bytes must be that, else AC_EINVAL), row r = (b (K+1) + f) C + c takes bytes
+ *     [r row_bytes, (r + 1) row_bytes) of data: the bytes ac_pack writes for the row's codes and sf under AC_EMIT_CODES, then
+ *     zero bytes to the end of the slot, and fits[r] = 1.  A row that is longer than its slot -- offset 254 reached with
+ *     the budget unmet -- is stored as the marked row: every width field 31, then zero bits, fits[r] = 0; it reads as a row
+ *     of bands with sf = -128.  Every byte of data is written.  ac_unpack and ac_decode_quantized's packed form read data
+ *     with index[r] = r row_bytes.  A plan without a row budget is AC_EINVAL.  Served where ac_encode_packed_launches
+ *     returns 1; AC_EUNSUPPORTED elsewhere: compose it from ac_encode_fused, ac_quantize_budget (row_bits_out > 8 row_bytes
+ *     marks a row that does not fit: fill its sf with -128) and ac_pack at those row starts into zero-filled data.
  * out0 / out1: float* noisy, float* db_norm under AC_EMIT_NOISY / AC_EMIT_DB_NORM; int16_t* codes, int8_t* sf under
- * AC_EMIT_CODES. */
-enum { AC_EMIT_NOISY = 1, AC_EMIT_DB_NORM = 2, AC_EMIT_CODES = 4 };
+ * AC_EMIT_CODES; ac_packed_out*, NULL under AC_EMIT_PACKED. */
+enum { AC_EMIT_NOISY = 1, AC_EMIT_DB_NORM = 2, AC_EMIT_CODES = 4, AC_EMIT_PACKED = 8 };
+/* The largest row budget the one launch of AC_EMIT_PACKED serves: a wave stages both rows of its frame pair in the 4 KB of
+ * its LDS buffer that the masking model has left, 2 KB = 16384 bits each. */
+#define AC_PACK_ROWS_MAX_BITS 16384
+typedef struct ac_packed_out {
+  uint8_t* data;     /* [B (K+1) C row_bytes] the packed rows (device) */
+  int64_t row_bytes; /* ceil(row_bits / 32) * 4 of the plan's budget */
+  uint8_t* fits;     /* [B,K+1,C] 1 = the row's codes are in its slot, 0 = the marked row (device) */
+} ac_packed_out;
 AC_API int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
                        float drown, int flags, void* out0, void* out1, uint64_t seed, int B, int K, int C,
                        void* stream);
@@ -245,6 +264,12 @@ AC_API int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
  * else, and every configuration while AC_ENCODE_QUANT_NOFUSE=1 is set in the environment: read per call).  0 for NULL or
  * inconsistent plans.  The results do not depend on it. */
 AC_API int ac_encode_quantized_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C);
+/* Library launches of an encode to fixed-stride packed rows on tensors of C channels: 1 = ac_encode_fused_ex with
+ * AC_EMIT_PACKED serves it (where ac_encode_quantized_launches returns 1, bark_bands_n = 64 and the plan's row budget is at
+ * most AC_PACK_ROWS_MAX_BITS), else ac_encode_launches + 2: the encode, ac_quantize_budget and ac_pack of the composition
+ * above (also everywhere while AC_ENCODE_PACKED_NOFUSE=1 is set in the environment: read per call).  0 for NULL or
+ * mismatched plans, C < 1, or a plan without a row budget.  The bytes do not depend on it. */
+AC_API int ac_encode_packed_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C);
 
 /* 16-bit PCM at the boundary (extension; the reference takes float PCM in [-1, 1] only, mdctransformer.py:104):
  * x = pcm / 32768 on the way in; on the way out pcm = 0 if x is NaN else clamp(rint(fp32(32768 x)), -32768, 32767), rint

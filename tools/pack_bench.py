@@ -4,8 +4,11 @@ decode_packed against decode_quantized, timed with HIP events.  Algorithmic byte
 codes + sf + the index; a decoder: its input + the PCM it writes).  Then decode_packed in its two forms -- the one launch of
 k_inv_fast_p and unpack + decode_quantized (AC_DECODE_PACKED_NOFUSE=1, read per call) -- and decode_quantized, float32 and
 16-bit PCM out, alternating over --rounds rounds of --round-steps calls with the spread of the rounds; the two forms'
-outputs are compared bit for bit first.
-python tools/pack_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7] [--round-steps 30]"""
+outputs are compared bit for bit first.  Last, at a row budget: encode_packed, encode_packed_rows in its two forms (the one
+launch of k_fwd_fast_qp; AC_ENCODE_PACKED_NOFUSE=1: the composition) and encode_quantized, alternating the same way
+(packed_rows(); --only-rows runs this section alone).
+python tools/pack_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7] [--round-steps 30]
+                           [--row-bits 1365] [--only-rows]"""
 import argparse
 import ctypes
 import os
@@ -31,8 +34,50 @@ def timed(fn, steps, warmup):
     return e0.elapsed_time(e1) / steps
 
 
+def packed_rows(a):
+    """encode_packed_rows at a bitrate (DESIGN.md section 8b, "packed rows"): (a) encode_packed, dense, with its host read;
+    (b) the composition of encode_packed_rows (AC_ENCODE_PACKED_NOFUSE=1, read per call); (c) its one launch; (d)
+    encode_quantized -- k_fwd_fast_qb alone -- as the floor.  Alternating in this process, --rounds rounds of --round-steps."""
+    B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    cbr = audiocodec_amd.AudioCodec(48000, N).with_row_budget(a.row_bits)
+    x = (torch.rand((B, K * N, C), device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * 2 - 1)
+    rows, rb = B * (K + 1) * C, cbr.row_bytes
+
+    def composition():
+        os.environ["AC_ENCODE_PACKED_NOFUSE"] = "1"   # (read per call)
+        try:
+            return cbr.encode_packed_rows(x)
+        finally:
+            del os.environ["AC_ENCODE_PACKED_NOFUSE"]
+
+    one, two = cbr.encode_packed_rows(x), composition()
+    assert all(torch.equal(g, r) for g, r in zip(one, two)), "the two forms differ"
+    dense = cbr.encode_packed(x)[0].numel()
+    print("packed rows: B=%d K=%d N=%d C=%d  %d bits per row, row_bytes %d  launches=%d  rows=%d (%d do not fit)  data %.1f MB "
+          "(dense %.1f MB)  the one launch and the composition agree byte for byte"
+          % (B, K, N, C, a.row_bits, rb, cbr.encode_packed_rows_launches(C), rows, int((~one[2]).sum()), rows * rb / 1e6,
+             dense / 1e6))
+    del one, two
+    forms = [("(a) encode_packed (dense, host read)", lambda: cbr.encode_packed(x)),
+             ("(b) encode_packed_rows, composition", composition),
+             ("(c) encode_packed_rows, %d launch" % cbr.encode_packed_rows_launches(C), lambda: cbr.encode_packed_rows(x)),
+             ("(d) encode_quantized (k_fwd_fast_qb)", lambda: cbr.encode_quantized(x))]
+    runs = dict((n, []) for n, _ in forms)
+    for _ in range(a.rounds):
+        for n, fn in forms:
+            runs[n].append(timed(fn, a.round_steps, 1))
+    med = []
+    for n, _ in forms:
+        v = sorted(runs[n])
+        med.append(v[len(v) // 2])
+        print("%-40s median %.3f ms  min %.3f  max %.3f  (%d alternating rounds of %d)" % (n, med[-1], v[0], v[-1], len(v), a.round_steps))
+    print("(c) / (b) = %.3f   (c) / (a) = %.3f   (c) / (d) = %.3f" % (med[2] / med[1], med[2] / med[0], med[2] / med[3]))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--row-bits", type=int, default=1365, help="the row budget of the packed-rows section (64 kbit/s)")
+    ap.add_argument("--only-rows", action="store_true", help="only the packed-rows section")
     ap.add_argument("--clips", type=int, default=256)
     ap.add_argument("--blocks", type=int, default=468)
     ap.add_argument("--filters", type=int, default=1024)
@@ -43,6 +88,8 @@ def main():
     ap.add_argument("--round-steps", type=int, default=30)
     a = ap.parse_args()
     B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    if a.only_rows:
+        return packed_rows(a)
     codec = audiocodec_amd.AudioCodec(48000, N)
     psy, lib = codec.psy, _lib.load()
     M = psy.bark_bands_n
@@ -140,6 +187,7 @@ def main():
     for k in (0, 3):
         print("%s: one launch / composition = %.3f   one launch / decode_quantized = %.3f"
               % ("pcm16" if k else "f32", med[forms[k][0]] / med[forms[k + 1][0]], med[forms[k][0]] / med[forms[k + 2][0]]))
+    packed_rows(a)
 
 
 if __name__ == "__main__":
