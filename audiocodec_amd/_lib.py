@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("AUDIOCODEC_AMD_LIB") or os.path.join(_HERE, "lib", "l
 AC_OK = 0
 AC_EINVAL, AC_EHIP, AC_ENOMEM, AC_ENODEV, AC_EUNSUPPORTED = -1, -2, -3, -4, -5
 AC_EMIT_NOISY, AC_EMIT_DB_NORM, AC_EMIT_CODES, AC_EMIT_PACKED = 1, 2, 4, 8   # flags of ac_encode_fused_ex
+AC_PACKED = 16   # spectrum-side format of ac_stream_encode_typed / ac_stream_inverse_typed: packed rows
 AC_PACK_ROWS_MAX_BITS = 16384   # the largest row budget AC_EMIT_PACKED serves in one launch (the header's macro)
 WINDOW_IDS = {"vorbis": 0, "sine": 1}   # anything else -> 2 (rectangular), mdctransformer.py:199-211
 WINDOW_RECT = 2
@@ -111,6 +112,7 @@ PROTOTYPES = {
     "ac_encode_quantized_launches": (c_int, [c_void_p, c_void_p, c_int]),
     "ac_decode_packed_launches": (c_int, [c_void_p, c_void_p, c_int]),
     "ac_encode_packed_launches": (c_int, [c_void_p, c_void_p, c_int]),
+    "ac_stream_packed_launches": (c_int, [c_void_p, c_void_p, c_int]),
     "ac_pack_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ac_pack_index": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ac_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
@@ -132,6 +134,11 @@ class PackedRows(ctypes.Structure):
 class PackedOut(ctypes.Structure):
     """``ac_packed_out``: what ``ac_encode_fused_ex`` takes for ``out0`` under ``AC_EMIT_PACKED``."""
     _fields_ = [("data", c_void_p), ("row_bytes", ctypes.c_int64), ("fits", c_void_p)]
+
+
+class StreamPackedIn(ctypes.Structure):
+    """``ac_stream_packed_in``: what ``ac_stream_inverse_typed`` takes for ``X_chunk`` under ``AC_PACKED``."""
+    _fields_ = [("rows", PackedRows), ("psy", c_void_p), ("pcm16", ctypes.c_int32)]
 
 
 _lock = threading.Lock()

@@ -21,6 +21,25 @@ from .mdctransformer import MDCTransformer
 from .psychoacoustic import PsychoacousticModel
 
 
+def _pack_rows_of_spectra(psy, X, thr, index, row_bytes):
+    """The tail of the composition of packed rows, shared by :meth:`AudioCodec.encode_packed_rows` and
+    :meth:`StreamingMDCT.encode_packed_rows_chunk`: ``psy.quantize_to_budget`` at the model's budget on X, thr [B, F, N, C] (on
+    plain allocations: nothing here may wait for the device), rows longer than their slot marked, then the packer at the fixed
+    row starts ``index`` into zero-filled data.  Returns (data uint8 [B*F*C*row_bytes], fits bool [B, F, C]); everything is
+    enqueued on the current stream."""
+    B, F, _, C = X.shape
+    dev = X.device
+    row_bits, min_offset = psy.row_budget
+    codes, sf, _, bits = psy.quantize_to_budget(X, thr, row_bits, min_offset)
+    fits = bits <= 8 * row_bytes
+    sf.masked_fill_(~fits.unsqueeze(2), -128)   # width 31 follows whatever the codes are
+    data = torch.zeros((B * F * C * row_bytes,), dtype=torch.uint8, device=dev)
+    with _host.on_device(dev):
+        _lib.check(_lib.load().ac_pack(psy._plan(dev), _host.ptr(codes), _host.ptr(sf), _host.ptr(index), _host.ptr(data), B, F, C,
+                                       _host.stream_ptr(dev)))
+    return data, fits
+
+
 class AudioCodec:
     """MDCT analysis + psychoacoustic masking (encode) and MDCT synthesis (decode)."""
 
@@ -362,13 +381,7 @@ class AudioCodec:
         t = torch.empty((B, F, 1, C), dtype=torch.float32, device=dev)
         thr = torch.empty_like(X)
         self.encode_into(x, X, t, thr, drown)
-        codes, sf, _, bits = self.psy.quantize_to_budget(X, thr, self.row_bits, self.psy.row_budget[1])
-        fits = bits <= 8 * rb
-        sf.masked_fill_(~fits.unsqueeze(2), -128)   # width 31 follows whatever the codes are
-        data = torch.zeros((rows * rb,), dtype=torch.uint8, device=dev)
-        with _host.on_device(dev):
-            _lib.check(self._lib.ac_pack(psy, _host.ptr(codes), _host.ptr(sf), _host.ptr(index), _host.ptr(data), B, F, C,
-                                         _host.stream_ptr(dev)))
+        data, fits = _pack_rows_of_spectra(self.psy, X, thr, index, rb)
         return data, index, fits
 
     # ---- rate control per clip (extension) ------------------------------------------------
@@ -463,7 +476,9 @@ class StreamingMDCT:
     (the stored last block of the previous chunk for ``i = 0``); synthesis block ``i`` overlap-adds
     frame ``i`` with the stored aliased half of the previous frame.  With a masking model (``psy``)
     :meth:`encode_chunk` also returns tonality and threshold of the chunk's frames -- bit for bit what the one-shot
-    ``AudioCodec.encode`` gives for those frames.
+    ``AudioCodec.encode`` gives for those frames.  On a stream of a codec at a bitrate (``with_bitrate()``)
+    :meth:`encode_packed_rows_chunk` and :meth:`decode_packed_chunk` go from a chunk of PCM to fixed-stride packed rows and
+    back on the same state, one launch each where :meth:`packed_chunk_launches` is 1.
 
     Streams: every chunk call only enqueues on its stream -- the current one, or ``stream=`` -- and never touches the
     default stream or waits for the device.  Creating the object may block the host and leaves the float32 state zeroed;
@@ -520,18 +535,20 @@ class StreamingMDCT:
             raise ValueError("%s lives on %s but the stream's state lives on %s" % (name, x.device, self.device))
         return x
 
-    def _out(self, out, name, shape, like, stream=None):
+    def _out(self, out, name, shape, like, stream=None, dtype=None):
+        """``out``, checked, or a new tensor on ``like``'s device, of ``dtype`` (default: ``like``'s)."""
+        dtype, device = like.dtype if dtype is None else dtype, like.device
         if out is None:
             # the allocator's pool (and reuse order) of the stream the work runs on; no test can assert this (only a reuse of
             # freed memory by another stream's work would show it): the class docstring states the rule
             if stream is not None:
                 with torch.cuda.stream(stream):
-                    return torch.empty(shape, dtype=like.dtype, device=like.device)
-            return torch.empty(shape, dtype=like.dtype, device=like.device)
-        if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != like.dtype \
-                or out.device != like.device or not out.is_contiguous() or out.data_ptr() % 16 != 0:
+                    return torch.empty(shape, dtype=dtype, device=device)
+            return torch.empty(shape, dtype=dtype, device=device)
+        if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != dtype \
+                or out.device != device or not out.is_contiguous() or out.data_ptr() % 16 != 0:
             raise ValueError("%s must be a contiguous, 16-byte aligned %s tensor of shape %s on %s"
-                             % (name, like.dtype, tuple(shape), like.device))
+                             % (name, dtype, tuple(shape), device))
         return out
 
     def _stream(self, stream):
@@ -699,3 +716,102 @@ class StreamingMDCT:
             _lib.check(self._lib.ac_stream_inverse_typed(self._handle, _host.ptr(X), _host.ptr(x), self.mdct._dtype_id, k,
                                                          self._stream(stream)))
         return x
+
+    # ---- packed rows at a bitrate, chunk by chunk (extension; DESIGN.md section 8b, "Packed rows in a stream") -----
+    def _packed_ready(self, what, budget):
+        _host.require_float32(self.mdct.compute_dtype, "StreamingMDCT.%s" % what)
+        if self.psy is None:
+            raise ValueError("this stream was created without a masking model (psy=...)")
+        if budget and self.psy.row_budget is None:
+            raise ValueError("%s needs a stream with a row budget: make it from a codec of with_bitrate() or "
+                             "with_row_budget() (codec.stream(...))" % what)
+
+    def _on(self, stream):
+        return torch.cuda.stream(stream) if stream is not None else _host._NO_SWITCH
+
+    @property
+    def row_bytes(self):
+        """Bytes of a row's slot in :meth:`encode_packed_rows_chunk`'s data; None without a row budget."""
+        if self.psy is None or self.psy.row_budget is None:
+            return None
+        return (self.psy.row_budget[0] + 31) // 32 * 4
+
+    def packed_chunk_launches(self, decode=False):
+        """Library launches of :meth:`encode_packed_rows_chunk` (``decode=True``: of :meth:`decode_packed_chunk`) on this
+        stream (``ac_stream_packed_launches``): 1 = one launch that carries the overlap state -- filters_n = 1024, 64 bands,
+        mono / stereo, a budget of at most ``_lib.AC_PACK_ROWS_MAX_BITS``, and for the encode a kernel instance that passed
+        the register gate (stereo with ``spreading="f32"`` did not) -- else the launches of the composition (everywhere
+        while ``AC_ENCODE_PACKED_NOFUSE=1`` / ``AC_DECODE_PACKED_NOFUSE=1`` is set: read per call).  0 for the encode on a
+        stream without a row budget."""
+        self._packed_ready("packed_chunk_launches", False)
+        return int(self._lib.ac_stream_packed_launches(self._handle, self.psy._plan(self.device), 1 if decode else 0))
+
+    def encode_packed_rows_chunk(self, x_chunk, drown=0.0, stream=None):
+        """On a stream of a codec made by ``with_bitrate()`` / ``with_row_budget()``: x_chunk [B, k*N, C] -> (data uint8
+        [B*k*C*row_bytes], index int64 [B, k, C], fits bool [B, k, C]) -- the rows ``AudioCodec.encode_packed_rows`` gives
+        for the chunk's frames of the whole signal, byte for byte: frame ``f`` of the chunk is frame (blocks so far + f),
+        ``index[b, f, c] = ((b*k + f)*C + c) * row_bytes``.  The overlap state advances as under :meth:`encode_chunk`, so
+        the chunk calls of every form may follow each other.  One launch where :meth:`packed_chunk_launches` is 1, else
+        :meth:`encode_chunk`, ``psy.quantize_to_budget`` and the packer: the same bytes.  Only enqueues, on ``stream`` or
+        the current stream; float32 only, not differentiable."""
+        self._packed_ready("encode_packed_rows_chunk", True)
+        N, rb = self.mdct.filters_n, self.row_bytes
+        with self._on(stream):
+            x = self._check_chunk(x_chunk, "x_chunk", 3)
+            B, S, C = x.shape
+            if (B, C) != (self.B, self.C) or S % N != 0:
+                raise ValueError("x_chunk must be [%d, k*%d, %d], got %s" % (self.B, N, self.C, tuple(x.shape)))
+            k = S // N
+            dev, rows = x.device, B * k * C
+            index = (torch.arange(rows, dtype=torch.int64, device=dev) * rb).view(B, k, C)
+            if rows == 0:
+                return (torch.empty((0,), dtype=torch.uint8, device=dev), index,
+                        torch.empty((B, k, C), dtype=torch.bool, device=dev))
+            psy = self.psy._plan(dev)
+            if self._lib.ac_stream_packed_launches(self._handle, psy, 0) == 1:
+                data = torch.empty((rows * rb,), dtype=torch.uint8, device=dev)
+                fits = torch.empty((B, k, C), dtype=torch.bool, device=dev)
+                out = _lib.PackedOut(data.data_ptr(), rb, fits.data_ptr())
+                with _host.on_device(dev):
+                    _lib.check(self._lib.ac_stream_encode_typed(self._handle, psy, _host.ptr(x), ctypes.addressof(out), None,
+                                                                None, float(drown), _lib.AC_PACKED, k, self._stream(stream)))
+                return data, index, fits
+            X, _, thr = self.encode_chunk(x, drown, stream=stream)
+            data, fits = _pack_rows_of_spectra(self.psy, X, thr, index, rb)
+            return data, index, fits
+
+    def decode_packed_chunk(self, data, index, pcm16=False, out=None, stream=None):
+        """data uint8 [nbytes], index int64 [B, k, C] -> x [B, k*N, C] (``torch.int16`` with ``pcm16=True``): the next k
+        blocks of the signal, bit-equal to ``inverse_chunk(psy.dequantize(*psy.unpack(data, index)))`` -- with ``pcm16``
+        through the store of ``AudioCodec.decode``: ``0 if NaN else clamp(rint(fp32(32768 * x)), -32768, 32767)``.
+        ``index`` may hold any row starts and damaged rows read as ``psy.unpack`` reads them.  One launch where
+        ``packed_chunk_launches(decode=True)`` is 1, else that composition.  Only enqueues, on ``stream`` or the current
+        stream; float32 only."""
+        self._packed_ready("decode_packed_chunk", False)
+        N = self.mdct.filters_n
+        with self._on(stream):
+            data = self.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
+            if data.device != self.device:
+                raise ValueError("data lives on %s but the stream's state lives on %s" % (data.device, self.device))
+            index = self.psy._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
+            B, k, C = index.shape
+            if (B, C) != (self.B, self.C):
+                raise ValueError("index must be [%d, k, %d], got %s" % (self.B, self.C, tuple(index.shape)))
+            x = self._out(out, "out", (B, k * N, C), data, stream, dtype=torch.int16 if pcm16 else torch.float32)
+            if k == 0:
+                return x
+            dev = data.device
+            psy = self.psy._plan(dev)
+            if self._lib.ac_stream_packed_launches(self._handle, psy, 1) == 1:
+                rows = _lib.StreamPackedIn(_lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr()), psy.value,
+                                           1 if pcm16 else 0)
+                with _host.on_device(dev):
+                    _lib.check(self._lib.ac_stream_inverse_typed(self._handle, ctypes.addressof(rows), _host.ptr(x),
+                                                                 _lib.AC_PACKED, k, self._stream(stream)))
+                return x
+            X = self.psy.dequantize(*self.psy.unpack(data, index))
+            if not pcm16:
+                return self.inverse_chunk(X, out=x, stream=stream)
+            p = torch.nan_to_num(self.inverse_chunk(X, stream=stream) * 32768.0, nan=0.0)   # the float32 product
+            x.copy_(p.round_().clamp_(-32768.0, 32767.0).to(torch.int16))                   # round: half to even
+            return x

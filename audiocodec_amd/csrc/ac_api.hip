@@ -1232,8 +1232,8 @@ int ac_decode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const 
     AC_REQUIRE_ALIGNED(rows.data, rows.index, out);
     DeviceGuard guard(mdct->device);
     if (Kp >= 1)
-      return launch_inv_fast_packed(mdct, psy, rows.data, rows.nbytes, rows.index, out, pcm16 != nullptr, B, Kp, C,
-                                    (hipStream_t)stream);
+      return launch_inv_fast_packed(mdct, psy, rows.data, rows.nbytes, rows.index, out, pcm16 != nullptr, nullptr, nullptr, B, Kp,
+                                    Kp + 1, C, (hipStream_t)stream);
     return mdct_inverse(mdct, nullptr, out, pcm16 != nullptr, B, Kp, C, stream);
   }
   AC_REQUIRE(Kp == 0 || (codes != nullptr && sf != nullptr), "NULL tensor pointer");
@@ -1486,8 +1486,94 @@ static int stream_typed_check(const ac_stream* s, int dtype, int k) {
   return AC_OK;
 }
 
+// ---- packed rows in a stream (AC_PACKED): a chunk of k blocks to k fixed-stride packed rows per signal
+// and back, one launch each, on the float32 state of the stream
+static bool stream_packed_args_match(const ac_stream* s, const ac_psy_plan* psy) {
+  return s && psy && s->plan && s->plan->N == psy->N && s->plan->device == psy->device;
+}
+static bool stream_encode_packed_fuses(const ac_stream* s, const ac_psy_plan* psy) {
+  return encode_packed_fuses(s->plan, psy, s->C) && fast_encode_pack_stream_serves(s->plan, psy, s->C);
+}
+
+int ac_stream_packed_launches(const ac_stream* s, const ac_psy_plan* psy, int decode) {
+  if (!stream_packed_args_match(s, psy)) return 0;
+  if (decode) return decode_packed_fuses(s->plan, psy, s->C) ? 1 : 3;   // ac_unpack, ac_dequantize, ac_stream_inverse
+  if (!psy->row_bits) return 0;
+  // ac_stream_encode, ac_quantize_budget, ac_pack
+  return stream_encode_packed_fuses(s, psy) ? 1 : ac_encode_launches(s->plan, psy, s->C) + 2;
+}
+
+static int stream_encode_packed(ac_stream* s, const ac_psy_plan* psy, const void* x_chunk, const ac_packed_out* out, const void* t,
+                                const void* thr, double drown, int k, void* stream) {
+  AC_REQUIRE(s != nullptr, "stream is NULL");
+  AC_REQUIRE(psy != nullptr, "AC_PACKED needs the masking model's plan");
+  AC_REQUIRE(k >= 0, "negative chunk length %d", k);
+  const ac_mdct_plan* p = s->plan;
+  AC_REQUIRE(p->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", p->N, psy->N);
+  AC_REQUIRE(p->device == psy->device, "plans live on different devices");
+  AC_REQUIRE(psy->row_bits != 0, "AC_PACKED needs a plan with a row budget (ac_psy_plan_with_row_budget)");
+  AC_REQUIRE(t == nullptr && thr == nullptr, "AC_PACKED writes no t or thr: they must be NULL");
+  AC_REQUIRE(out != nullptr, "AC_PACKED without its ac_packed_out (X)");
+  const ac_packed_out po = *out;
+  const int64_t row_bytes = (int64_t)((psy->row_bits + 31) / 32) * 4;
+  AC_REQUIRE(po.row_bytes == row_bytes, "row_bytes (%lld) is not the plan's ceil(%d / 32) * 4 = %lld", (long long)po.row_bytes,
+             psy->row_bits, (long long)row_bytes);
+  if (k == 0) return AC_OK;
+  if (!stream_encode_packed_fuses(s, psy)) {
+    set_error("AC_PACKED: no kernel encodes a chunk to packed rows in one launch for filters_n = %d, bark_bands_n = %d, %d "
+              "channels, row budget %d here (ac_stream_packed_launches() != 1): use the composition -- ac_stream_encode, "
+              "ac_quantize_budget, then ac_pack at row starts r * row_bytes into zero-filled data",
+              p->N, psy->M, s->C, psy->row_bits);
+    return AC_EUNSUPPORTED;
+  }
+  int st = check_quant(psy, s->B, k, s->C);
+  if (st) return st;
+  AC_REQUIRE(po.data != nullptr && po.fits != nullptr && x_chunk != nullptr, "NULL tensor pointer");
+  AC_REQUIRE_ALIGNED(x_chunk, po.data);
+  DeviceGuard guard(s->device);
+  st = launch_fwd_fast_pack_rows_stream(p, psy, static_cast<const float*>(x_chunk), (float)drown, po.data, row_bytes, po.fits,
+                                        s->d_prev_block, s->d_prev_tmp, s->B, k, s->C, (hipStream_t)stream);
+  if (st) return st;
+  std::swap(s->d_prev_block, s->d_prev_tmp);
+  return AC_OK;
+}
+
+static int stream_inverse_packed(ac_stream* s, const ac_stream_packed_in* in, void* x, int k, void* stream) {
+  AC_REQUIRE(s != nullptr, "stream is NULL");
+  AC_REQUIRE(k >= 0, "negative chunk length %d", k);
+  AC_REQUIRE(in != nullptr, "AC_PACKED without its ac_stream_packed_in (X_chunk)");
+  const ac_stream_packed_in pin = *in;
+  const ac_psy_plan* psy = pin.psy;
+  const ac_mdct_plan* p = s->plan;
+  AC_REQUIRE(psy != nullptr, "ac_stream_packed_in: psy is NULL");
+  AC_REQUIRE(p->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", p->N, psy->N);
+  AC_REQUIRE(p->device == psy->device, "plans live on different devices");
+  AC_REQUIRE(pin.pcm16 == 0 || pin.pcm16 == 1, "ac_stream_packed_in: pcm16 must be 0 or 1 (got %d)", (int)pin.pcm16);
+  if (k == 0) return AC_OK;
+  if (!decode_packed_fuses(p, psy, s->C)) {
+    set_error("AC_PACKED: no kernel decodes a chunk of packed rows in one launch for filters_n = %d, bark_bands_n = %d, %d "
+              "channels here (ac_stream_packed_launches() != 1): use the composition -- ac_unpack, ac_dequantize, then "
+              "ac_stream_inverse",
+              p->N, psy->M, s->C);
+    return AC_EUNSUPPORTED;
+  }
+  int st = check_quant(psy, s->B, k, s->C);
+  if (st) return st;
+  AC_REQUIRE(pin.rows.nbytes >= 0, "negative nbytes (%lld)", (long long)pin.rows.nbytes);
+  AC_REQUIRE(pin.rows.index != nullptr && x != nullptr, "NULL tensor pointer");
+  AC_REQUIRE(pin.rows.data != nullptr || pin.rows.nbytes == 0, "data is NULL");
+  AC_REQUIRE_ALIGNED(pin.rows.data, pin.rows.index, x);
+  DeviceGuard guard(s->device);
+  st = launch_inv_fast_packed(p, psy, pin.rows.data, pin.rows.nbytes, pin.rows.index, x, pin.pcm16 != 0, s->d_tail, s->d_tail_tmp,
+                              s->B, k, k, s->C, (hipStream_t)stream);
+  if (st) return st;
+  std::swap(s->d_tail, s->d_tail_tmp);
+  return AC_OK;
+}
+
 int ac_stream_encode_typed(ac_stream* s, const ac_psy_plan* psy, const void* x_chunk, void* X, void* t, void* thr, double drown,
                            int dtype, int k, void* stream) {
+  if (dtype == AC_PACKED) return stream_encode_packed(s, psy, x_chunk, static_cast<const ac_packed_out*>(X), t, thr, drown, k, stream);
   AC_REQUIRE_DTYPE(dtype);
   if (dtype == AC_F32) {
     if (psy) return ac_stream_encode(s, psy, static_cast<const float*>(x_chunk), static_cast<float*>(X), static_cast<float*>(t),
@@ -1534,6 +1620,7 @@ int ac_stream_encode_typed(ac_stream* s, const ac_psy_plan* psy, const void* x_c
 }
 
 int ac_stream_inverse_typed(ac_stream* s, const void* X_chunk, void* x, int dtype, int k, void* stream) {
+  if (dtype == AC_PACKED) return stream_inverse_packed(s, static_cast<const ac_stream_packed_in*>(X_chunk), x, k, stream);
   AC_REQUIRE_DTYPE(dtype);
   if (dtype == AC_F32) return ac_stream_inverse(s, static_cast<const float*>(X_chunk), static_cast<float*>(x), k, stream);
   int st = stream_typed_check(s, dtype, k);

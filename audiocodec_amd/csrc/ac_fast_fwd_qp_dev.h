@@ -204,5 +204,25 @@ __global__ __launch_bounds__(AC_WAVES_PSY * 64, 2) void k_fwd_fast_qp(FwdArgs a,
   fwd_fast_body<8, CMODE, true, AC_WAVES_PSY, 0, SPREAD, false, PackStage<8, CMODE, SPREAD>>(a, lds, (int)blockIdx.x, (int)gridDim.x, qz);
 }
 
+// k_fwd_fast_qp on a chunk of a stream (instantiated in ac_fast_fwd_qps.hip): F == Kin, a.prev_block is block -1 of every
+// signal and the wave that loads block Kin - 1 stores it to a.state_out, as k_fwd_fast does for ac_stream_encode.  A kernel
+// of its own, so that the one-shot instances keep their registers and their text.
+template <int CMODE, int SPREAD>
+__global__ __launch_bounds__(AC_WAVES_PSY * 64, 2) void k_fwd_fast_qps(FwdArgs a, QuantOut q, PackOut po, int row_bits, int kmin) {
+  __shared__ __attribute__((aligned(16))) char lds[fwd_lds_bytes<8, true, AC_WAVES_PSY, SPREAD>()];
+  PackStage<8, CMODE, SPREAD> qz;
+  q.codes = nullptr;
+  q.sf = nullptr;
+  qz.q = q;
+  qz.po = po;
+  qz.pp = a.psy;
+  qz.row_bits = row_bits;
+  qz.kmin = kmin;
+  a.C = CMODE == 0 ? 2 : 1;
+  a.X = a.t = a.thr = nullptr;
+  a.noisy = a.dbn = nullptr;
+  fwd_fast_body<8, CMODE, true, AC_WAVES_PSY, 0, SPREAD, false, PackStage<8, CMODE, SPREAD>>(a, lds, (int)blockIdx.x, (int)gridDim.x, qz);
+}
+
 }  // namespace
 }  // namespace ac

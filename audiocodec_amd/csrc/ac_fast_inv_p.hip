@@ -16,15 +16,16 @@ static void launch_inv_p(const InvArgs& a, const PackedRows& pr, int C, unsigned
 }
 
 int launch_inv_fast_packed(const ac_mdct_plan* p, const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes,
-                           const int64_t* index, void* x, bool pcm16, int B, int Kp, int C, hipStream_t s) {
+                           const int64_t* index, void* x, bool pcm16, const float* tail_in, float* tail_out, int B, int Kp,
+                           int nblk, int C, hipStream_t s) {
   if (B <= 0 || C <= 0 || Kp <= 0) return AC_OK;
-  if (!fast_inv_packed_serves(p, psy, C)) {
+  if (!fast_inv_packed_serves(p, psy, C) || (nblk != Kp && nblk != Kp + 1)) {
     set_error("internal: no synthesis from packed rows for filters_n = %d, %d bands, %d channels", p->N, psy->M, C);
     return AC_EUNSUPPORTED;
   }
   InvArgs a;
   unsigned grid;
-  int st = prep_inv_fast(p, nullptr, x, pcm16 ? 1 : 0, nullptr, nullptr, B, Kp, Kp + 1, C, a, grid);
+  int st = prep_inv_fast(p, nullptr, x, pcm16 ? 1 : 0, tail_in, tail_out, B, Kp, nblk, C, a, grid);
   if (st) return st;
   if (a.seglen > P_SLOTS - 1) {   // (AC_SEGLEN asked for longer strips than a wave holds band records for)
     a.seglen = P_SLOTS - 1;

@@ -280,6 +280,13 @@ constexpr int kPackRowsMaxBits = AC_PACK_ROWS_MAX_BITS;
 bool fast_encode_pack_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);
 int launch_fwd_fast_pack_rows(const ac_mdct_plan* p, const ac_psy_plan* psy, const float* x, float drown, uint8_t* data,
                               int64_t row_bytes, uint8_t* fits, int B, int Kin, int F, int C, hipStream_t s);
+// ... for a chunk of k blocks of a stream (k_fwd_fast_qps, ac_fast_fwd_qps.hip): k frames per signal, frame 0 pairs block 0 with
+// prev_block [B,N,C]; state_out (another buffer) receives block k - 1.  Serves where fast_encode_pack_serves() and the
+// instance passed the register gate
+bool fast_encode_pack_stream_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);
+int launch_fwd_fast_pack_rows_stream(const ac_mdct_plan* p, const ac_psy_plan* psy, const float* x, float drown, uint8_t* data,
+                                     int64_t row_bytes, uint8_t* fits, const float* prev_block, float* state_out, int B, int k,
+                                     int C, hipStream_t s);
 int launch_inv_fast(const ac_mdct_plan* p, const float* X, void* x, int iof, const float* tail_in, float* tail_out,
                     int B, int Kp, int nblk, int C, hipStream_t s);
 // synthesis straight from quantised spectra (codes int16 [B,Kp,N,C], sf int8 [B,Kp,M,C]; ac_quant.hip), filters_n 1024 /
@@ -288,10 +295,12 @@ bool fast_inv_quant_serves(const ac_mdct_plan* p, int C);
 int launch_inv_fast_quant(const ac_mdct_plan* p, const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, void* x,
                           bool pcm16, int B, int Kp, int C, hipStream_t s);
 // ... and from rows of the packed bitstream (k_inv_fast_p, ac_fast_inv_p.hip): filters_n = 1024 with 64 bands, mono / stereo;
-// data [nbytes], index [B,Kp,C]; bit-equal to launch_inv_fast_quant on launch_unpack's output, damaged rows included
+// data [nbytes], index [B,Kp,C]; bit-equal to launch_inv_fast_quant on launch_unpack's output, damaged rows included.
+// nblk = Kp + 1 with null tails: the one-shot synthesis; nblk = Kp with the stream's tail buffers: a chunk of a stream
 bool fast_inv_packed_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);
 int launch_inv_fast_packed(const ac_mdct_plan* p, const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes,
-                           const int64_t* index, void* x, bool pcm16, int B, int Kp, int C, hipStream_t s);
+                           const int64_t* index, void* x, bool pcm16, const float* tail_in, float* tail_out, int B, int Kp,
+                           int nblk, int C, hipStream_t s);
 int launch_psy_fast(const ac_psy_plan* p, const float* X, const float* t_in, float* t_out, float* thr, float drown,
                     int B, int F, int C, hipStream_t s, int iof = 0);
 // streaming duplex: the analysis of a chunk of k_fwd blocks (psy: with the fused masking model) and the synthesis of a

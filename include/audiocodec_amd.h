@@ -49,7 +49,8 @@ extern "C" {
                           * ac_pack, ac_unpack, ac_pack_scratch_bytes; decoded in one launch: ac_packed_rows,
                           * ac_decode_packed_launches) and its rate control (ac_quantize_budget, per clip
                           * ac_quantize_clip_budget, ac_clip_budget_scratch_bytes; in the plan: ac_psy_plan_with_row_budget,
-                          * ac_psy_plan_row_budget); additions only, so the number stays.
+                          * ac_psy_plan_row_budget; packed rows in a stream: AC_PACKED, ac_stream_packed_in,
+                          * ac_stream_packed_launches); additions only, so the number stays.
                           * 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
                           * with a 5-smooth half up to 8192, float32); masking model for general band layouts up to 4096 bins.
                           * 0.1.7: only the ac_* entry points are exported; ac_stream_settle (home buffers for the streaming state);
@@ -542,6 +543,34 @@ AC_API int ac_encode_fused_typed(const ac_mdct_plan* mdct, const ac_psy_plan* ps
 AC_API int ac_stream_encode_typed(ac_stream* s, const ac_psy_plan* psy, const void* x_chunk, void* X, void* t, void* thr,
                                   double drown, int dtype, int k, void* stream);
 AC_API int ac_stream_inverse_typed(ac_stream* s, const void* X_chunk, void* x, int dtype, int k, void* stream);
+/* Packed rows in a stream (extension): AC_PACKED is a format of the SPECTRUM side of the two calls above and
+ * of nothing else -- every other *_typed entry point rejects it as a dtype.  The PCM side is float32 (or, out of the decoder,
+ * 16-bit PCM); the overlap state is the float32 state ac_stream_encode / ac_stream_inverse keep, in the same pair of buffers, so
+ * chunk calls of every form may follow each other on one ac_stream and ac_stream_settle / ac_stream_run find the state.
+ *   ac_stream_encode_typed(s, psy, x_chunk, X, NULL, NULL, drown, AC_PACKED, k, stream): x_chunk float32 [B,k*N,C]; X addresses
+ *     one ac_packed_out (its row_bytes must be the plan's ceil(row_bits / 32) * 4, else AC_EINVAL); psy must carry a row budget
+ *     (AC_EINVAL otherwise) and t, thr must be NULL.  Writes data [B k C row_bytes] and fits [B,k,C]: row r = (b k + f) C + c,
+ *     frame f of the chunk being frame (blocks so far + f) of the stream, holds the bytes AC_EMIT_PACKED writes for that frame
+ *     -- ac_pack's bytes then zeros, or the marked row.  k == 0 is AC_OK.
+ *   ac_stream_inverse_typed(s, X_chunk, x, AC_PACKED, k, stream): X_chunk addresses one ac_stream_packed_in; x is float32 or
+ *     int16 [B,k*N,C] per pcm16.  Bit-equal to ac_unpack, ac_dequantize, ac_stream_inverse (pcm16: that result through
+ *     ac_mdct_inverse_pcm16's store: 0 if NaN else clamp(rint(fp32(32768 x)), -32768, 32767)); damaged rows and row starts outside
+ *     data read as ac_unpack reads them.
+ * Each is ONE launch where ac_stream_packed_launches returns 1, and AC_EUNSUPPORTED elsewhere, with the state untouched: compose
+ * it from ac_stream_encode, ac_quantize_budget (row_bits_out > 8 row_bytes: fill the row's sf with -128) and ac_pack at row
+ * starts r row_bytes into zero-filled data; from ac_unpack, ac_dequantize and ac_stream_inverse.
+ * ac_stream_packed_launches(s, psy, decode): library launches of a chunk on this stream.  decode = 0: 1 where
+ *   ac_encode_packed_launches is 1 for the stream's channels and the kernel instance with streaming state passed its register
+ *   gate (stereo with the f32 spreading product did not), else ac_encode_launches + 2.  decode != 0: 1 where
+ *   ac_decode_packed_launches is 1, else 3.  AC_ENCODE_PACKED_NOFUSE=1 / AC_DECODE_PACKED_NOFUSE=1 apply as they do one-shot
+ *   (read per call).  0 for NULL or mismatched arguments, or (decode = 0) a plan without a row budget. */
+enum { AC_PACKED = 16 };   /* ac_stream_encode_typed / ac_stream_inverse_typed: the spectra are packed rows */
+typedef struct ac_stream_packed_in {
+  ac_packed_rows rows;      /* data, nbytes, index [B,k,C] */
+  const ac_psy_plan* psy;   /* the band layout of the rows */
+  int32_t pcm16;            /* 0: x is float32 [B,k*N,C]; 1: int16 */
+} ac_stream_packed_in;
+AC_API int ac_stream_packed_launches(const ac_stream* s, const ac_psy_plan* psy, int decode);
 AC_API int ac_amplitude_to_db_typed(const void* a, void* out, size_t n, int norm, int dtype, void* stream);
 AC_API int ac_add_noise_typed(const void* X, const void* thr, void* out, size_t n, uint64_t seed, int dtype, void* stream);
 

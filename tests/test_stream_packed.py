@@ -1,0 +1,606 @@
+"""Packed rows in a stream: ``StreamingMDCT.encode_packed_rows_chunk`` / ``decode_packed_chunk``, the
+``AC_PACKED`` form of ``ac_stream_encode_typed`` / ``ac_stream_inverse_typed`` behind them, and the one launch per chunk at
+filters_n = 1024 -- k_fwd_fast_qps (k_fwd_fast_qp with the overlap state live) and k_inv_fast_p with the tail state.
+
+The reference of every GPU comparison is the one-shot call on the whole signal: ``encode_packed_rows(x)`` viewed as
+[B, K+1, C, row_bytes] for the encode, ``decode_packed(data, index, pcm16)[:, :K*N]`` for the decode; every comparison is bit
+for bit.  The input is test_encode_cbr's ``_input(C, 3, 7, seed, True)``: mono B = 3 (a half-empty pair), a zero frame, NaN,
+Inf, the 1e15 sample, and the 3e12 sample in block 4 whose rows do not fit a small budget -- with the chunking (2, 3, 2) that
+block is the state handed to the next chunk.  Before any comparison the reference alone must show that a budget binds and
+that every chunk boundary matters (a fresh stream gives other rows / other PCM there), so a kernel that ignored the state
+cannot pass.  Which kernel instances passed the register gate is read from the library's symbols.
+
+Three places where the input itself rules a check out, each stated where it applies: at 320 bits a row holds widths only, so
+no boundary can show the state in the rows; in mono the decoded blocks 3 and 4 are NaN (or follow the all-zero frame) in
+every clip whatever the tail; and with three channels at filters_n = 1024 the one-shot 16-bit PCM comes from other kernels
+than the one-shot float32 PCM and differs from the stated store of it in a few samples (16 of 64 512), so there the 16-bit
+PCM of the composition is held to the stated definition on the one-shot float32 result.
+"""
+
+import ctypes
+import functools
+import os
+import re
+
+import pytest
+import torch
+
+import audiocodec_amd
+from audiocodec_amd import _lib
+from audiocodec_amd.codec import StreamingMDCT
+from conftest import ROOT
+
+from test_encode_cbr import _input
+from test_encode_packed_rows import CAP
+from test_encode_quantized_fused import _pcm, _same, _where
+
+gpu = pytest.mark.gpu
+N0 = 1024
+B0, K0 = 3, 7
+HEADER = os.path.join(ROOT, "include", "audiocodec_amd.h")
+CHUNKINGS = [(7,), (1,) * 7, (2, 3, 2), (4, 1, 2)]
+BUDGETS = [(1365, 0), (2730, -8), (320, 0), (CAP, 0)]           # (row_bits, min_offset)
+ENC_NOFUSE, DEC_NOFUSE = "AC_ENCODE_PACKED_NOFUSE", "AC_DECODE_PACKED_NOFUSE"
+ELSEWHERE = [(1024, 64, 3, 1365), (2048, 64, 2, 1365), (960, 64, 2, 1365), (1024, 32, 2, 1365), (1024, 64, 2, CAP + 32)]
+
+
+# ---- CPU: header, library, Python validation -----------------------------------------------------------------------
+def test_header_declares_the_format_the_struct_and_the_launch_query():
+    text = open(HEADER).read()
+    assert re.search(r"\benum\s*\{\s*AC_PACKED\s*=\s*16\s*\}", text)
+    m = re.search(r"typedef\s+struct\s+ac_stream_packed_in\s*\{(.*?)\}\s*ac_stream_packed_in\s*;", text, flags=re.S)
+    assert m, "ac_stream_packed_in is not declared"
+    body = re.sub(r"/\*.*?\*/", " ", m.group(1), flags=re.S)
+    fields = [" ".join(f.split()) for f in body.split(";") if f.strip()]
+    assert fields == ["ac_packed_rows rows", "const ac_psy_plan* psy", "int32_t pcm16"], fields
+    m = re.search(r"AC_API\s+int\s+ac_stream_packed_launches\s*\(([^;]*)\)\s*;", text)
+    assert m and "stream" not in m.group(1).replace("ac_stream", ""), m and m.group(1)
+    assert " ".join(m.group(1).split()) == "const ac_stream* s, const ac_psy_plan* psy, int decode"
+    assert re.search(r"#define\s+AC_VERSION\s+171\b", text)
+
+
+def test_ctypes_mirror_has_the_headers_layout():
+    P = _lib.StreamPackedIn
+    assert [f[0] for f in P._fields_] == ["rows", "psy", "pcm16"]
+    assert (P.rows.offset, P.psy.offset, P.pcm16.offset) == (0, 24, 32) and ctypes.sizeof(P) == 40
+    assert P.rows.size == ctypes.sizeof(_lib.PackedRows) == 24 and P.psy.size == 8 and P.pcm16.size == 4
+    assert _lib.AC_PACKED == 16
+
+
+def test_library_exports_the_launch_query_and_keeps_its_version():
+    lib = _lib.load()
+    assert "ac_stream_packed_launches" in _lib.PROTOTYPES
+    assert lib.ac_stream_packed_launches(None, None, 0) == 0 and lib.ac_stream_packed_launches(None, None, 1) == 0
+    assert lib.ac_version() == 171
+
+
+def test_sixteen_stays_no_dtype_elsewhere():
+    lib = _lib.load()
+    assert lib.ac_mdct_forward_typed(None, None, None, 16, 1, 1, 1, None) == _lib.AC_EINVAL
+    assert b"dtype = 16" in lib.ac_last_error()
+    for fn, args in (("ac_mdct_inverse_typed", (None, None, None, 16, 1, 1, 1, None)),
+                     ("ac_tonality_typed", (None, None, None, 16, 1, 1, 1, None)),
+                     ("ac_encode_fused_typed", (None, None, None, None, None, None, 0.0, 16, 1, 1, 1, None)),
+                     ("ac_amplitude_to_db_typed", (None, None, 0, 0, 16, None))):
+        assert getattr(lib, fn)(*args) == _lib.AC_EINVAL, fn
+    # under AC_PACKED the two stream calls check their own arguments: no stream object, no call
+    assert lib.ac_stream_encode_typed(None, None, None, None, None, None, 0.0, 16, 1, None) == _lib.AC_EINVAL
+    assert b"stream is NULL" in lib.ac_last_error()
+    assert lib.ac_stream_inverse_typed(None, None, None, 16, 1, None) == _lib.AC_EINVAL
+    assert b"stream is NULL" in lib.ac_last_error()
+
+
+def _hostless(codec):
+    """A StreamingMDCT without its native state (which needs a device): what the argument checks run on."""
+    st = object.__new__(StreamingMDCT)
+    st.mdct, st.psy, st.B, st.C = codec.mdct, codec.psy, 1, 2
+    st.device, st._lib, st._handle, st._graphs = torch.device("cuda", 0), _lib.load(), None, {}
+    return st
+
+
+def test_python_interface_validates_its_arguments():
+    for name in ("encode_packed_rows_chunk", "decode_packed_chunk", "packed_chunk_launches"):
+        assert callable(getattr(StreamingMDCT, name, None)), name
+    base = audiocodec_amd.AudioCodec(48000, N0)
+    x = torch.zeros(1, N0, 2)
+    data, index = torch.zeros(8, dtype=torch.uint8), torch.zeros((1, 1, 2), dtype=torch.int64)
+    bare = _hostless(base)
+    bare.psy = None
+    for call in (lambda: bare.encode_packed_rows_chunk(x), lambda: bare.decode_packed_chunk(data, index),
+                 lambda: bare.packed_chunk_launches()):
+        with pytest.raises(ValueError, match="masking model"):
+            call()
+    nobudget = _hostless(base)
+    assert nobudget.row_bytes is None
+    with pytest.raises(ValueError, match=r"with_bitrate\(\)"):
+        nobudget.encode_packed_rows_chunk(x)
+    assert _hostless(base.with_bitrate(64000)).row_bytes == 172 and _hostless(base.with_row_budget(320)).row_bytes == 40
+    f64 = _hostless(audiocodec_amd.AudioCodec(48000, N0, compute_dtype=torch.float64))
+    for call in (lambda: f64.encode_packed_rows_chunk(x.double()), lambda: f64.decode_packed_chunk(data, index),
+                 lambda: f64.packed_chunk_launches()):
+        with pytest.raises(NotImplementedError, match="float32"):
+            call()
+
+
+# ---- GPU: shared references (computed once, never modified) ---------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _built():
+    """(CMODE, SPREAD) of the k_fwd_fast_qps instances the library holds -- the ones that passed the register gate -- from
+    the kernel names in the library file (its code objects' symbols and the host side's registration strings)."""
+    with open(_lib.LIB_PATH, "rb") as f:
+        names = re.findall(rb"14k_fwd_fast_qpsILi(\d)ELi(\d)E", f.read())
+    return {(int(c), int(sp)) for c, sp in names}
+
+
+def _gate_passed(codec, C):
+    spread = codec.psy.SPREADING[codec.psy.plan_spreading()]
+    return ((0 if C == 2 else 2), spread) in _built()
+
+
+@functools.lru_cache(maxsize=None)
+def _codec(spreading, R, kmin, N=N0, M=64):
+    return audiocodec_amd.AudioCodec(48000, N, bark_bands_n=M, spreading=spreading).with_row_budget(R, kmin)
+
+
+@functools.lru_cache(maxsize=None)
+def _x(C, K=K0, N=N0):
+    return _input(C, B0, K, C + 2 * B0 + K, True, N=N)
+
+
+@functools.lru_cache(maxsize=None)
+def _oneshot(C, spreading, R, kmin, N=N0, M=64):
+    """(rows uint8 [B, K+1, C, row_bytes], fits [B, K+1, C], data, index) of the one-shot encode of _x(C)."""
+    cbr = _codec(spreading, R, kmin, N, M)
+    data, index, fits = cbr.encode_packed_rows(_x(C, N=N))
+    return data.view(B0, K0 + 1, C, cbr.row_bytes), fits, data, index
+
+
+class _env:
+    """An environment switch that the library reads per call, set around a block; what was there before comes back."""
+
+    def __init__(self, name, on=True):
+        self.name, self.on = name, on
+
+    def __enter__(self):
+        self.before = os.environ.get(self.name)
+        if self.on:
+            os.environ[self.name] = "1"
+
+    def __exit__(self, *exc):
+        if self.on:
+            if self.before is None:
+                del os.environ[self.name]
+            else:
+                os.environ[self.name] = self.before
+        return False
+
+
+def _bounds(chunks):
+    out, a = [], 0
+    for k in chunks:
+        out.append((a, a + k))
+        a += k
+    return out
+
+
+def _encode_chunks(st, x, chunks, flush=True):
+    """The chunks' rows [B, sum(k) (+1), C, row_bytes] and fits; ``flush``: one further chunk of a zero block (frame K)."""
+    N, C, rb = st.mdct.filters_n, x.shape[2], st.row_bytes
+    parts = [x[:, a * N:b * N] for a, b in _bounds(chunks)] + ([torch.zeros_like(x[:, :N])] if flush else [])
+    rows, fits = [], []
+    for part in parts:
+        k = part.shape[1] // N
+        d, i, f = st.encode_packed_rows_chunk(part)
+        assert d.dtype == torch.uint8 and d.shape == (B0 * k * C * rb,) and f.dtype == torch.bool and f.shape == (B0, k, C)
+        assert i.dtype == torch.int64 and torch.equal(i.flatten().cpu(), torch.arange(B0 * k * C, dtype=torch.int64) * rb)
+        rows.append(d.view(B0, k, C, rb))
+        fits.append(f)
+    return torch.cat(rows, dim=1), torch.cat(fits, dim=1)
+
+
+def _decode_chunks(st, data, index, chunks, pcm16):
+    return torch.cat([st.decode_packed_chunk(data, index[:, a:b].contiguous(), pcm16=pcm16) for a, b in _bounds(chunks)], dim=1)
+
+
+# ---- 1. chunked encode equals one-shot -------------------------------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("spreading", [None, "f32"])
+@pytest.mark.parametrize("C", [1, 2])
+def test_chunked_encode_equals_one_shot(C, spreading):
+    x = _x(C)
+    for R, kmin in BUDGETS:
+        cbr = _codec(spreading, R, kmin)
+        ref_rows, ref_fits, _, _ = _oneshot(C, spreading, R, kmin)
+        _, _, off, bits = cbr.encode_quantized_budget(x, R, kmin)
+        print("R=%d kmin=%d: %d rows, %d do not fit, %d fitting above kmin" % (
+            R, kmin, ref_fits.numel(), int((~ref_fits).sum()), int((ref_fits & (off > kmin)).sum())))
+        if R in (1365, 320):                                     # the budget binds, on the reference alone
+            assert int((~ref_fits).sum()) >= 1, "no row that does not fit"
+            assert int((ref_fits & (off > kmin)).sum()) >= 1, "no fitting row above min_offset"
+        one = _gate_passed(cbr, C)
+        for chunks in CHUNKINGS:
+            # every boundary at a block > 0 matters: a fresh stream gives other rows for the boundary frame.  (Not at 320 bits:
+            # there a row holds its 64 width fields and nothing else -- all zero, or all 31 in a marked row -- and the one
+            # marked row, frame 4 with the 3e12 sample under the window's peak, has that sample in its own chunk at every
+            # boundary; the other three budgets show the state at the same boundaries.)
+            for a, b in _bounds(chunks)[1:]:
+                if R > 5 * 64:
+                    fresh = cbr.stream(B0, C)
+                    d, _, _ = fresh.encode_packed_rows_chunk(x[:, a * N0:b * N0])
+                    assert not torch.equal(d.view(B0, b - a, C, -1)[:, 0], ref_rows[:, a]), (R, chunks, a)
+            st = cbr.stream(B0, C)
+            assert st.packed_chunk_launches() == (1 if one else cbr.encode_launches(C) + 2), (C, spreading, R)
+            rows, fits = _encode_chunks(st, x, chunks)
+            assert torch.equal(fits, ref_fits), (R, kmin, chunks, _where(fits, ref_fits))
+            assert torch.equal(rows, ref_rows), (R, kmin, chunks, _where(rows, ref_rows))
+            with _env(ENC_NOFUSE):                               # the composition: the same bytes
+                st = cbr.stream(B0, C)
+                assert st.packed_chunk_launches() == cbr.encode_launches(C) + 2 == 3
+                rows, fits = _encode_chunks(st, x, chunks)
+            assert torch.equal(fits, ref_fits), (R, kmin, chunks, "composition", _where(fits, ref_fits))
+            assert torch.equal(rows, ref_rows), (R, kmin, chunks, "composition", _where(rows, ref_rows))
+
+
+@gpu
+def test_some_instance_runs_in_one_launch():
+    """The gate left at least the default stereo and mono forms: the one launch is what the tests above held to the one-shot."""
+    assert _built(), "no k_fwd_fast_qps instance in the library"
+    for C in (1, 2):
+        cbr = _codec(None, 1365, 0)
+        assert _gate_passed(cbr, C) and cbr.stream(B0, C).packed_chunk_launches() == 1
+        assert cbr.stream(B0, C).packed_chunk_launches(decode=True) == 1
+    assert audiocodec_amd.AudioCodec(48000, N0).stream(1, 2).packed_chunk_launches() == 0          # no budget
+    assert audiocodec_amd.AudioCodec(48000, N0).stream(1, 2).packed_chunk_launches(decode=True) == 1
+
+
+# ---- 2. the state is shared with the other chunk calls ----------------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("C", [1, 2])
+def test_state_is_shared(C):
+    cbr = _codec(None, 1365, 0)
+    x = _x(C)
+    ref_rows, ref_fits, _, _ = _oneshot(C, None, 1365, 0)
+    X, t, thr = cbr.encode(x)
+    st = cbr.stream(B0, C)
+    assert st.packed_chunk_launches() == 1
+
+    def spectra(a, b):
+        got = st.encode_chunk(x[:, a * N0:b * N0])
+        for g, r in zip(got, (X, t, thr)):
+            assert _same(g, r[:, a:b].contiguous()), (a, b, _where(g, r[:, a:b].contiguous()))
+
+    def rows(a, b):
+        d, _, f = st.encode_packed_rows_chunk(x[:, a * N0:b * N0])
+        assert torch.equal(f, ref_fits[:, a:b]) and torch.equal(d.view(B0, b - a, C, -1), ref_rows[:, a:b]), (a, b)
+
+    spectra(0, 2)
+    rows(2, 5)                 # block 4 (the 3e12 sample) becomes the state
+    spectra(5, 7)
+    st.reset()                 # the zero state again
+    rows(0, 3)
+    spectra(3, 4)
+    # a captured run() after a packed chunk call: ac_stream_settle finds the state the packed call left
+    one = cbr.stream(1, C)
+    x1 = x[:1].contiguous()
+    X1, t1, thr1 = cbr.encode(x1)
+    d, _, _ = one.encode_packed_rows_chunk(x1[:, :3 * N0])
+    rest = x1[:, 3 * N0:].contiguous()
+    for _ in range(2):         # the capture, then a replay from a state that is not at home
+        Xr, tr, thrr, _ = one.run(rest, 2, synthesis=False, graph=True)
+        torch.cuda.synchronize()
+        for g, r in zip((Xr, tr, thrr), (X1, t1, thr1)):
+            assert _same(g, r[:, 3:K0].contiguous()), _where(g, r[:, 3:K0].contiguous())
+        one.reset()
+        one.encode_packed_rows_chunk(x1[:, :3 * N0])
+
+
+# ---- 3. chunked decode equals one-shot ---------------------------------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("pcm16", [False, True])
+@pytest.mark.parametrize("C", [1, 2])
+def test_chunked_decode_equals_one_shot(C, pcm16):
+    # (at 320 bits nearly every row decodes to silence, no boundary would show: that budget is decoded below, without the
+    # precondition)
+    for R, kmin in BUDGETS:
+        cbr = _codec(None, R, kmin)
+        _, _, data, index = _oneshot(C, None, R, kmin)
+        index = index[:, :K0].contiguous()
+        ref = cbr.decode_packed(data, index, pcm16)[:, :K0 * N0]
+        assert ref.dtype == (torch.int16 if pcm16 else torch.float32) and (R == 320 or int((ref != 0).sum()) > 0)
+        for chunks in CHUNKINGS:
+            # the tail matters at every boundary: a fresh stream decodes another block there.  (Not in mono at blocks 3 and 4,
+            # by the input alone: the NaN at 2N + 17 of clip 0 sits in frames 2 and 3, the Inf at 3N + 5 of clip 2 in frames 3
+            # and 4, the 1e15 and 3e12 samples at 4N + 9 of clips 1 and 0 in frame 4 -- blocks that are NaN with any tail --
+            # and clip 1's frame 2 is the all-zero frame, a zero tail for block 3.  In stereo clip 0's second channel shows.)
+            for a, b in _bounds(chunks)[1:]:
+                if R > 5 * 64 and (C == 2 or a not in (3, 4)):
+                    fresh = cbr.stream(B0, C).decode_packed_chunk(data, index[:, a:b].contiguous(), pcm16=pcm16)
+                    assert not _same(fresh[:, :N0], ref[:, a * N0:(a + 1) * N0].contiguous()), (chunks, a)
+            st = cbr.stream(B0, C)
+            assert st.packed_chunk_launches(decode=True) == 1
+            got = _decode_chunks(st, data, index, chunks, pcm16)
+            assert _same(got, ref), (R, chunks, _where(got, ref))
+            with _env(DEC_NOFUSE):
+                st = cbr.stream(B0, C)
+                assert st.packed_chunk_launches(decode=True) == 3
+                got = _decode_chunks(st, data, index, chunks, pcm16)
+            assert _same(got, ref), (R, chunks, "composition", _where(got, ref))
+
+
+@gpu
+@pytest.mark.parametrize("pcm16", [False, True])
+@pytest.mark.parametrize("C", [1, 2])
+def test_decode_of_a_long_chunk_and_of_row_starts_outside_data(C, pcm16):
+    cbr = _codec(None, 1365, 0)
+    K = 40
+    x = _pcm(N0, C, B0, K, seed=90 + C, inject=True)
+    data, index, _ = cbr.encode_packed_rows(x)
+    index = index[:, :K].clone()
+    index[0, 3, 0] = -1                                          # reads as psy.unpack reads it
+    index[2, 5, C - 1] = data.numel() + 64
+    index[1, 9, 0] = data.numel() - 8                            # a row that runs off the end of data
+    ref = cbr.decode_packed(data, index, pcm16)[:, :K * N0]
+    st = cbr.stream(B0, C)
+    got = st.decode_packed_chunk(data, index, pcm16=pcm16)       # one chunk of 40 blocks
+    assert _same(got, ref), _where(got, ref)
+    comp = cbr.stream(B0, C)
+    codes, sf = cbr.psy.unpack(data, index)
+    xf = comp.inverse_chunk(cbr.psy.dequantize(codes, sf))
+    if pcm16:
+        xf = torch.nan_to_num(xf * 32768.0, nan=0.0).round().clamp(-32768, 32767).to(torch.int16)
+    assert _same(got, xf), _where(got, xf)
+    with _env(DEC_NOFUSE):
+        st = cbr.stream(B0, C)
+        got = torch.cat([st.decode_packed_chunk(data, index[:, :25].contiguous(), pcm16=pcm16),
+                         st.decode_packed_chunk(data, index[:, 25:].contiguous(), pcm16=pcm16)], dim=1)
+    assert _same(got, ref), _where(got, ref)
+    out = torch.empty_like(ref)
+    st = cbr.stream(B0, C)
+    assert st.decode_packed_chunk(data, index, pcm16=pcm16, out=out) is out and _same(out, ref)
+
+
+@gpu
+@pytest.mark.parametrize("C,B,chunks", [(2, 136, (33, 31)), (1, 265, (47, 49))])
+def test_decode_with_several_blocks_per_strip(C, B, chunks):
+    """The strips of the bench workload -- 2 blocks (stereo), 3 (mono) -- with the stream's tails live.  The synthesis takes
+    them once a launch has 2 x 4 waves x 256 CUs = 2048 strips: stereo 136 pairs x ceil(33 / 2) = 2312 and x ceil(31 / 2) =
+    2176, the last strip one block; mono 133 pairs (one half empty) x ceil(47 / 3) = 2128, the last strip two blocks, and x
+    ceil(49 / 3) = 2261, the last strip one.  The second chunk starts from the tail the first one wrote.  Clean input (seeded
+    noise with a rising envelope), so the tail shows in every signal: asserted on the reference before comparing."""
+    cbr = _codec(None, 1365, 0)
+    K = sum(chunks)
+    g = torch.Generator("cuda").manual_seed(B + K)
+    x = (torch.rand((B, K * N0, C), device="cuda", generator=g) * 2 - 1) * torch.linspace(0.01, 1, K * N0, device="cuda")[None, :, None]
+    data, index, fits = cbr.encode_packed_rows(x)
+    assert bool(fits.all())
+    del x
+    index = index[:, :K].contiguous()
+    parts = [index[:, a:b].contiguous() for a, b in _bounds(chunks)]
+    pairs = B if C == 2 else (B + 1) // 2
+    assert all(pairs * ((k + (4 - C) - 1) // (4 - C)) >= 2048 for k in chunks)
+    xf = None
+    for pcm16 in (False, True):
+        ref = cbr.decode_packed(data, index, pcm16)[:, :K * N0]
+        a = chunks[0]
+        fresh = cbr.stream(B, C).decode_packed_chunk(data, parts[1], pcm16=pcm16)[:, :N0]
+        differs = (fresh != ref[:, a * N0:(a + 1) * N0]).flatten(1).any(dim=1)
+        assert bool(differs.all()), "the tail does not show in every clip"
+        st = cbr.stream(B, C)
+        assert st.packed_chunk_launches(decode=True) == 1
+        got = torch.cat([st.decode_packed_chunk(data, i, pcm16=pcm16) for i in parts], dim=1)
+        assert _same(got, ref), (pcm16, _where(got, ref))
+        if xf is None:                                           # the composition, chunk by chunk on a stream of its own
+            comp = cbr.stream(B, C)
+            xf = torch.cat([comp.inverse_chunk(cbr.psy.dequantize(*cbr.psy.unpack(data, i))) for i in parts], dim=1)
+        want = torch.nan_to_num(xf * 32768.0, nan=0.0).round().clamp(-32768, 32767).to(torch.int16) if pcm16 else xf
+        assert _same(got, want), (pcm16, "composition", _where(got, want))
+        with _env(DEC_NOFUSE):
+            st = cbr.stream(B, C)
+            assert st.packed_chunk_launches(decode=True) == 3
+            got = torch.cat([st.decode_packed_chunk(data, i, pcm16=pcm16) for i in parts], dim=1)
+        assert _same(got, ref), (pcm16, "NOFUSE", _where(got, ref))
+
+
+# ---- 4. round trip through both ----------------------------------------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("C", [1, 2])
+def test_round_trip(C):
+    cbr = _codec(None, 1365, 0)
+    x = _x(C)
+    _, _, data, index = _oneshot(C, None, 1365, 0)
+    enc, dec = cbr.stream(B0, C), cbr.stream(B0, C)
+    for pcm16 in (False, True):
+        ref = cbr.decode_packed(data, index, pcm16)[:, :K0 * N0]
+        enc.reset()
+        dec.reset()
+        got = []
+        for a, b in _bounds((2, 3, 2)):
+            d, i, _ = enc.encode_packed_rows_chunk(x[:, a * N0:b * N0])
+            got.append(dec.decode_packed_chunk(d, i, pcm16=pcm16))
+        got = torch.cat(got, dim=1)
+        assert _same(got, ref), (pcm16, _where(got, ref))
+
+
+# ---- 5. the composition elsewhere ---------------------------------------------------------------------------------------
+def _c_encode(st, psy, x, k, rb):
+    lib = _lib.load()
+    data = torch.full((st.B * k * st.C * rb,), 0xA5, dtype=torch.uint8, device=x.device)
+    fits = torch.full((st.B * k * st.C,), 7, dtype=torch.uint8, device=x.device)
+    out = _lib.PackedOut(data.data_ptr(), rb, fits.data_ptr())
+    status = lib.ac_stream_encode_typed(st._handle, psy, ctypes.c_void_p(x.data_ptr()), ctypes.addressof(out), None, None, 0.0,
+                                        _lib.AC_PACKED, k, None)
+    torch.cuda.synchronize()
+    return status, data, fits
+
+
+def _c_decode(st, psy, data, index, k, N, pcm16=0):
+    lib = _lib.load()
+    x = torch.full((st.B, k * N, st.C), 7.0, device=data.device)
+    rows = _lib.StreamPackedIn(_lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr()), psy.value if psy else None, pcm16)
+    status = lib.ac_stream_inverse_typed(st._handle, ctypes.addressof(rows), ctypes.c_void_p(x.data_ptr()), _lib.AC_PACKED, k, None)
+    torch.cuda.synchronize()
+    return status, x
+
+
+@gpu
+@pytest.mark.parametrize("N,M,C,R", ELSEWHERE)
+def test_composition_elsewhere(N, M, C, R):
+    lib = _lib.load()
+    cbr = _codec(None, R, 0, N, M)
+    x = _x(C, N=N)
+    ref_rows, ref_fits, data, index = _oneshot(C, None, R, 0, N, M)
+    st = cbr.stream(B0, C)
+    assert st.packed_chunk_launches() == cbr.encode_launches(C) + 2 > 1
+    rows, fits = _encode_chunks(st, x, (2, 3, 2))
+    assert torch.equal(fits, ref_fits), _where(fits, ref_fits)
+    assert torch.equal(rows, ref_rows), _where(rows, ref_rows)
+    psy = cbr.psy._plan(x.device)
+    index = index[:, :K0].contiguous()
+    one_launch_decode = (N, M) == (1024, 64) and C <= 2
+    dec = cbr.stream(B0, C)
+    assert dec.packed_chunk_launches(decode=True) == (1 if one_launch_decode else 3)
+    ref = cbr.decode_packed(data, index)[:, :K0 * N].contiguous()
+    got = _decode_chunks(dec, data, index, (2, 3, 2), False)
+    assert _same(got, ref), _where(got, ref)
+    # 16-bit PCM: the stated store on the float32 result ...
+    dec.reset()
+    got = _decode_chunks(dec, data, index, (2, 3, 2), True)
+    want = torch.nan_to_num(ref * 32768.0, nan=0.0).round().clamp(-32768, 32767).to(torch.int16)
+    assert _same(got, want), _where(got, want)
+    # ... which is the one-shot call's 16-bit PCM wherever that runs the float32 synthesis' arithmetic.  With three channels at
+    # filters_n = 1024 it does not: float32 tensors take the channel-pair kernels of the LDS-FFT tier, 16-bit PCM the wave-level
+    # strided ones (wave_level() in ac_api.hip), and the two round differently in a few samples.
+    if C <= 2:
+        ref16 = cbr.decode_packed(data, index, True)[:, :K0 * N]
+        assert _same(got, ref16), _where(got, ref16)
+    # the C entry points refuse, naming the composition, and leave the state as it was
+    X, t, thr = cbr.encode(x)
+    st.reset()
+    st.encode_chunk(x[:, :2 * N])
+    status, d, f = _c_encode(st, psy, x[:, 2 * N:4 * N].contiguous(), 2, cbr.row_bytes)
+    assert status == _lib.AC_EUNSUPPORTED and b"composition" in lib.ac_last_error()
+    assert int(d.min()) == 0xA5 == int(d.max()) and int(f.min()) == 7 == int(f.max())
+    got = st.encode_chunk(x[:, 2 * N:3 * N])
+    for g, r in zip(got, (X, t, thr)):
+        assert _same(g, r[:, 2:3].contiguous()), _where(g, r[:, 2:3].contiguous())
+    if not one_launch_decode:
+        dec.reset()
+        first = dec.decode_packed_chunk(data, index[:, :2].contiguous())
+        status, xo = _c_decode(dec, psy, data, index[:, 2:4].contiguous(), 2, N)
+        assert status == _lib.AC_EUNSUPPORTED and b"composition" in lib.ac_last_error()
+        assert int((xo != 7.0).sum()) == 0
+        ref = cbr.decode_packed(data, index)[:, :4 * N]
+        got = torch.cat([first, dec.decode_packed_chunk(data, index[:, 2:4].contiguous())], dim=1)
+        assert _same(got, ref), _where(got, ref)
+
+
+@gpu
+def test_c_abi():
+    lib = _lib.load()
+    base = audiocodec_amd.AudioCodec(48000, N0)
+    cbr = _codec(None, 1365, 0)
+    C = 2
+    x = _x(C)
+    ref_rows, ref_fits, data, index = _oneshot(C, None, 1365, 0)
+    psy, rb = cbr.psy._plan(x.device), cbr.row_bytes
+    st = cbr.stream(B0, C)
+    first = x[:, :2 * N0].contiguous()
+    status, d, f = _c_encode(st, psy, first, 2, rb)
+    assert status == _lib.AC_OK, lib.ac_last_error()
+    assert torch.equal(d.view(B0, 2, C, rb), ref_rows[:, :2]) and torch.equal(f.view(B0, 2, C), ref_fits[:, :2].to(torch.uint8))
+    # refused calls leave the state: the next chunk still continues the signal
+    assert _c_encode(st, psy, first, 2, rb + 4)[0] == _lib.AC_EINVAL and b"row_bytes" in lib.ac_last_error()
+    assert _c_encode(st, base.psy._plan(x.device), first, 2, rb)[0] == _lib.AC_EINVAL and b"row budget" in lib.ac_last_error()
+    assert _c_encode(st, None, first, 2, rb)[0] == _lib.AC_EINVAL
+    spare = torch.zeros((B0, 2, N0, C), device=x.device)
+    out = _lib.PackedOut(d.data_ptr(), rb, f.data_ptr())
+    for t_, thr_ in ((spare, None), (None, spare)):
+        p = lambda v: ctypes.c_void_p(v.data_ptr()) if v is not None else None   # noqa: E731
+        assert lib.ac_stream_encode_typed(st._handle, psy, p(first), ctypes.addressof(out), p(t_), p(thr_), 0.0, _lib.AC_PACKED,
+                                          2, None) == _lib.AC_EINVAL
+    assert lib.ac_stream_encode_typed(st._handle, psy, None, ctypes.addressof(out), None, None, 0.0, _lib.AC_PACKED, 0,
+                                      None) == _lib.AC_OK                     # k == 0
+    status, d, f = _c_encode(st, psy, x[:, 2 * N0:5 * N0].contiguous(), 3, rb)
+    assert status == _lib.AC_OK and torch.equal(d.view(B0, 3, C, rb), ref_rows[:, 2:5])
+    # the decoder
+    dec = cbr.stream(B0, C)
+    index = index[:, :K0].contiguous()
+    ref = cbr.decode_packed(data, index)[:, :K0 * N0]
+    status, xo = _c_decode(dec, psy, data, index[:, :3].contiguous(), 3, N0)
+    assert status == _lib.AC_OK and _same(xo, ref[:, :3 * N0].contiguous())
+    assert _c_decode(dec, None, data, index[:, 3:5].contiguous(), 2, N0)[0] == _lib.AC_EINVAL
+    assert _c_decode(dec, psy, data, index[:, 3:5].contiguous(), 2, N0, pcm16=2)[0] == _lib.AC_EINVAL
+    assert _c_decode(dec, psy, data, index, 0, N0)[0] == _lib.AC_OK
+    status, xo = _c_decode(dec, psy, data, index[:, 3:].contiguous(), 4, N0)
+    assert status == _lib.AC_OK and _same(xo, ref[:, 3 * N0:].contiguous()), _where(xo, ref[:, 3 * N0:].contiguous())
+
+
+@gpu
+def test_python_interface_validates_tensors():
+    cbr = _codec(None, 1365, 0)
+    st = cbr.stream(2, 2)
+    good = torch.zeros((2, 2 * N0, 2), device="cuda")
+    for bad in (torch.zeros((3, 2 * N0, 2), device="cuda"), torch.zeros((2, 2 * N0, 1), device="cuda"),
+                torch.zeros((2, N0 + 8, 2), device="cuda"), torch.zeros((2, 2 * N0), device="cuda"), good.double()):
+        with pytest.raises(ValueError):
+            st.encode_packed_rows_chunk(bad)
+    with pytest.raises(ValueError, match="gradient"):
+        st.encode_packed_rows_chunk(good.clone().requires_grad_())
+    with pytest.raises(RuntimeError):
+        st.encode_packed_rows_chunk(good.cpu())
+    data, index, _ = st.encode_packed_rows_chunk(good)
+    for d, i in ((data, index[:1].contiguous()), (data, index[:, :, :1].contiguous()), (data.view(2, -1), index),
+                 (data, index.to(torch.int32)), (data.to(torch.int16), index), (data.cpu(), index.cpu())):
+        with pytest.raises(ValueError):
+            st.decode_packed_chunk(d, i)
+    with pytest.raises(ValueError):
+        st.decode_packed_chunk(data, index, out=torch.empty((2, 2 * N0, 2), dtype=torch.int16, device="cuda"))
+    empty = st.encode_packed_rows_chunk(good[:, :0])
+    assert empty[0].shape == (0,) and empty[1].shape == (2, 0, 2) and empty[2].shape == (2, 0, 2)
+    assert st.decode_packed_chunk(data, index[:, :0].contiguous()).shape == (2, 0, 2)
+
+
+# ---- 6. the stream contract -----------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def harness():
+    from stream_order import Harness
+    return Harness()
+
+
+@gpu
+@pytest.mark.parametrize("how", ["stream=", "current"])
+@pytest.mark.parametrize("route", ["one_launch", "composition"])
+@pytest.mark.parametrize("check", ["delayed_producer", "busy_default"])
+def test_stream_contract(harness, check, route, how):
+    """Both methods only enqueue, on ``stream=`` or on the current side stream, on both routes.  The case resets the stream's
+    state on the stream it runs on, so every call of it computes the same thing."""
+    cbr = _codec(None, 1365, 0)
+    st = cbr.stream(1, 2)
+    assert st.packed_chunk_launches() == 1 and st.packed_chunk_launches(decode=True) == 1
+    x = _pcm(N0, 2, 1, 20, seed=78, inject=False)
+    data, index, _ = cbr.stream(1, 2).encode_packed_rows_chunk(x)
+    torch.cuda.synchronize()
+    switch = route == "composition"
+
+    other = torch.cuda.Stream()
+
+    def on(call):
+        """``current``: the method takes the current stream; ``stream=``: it is given that stream while ANOTHER one is current."""
+        st.reset()                                               # (on the stream the case runs on)
+        if how == "current":
+            return call(None)
+        s = torch.cuda.current_stream()
+        with torch.cuda.stream(other):
+            return call(s)
+
+    def enc(x):
+        with _env(ENC_NOFUSE, switch):
+            return on(lambda s: st.encode_packed_rows_chunk(x, stream=s))
+
+    def dec(data, index):
+        with _env(DEC_NOFUSE, switch):
+            return on(lambda s: (st.decode_packed_chunk(data, index, stream=s),
+                                 st.decode_packed_chunk(data, index, pcm16=True, stream=s)))
+
+    getattr(harness, check)("st.encode_packed_rows_chunk[%s,%s]" % (route, how), ([x], enc))
+    getattr(harness, check)("st.decode_packed_chunk[%s,%s]" % (route, how), ([data, index], dec))

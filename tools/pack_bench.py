@@ -7,8 +7,12 @@ k_inv_fast_p and unpack + decode_quantized (AC_DECODE_PACKED_NOFUSE=1, read per 
 outputs are compared bit for bit first.  Last, at a row budget: encode_packed, encode_packed_rows in its two forms (the one
 launch of k_fwd_fast_qp; AC_ENCODE_PACKED_NOFUSE=1: the composition) and encode_quantized, alternating the same way
 (packed_rows(); --only-rows runs this section alone).
+--stream: packed rows chunk by chunk on a StreamingMDCT (stream_rows()): the chain of public calls a caller had before the
+chunk methods existed -- encode_chunk, quantize_to_budget, the mask, ac_pack; unpack, dequantize, inverse_chunk -- against
+encode_packed_rows_chunk / decode_packed_chunk where the package has them, so the same script times the baseline on an older
+commit.  Two workloads: one stereo clip in chunks of 256 blocks (per-chunk latency) and --clips x --blocks as one chunk.
 python tools/pack_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7] [--round-steps 30]
-                           [--row-bits 1365] [--only-rows]"""
+                           [--row-bits 1365] [--only-rows] [--stream]"""
 import argparse
 import ctypes
 import os
@@ -74,8 +78,77 @@ def packed_rows(a):
     print("(c) / (b) = %.3f   (c) / (a) = %.3f   (c) / (d) = %.3f" % (med[2] / med[1], med[2] / med[0], med[2] / med[3]))
 
 
+def stream_rows(a):
+    """Packed rows in a stream: per workload the chain of older public calls and, where the package has
+    them, the chunk methods; forms alternating, --rounds rounds of --round-steps passes over the workload's chunks."""
+    N, C, lib = a.filters, a.channels, _lib.load()
+    cbr = audiocodec_amd.AudioCodec(48000, N).with_row_budget(a.row_bits)
+    rb, psy = (a.row_bits + 31) // 32 * 4, cbr.psy
+    kmin = psy.row_budget[1]
+    new = hasattr(audiocodec_amd.codec.StreamingMDCT, "encode_packed_rows_chunk")
+    for name, B, k, n in (("one clip, chunks of 256 blocks", 1, 256, 8), ("%d clips x %d blocks, one chunk" % (a.clips, a.blocks), a.clips, a.blocks, 1)):
+        g = torch.Generator("cuda").manual_seed(1)
+        chunks = [torch.rand((B, k * N, C), device="cuda", generator=g) * 2 - 1 for _ in range(n)]
+        enc, dec = cbr.stream(B, C), cbr.stream(B, C)
+        index = (torch.arange(B * k * C, dtype=torch.int64, device="cuda") * rb).view(B, k, C)
+        plan = psy._plan(index.device)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
+
+        def chain_enc(x):
+            X, _, thr = enc.encode_chunk(x)
+            codes, sf, _, bits = psy.quantize_to_budget(X, thr, a.row_bits, kmin)
+            fits = bits <= 8 * rb
+            sf.masked_fill_(~fits.unsqueeze(2), -128)
+            data = torch.zeros((B * k * C * rb,), dtype=torch.uint8, device=x.device)
+            _lib.check(lib.ac_pack(plan, p(codes), p(sf), p(index), p(data), B, k, C,
+                                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            return data, fits
+
+        def chain_dec(data):
+            return dec.inverse_chunk(psy.dequantize(*psy.unpack(data, index)))
+
+        def chain_dec16(data):
+            return torch.nan_to_num(chain_dec(data) * 32768.0, nan=0.0).round_().clamp_(-32768.0, 32767.0).to(torch.int16)
+
+        packed = [chain_enc(x)[0] for x in chunks]
+        forms = [("encode: encode_chunk + quantize_to_budget + mask + ac_pack", lambda: [chain_enc(x) for x in chunks]),
+                 ("decode f32: unpack + dequantize + inverse_chunk", lambda: [chain_dec(d) for d in packed]),
+                 ("decode pcm16: the same + the 16-bit store in torch", lambda: [chain_dec16(d) for d in packed])]
+        launches = ""
+        if new:
+            enc.reset()
+            for x, d in zip(chunks, packed):
+                assert torch.equal(enc.encode_packed_rows_chunk(x)[0], d), "the chunk method and the chain differ"
+            dec.reset()
+            want = [chain_dec(d) for d in packed]
+            want16 = [torch.nan_to_num(w * 32768.0, nan=0.0).round_().clamp_(-32768.0, 32767.0).to(torch.int16) for w in want]
+            for pcm16, ws in ((False, want), (True, want16)):
+                dec.reset()
+                for d, w in zip(packed, ws):
+                    got = dec.decode_packed_chunk(d, index, pcm16=pcm16)
+                    assert got.dtype == w.dtype and torch.equal(got.view(torch.int16), w.view(torch.int16)), \
+                        "decode_packed_chunk and the chain differ (pcm16=%s)" % pcm16
+            del want, want16
+            forms += [("encode: encode_packed_rows_chunk", lambda: [enc.encode_packed_rows_chunk(x) for x in chunks]),
+                      ("decode f32: decode_packed_chunk", lambda: [dec.decode_packed_chunk(d, index) for d in packed]),
+                      ("decode pcm16: decode_packed_chunk", lambda: [dec.decode_packed_chunk(d, index, pcm16=True) for d in packed])]
+            launches = ("  launches: encode %d, decode %d; the chunk methods and the chain agree bit for bit (rows; float32 and 16-bit PCM)"
+                        % (enc.packed_chunk_launches(), dec.packed_chunk_launches(decode=True)))
+        print("stream rows: %s  (B=%d k=%d N=%d C=%d, %d chunks per pass, %d bits per row)%s"
+              % (name, B, k, N, C, n, a.row_bits, launches))
+        runs = dict((f, []) for f, _ in forms)
+        for _ in range(a.rounds):
+            for f, fn in forms:
+                runs[f].append(timed(fn, a.round_steps, 1) / n * 1e3)
+        for f, _ in forms:
+            v = sorted(runs[f])
+            print("  %-60s median %9.1f us per chunk  min %9.1f  max %9.1f  (%d alternating rounds of %d)"
+                  % (f, v[len(v) // 2], v[0], v[-1], len(v), a.round_steps))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--stream", action="store_true", help="only the packed rows of a stream, chunk by chunk")
     ap.add_argument("--row-bits", type=int, default=1365, help="the row budget of the packed-rows section (64 kbit/s)")
     ap.add_argument("--only-rows", action="store_true", help="only the packed-rows section")
     ap.add_argument("--clips", type=int, default=256)
@@ -88,6 +161,8 @@ def main():
     ap.add_argument("--round-steps", type=int, default=30)
     a = ap.parse_args()
     B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    if a.stream:
+        return stream_rows(a)
     if a.only_rows:
         return packed_rows(a)
     codec = audiocodec_amd.AudioCodec(48000, N)
