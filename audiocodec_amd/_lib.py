@@ -17,6 +17,8 @@ AC_OK = 0
 AC_EINVAL, AC_EHIP, AC_ENOMEM, AC_ENODEV, AC_EUNSUPPORTED = -1, -2, -3, -4, -5
 AC_EMIT_NOISY, AC_EMIT_DB_NORM, AC_EMIT_CODES, AC_EMIT_PACKED = 1, 2, 4, 8   # flags of ac_encode_fused_ex
 AC_PACKED = 16   # spectrum-side format of ac_stream_encode_typed / ac_stream_inverse_typed: packed rows
+AC_IN_PCM16 = 32   # x is int16 PCM: flag of ac_encode_fused_ex beside AC_EMIT_CODES / AC_EMIT_PACKED, and of
+                   # ac_stream_encode_typed's dtype beside AC_PACKED
 AC_PACK_ROWS_MAX_BITS = 16384   # the largest row budget AC_EMIT_PACKED serves in one launch (the header's macro)
 WINDOW_IDS = {"vorbis": 0, "sine": 1}   # anything else -> 2 (rectangular), mdctransformer.py:199-211
 WINDOW_RECT = 2
@@ -113,6 +115,9 @@ PROTOTYPES = {
     "ac_decode_packed_launches": (c_int, [c_void_p, c_void_p, c_int]),
     "ac_encode_packed_launches": (c_int, [c_void_p, c_void_p, c_int]),
     "ac_stream_packed_launches": (c_int, [c_void_p, c_void_p, c_int]),
+    "ac_encode_quantized_launches_pcm16": (c_int, [c_void_p, c_void_p, c_int]),
+    "ac_encode_packed_launches_pcm16": (c_int, [c_void_p, c_void_p, c_int]),
+    "ac_stream_packed_launches_pcm16": (c_int, [c_void_p, c_void_p]),
     "ac_pack_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ac_pack_index": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ac_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -230,25 +230,29 @@ class AudioCodec:
         X, _, thr = self.encode(x, drown)
         return X, thr
 
-    def encode_quantized_launches(self, channels_n=2, device=None):
+    def encode_quantized_launches(self, channels_n=2, device=None, *, pcm16=False):
         """Launches :meth:`encode_quantized` takes for float32 PCM of ``channels_n`` channels
         (``ac_encode_quantized_launches``): 1 = the fused encode quantises the frame in its registers (filters_n = 1024, mono /
-        stereo, spreading ``"f32"`` or ``"bf16x2_mfma"``), 2 = :meth:`encode`, then the quantiser."""
+        stereo, spreading ``"f32"`` or ``"bf16x2_mfma"``), 2 = :meth:`encode`, then the quantiser.  ``pcm16=True``: for
+        ``torch.int16`` PCM (``ac_encode_quantized_launches_pcm16``)."""
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        return int(self._lib.ac_encode_quantized_launches(self.mdct._plan(dev), self.psy._plan(dev), int(channels_n)))
+        query = self._lib.ac_encode_quantized_launches_pcm16 if pcm16 else self._lib.ac_encode_quantized_launches
+        return int(query(self.mdct._plan(dev), self.psy._plan(dev), int(channels_n)))
 
     def encode_quantized(self, x, drown=0.0):
         """:meth:`encode`, then :meth:`PsychoacousticModel.quantize` on its X and threshold: x [B, K*N, C] (float or
         ``torch.int16`` PCM) -> (codes int16 [B, K+1, N, C], sf int8 [B, K+1, M, C]).  One launch that writes only codes and
-        scale factors where :meth:`encode_quantized_launches` is 1 and ``x`` is float32 (``ac_encode_fused_ex`` with
-        ``AC_EMIT_CODES``: the same values, bit for bit); elsewhere two launches with X, tonality and threshold as
-        temporaries.  On a codec made by :meth:`with_row_budget` / :meth:`with_bitrate` the quantiser is
-        ``quantize_to_budget`` at the codec's budget, in the same number of launches.  float32 only, not differentiable."""
-        if (self.compute_dtype == torch.float32 and isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.is_cuda
-                and x.dim() == 3 and not (x.requires_grad and torch.is_grad_enabled())
+        scale factors where :meth:`encode_quantized_launches` is 1 for ``x``'s format -- asked with ``pcm16=True`` for
+        ``torch.int16`` (``ac_encode_fused_ex`` with ``AC_EMIT_CODES``, and ``AC_IN_PCM16`` for int16: the same values, bit
+        for bit); elsewhere two launches with X, tonality and threshold as temporaries.  On a codec made by
+        :meth:`with_row_budget` / :meth:`with_bitrate` the quantiser is ``quantize_to_budget`` at the codec's budget, in the
+        same number of launches.  float32 only, not differentiable."""
+        pcm16 = isinstance(x, torch.Tensor) and x.dtype == torch.int16
+        if (self.compute_dtype == torch.float32 and isinstance(x, torch.Tensor) and (pcm16 or x.dtype == torch.float32)
+                and x.is_cuda and x.dim() == 3 and not (x.requires_grad and torch.is_grad_enabled())
                 and x.shape[1] % self.filters_n == 0
-                and self.encode_quantized_launches(x.shape[2], x.device) == 1):
-            x = _host.check_device_tensor(x, "x", torch.float32, 3)
+                and self.encode_quantized_launches(x.shape[2], x.device, pcm16=pcm16) == 1):
+            x = _host.check_device_tensor(x, "x", x.dtype, 3)
             B, S, C = x.shape
             K = S // self.filters_n
             codes = torch.empty((B, K + 1, self.filters_n, C), dtype=torch.int16, device=x.device)
@@ -256,7 +260,8 @@ class AudioCodec:
             with _host.on_device(x.device):
                 _lib.check(self._lib.ac_encode_fused_ex(
                     self.mdct._plan(x.device), self.psy._plan(x.device), _host.ptr(x), None, None, None, float(drown),
-                    _lib.AC_EMIT_CODES, _host.ptr(codes), _host.ptr(sf), 0, B, K, C, _host.stream_ptr(x.device)))
+                    _lib.AC_EMIT_CODES | (_lib.AC_IN_PCM16 if pcm16 else 0), _host.ptr(codes), _host.ptr(sf), 0, B, K, C,
+                    _host.stream_ptr(x.device)))
             return codes, sf
         X, thr = self._encode_for_quantizer(x, drown, "encode_quantized")
         return self.psy.quantize(X, thr)
@@ -327,26 +332,30 @@ class AudioCodec:
         """Bytes of a row's slot in :meth:`encode_packed_rows`' data: ceil(row_bits / 32) * 4; None without a row budget."""
         return None if self.row_bits is None else (self.row_bits + 31) // 32 * 4
 
-    def encode_packed_rows_launches(self, channels_n=2, device=None):
+    def encode_packed_rows_launches(self, channels_n=2, device=None, *, pcm16=False):
         """Library launches :meth:`encode_packed_rows` takes for float32 PCM of ``channels_n`` channels
         (``ac_encode_packed_launches``): 1 = the fused encode packs the frame's rows itself (where
         :meth:`encode_quantized_launches` is 1, bark_bands_n = 64 and the budget is at most ``_lib.AC_PACK_ROWS_MAX_BITS``),
         else :meth:`encode_launches` + 2: the encode, the budgeted quantiser and the packer (everywhere while
-        ``AC_ENCODE_PACKED_NOFUSE=1`` is set: read per call).  0 on a codec without a row budget."""
+        ``AC_ENCODE_PACKED_NOFUSE=1`` is set: read per call).  0 on a codec without a row budget.  ``pcm16=True``: for
+        ``torch.int16`` PCM (``ac_encode_packed_launches_pcm16``)."""
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        return int(self._lib.ac_encode_packed_launches(self.mdct._plan(dev), self.psy._plan(dev), int(channels_n)))
+        query = self._lib.ac_encode_packed_launches_pcm16 if pcm16 else self._lib.ac_encode_packed_launches
+        return int(query(self.mdct._plan(dev), self.psy._plan(dev), int(channels_n)))
 
     def encode_packed_rows(self, x, drown=0.0):
-        """On a codec made by :meth:`with_bitrate` / :meth:`with_row_budget`: x [B, K*N, C] -> (data uint8
+        """On a codec made by :meth:`with_bitrate` / :meth:`with_row_budget`: x [B, K*N, C] (float32, or ``torch.int16``
+        PCM read as ``pcm / 32768``: the bytes of the call on that float32 tensor) -> (data uint8
         [B*(K+1)*C*row_bytes], index int64 [B, K+1, C], fits bool [B, K+1, C]) -- every row in a slot of :attr:`row_bytes`
         bytes, ``index[b, f, c] = ((b*(K+1) + f)*C + c) * row_bytes``.  A slot holds the bytes
         :meth:`PsychoacousticModel.pack` writes for the row's codes and scale factors of :meth:`encode_quantized`, then zero
         bytes; a row longer than its slot (offset 254 reached with the budget unmet) is stored as the marked row -- every
         width 31, ``fits`` False -- and decodes as bands the quantiser could not represent.  :meth:`decode_packed` and
         :meth:`PsychoacousticModel.unpack` read ``(data, index)`` as they are.  One launch where
-        :meth:`encode_packed_rows_launches` is 1, else the composition of the encode, ``quantize_to_budget`` and the packer:
-        the same bytes.  The size of ``data`` is known before the call: it never synchronises with the device, only
-        enqueues on the current stream, and can be captured in a graph.  float32 only, not differentiable."""
+        :meth:`encode_packed_rows_launches` is 1 (``pcm16=True`` for int16), else the composition of the encode,
+        ``quantize_to_budget`` and the packer: the same bytes.  The size of ``data`` is known before the call: it never
+        synchronises with the device, only enqueues on the current stream, and can be captured in a graph.  float32 only,
+        not differentiable."""
         _host.require_float32(self.compute_dtype, "encode_packed_rows")
         if self.row_bits is None:
             raise ValueError("encode_packed_rows needs a codec with a row budget: make one with with_bitrate() or "
@@ -354,7 +363,8 @@ class AudioCodec:
         if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
             raise ValueError("x requires a gradient: quantisation is not differentiable -- use encode() and "
                              "psy.add_noise(), its differentiable stand-in")
-        x = _host.check_device_tensor(x, "x", torch.float32, 3)
+        pcm16 = isinstance(x, torch.Tensor) and x.dtype == torch.int16
+        x = _host.check_device_tensor(x, "x", torch.int16 if pcm16 else torch.float32, 3)
         B, S, C = x.shape
         N = self.filters_n
         if S % N != 0:
@@ -366,14 +376,14 @@ class AudioCodec:
         if rows == 0:
             return (torch.empty((0,), dtype=torch.uint8, device=dev), index, torch.empty((B, F, C), dtype=torch.bool, device=dev))
         mdct, psy = self.mdct._plan(dev), self.psy._plan(dev)
-        if self._lib.ac_encode_packed_launches(mdct, psy, C) == 1:
+        if (self._lib.ac_encode_packed_launches_pcm16 if pcm16 else self._lib.ac_encode_packed_launches)(mdct, psy, C) == 1:
             data = torch.empty((rows * rb,), dtype=torch.uint8, device=dev)
             fits = torch.empty((B, F, C), dtype=torch.bool, device=dev)
             out = _lib.PackedOut(data.data_ptr(), rb, fits.data_ptr())
             with _host.on_device(dev):
                 _lib.check(self._lib.ac_encode_fused_ex(mdct, psy, _host.ptr(x), None, None, None, float(drown),
-                                                        _lib.AC_EMIT_PACKED, ctypes.addressof(out), None, 0, B, K, C,
-                                                        _host.stream_ptr(dev)))
+                                                        _lib.AC_EMIT_PACKED | (_lib.AC_IN_PCM16 if pcm16 else 0),
+                                                        ctypes.addressof(out), None, 0, B, K, C, _host.stream_ptr(dev)))
             return data, index, fits
         # the composition: encode_quantized_budget's codes, scale factors and row lengths (on plain allocations: nothing
         # here may wait for the device), rows longer than their slot marked, then the packer at the fixed row starts
@@ -526,11 +536,11 @@ class StreamingMDCT:
         with _host.on_device(self.device):
             _lib.check(self._lib.ac_stream_reset(self._handle, _host.stream_ptr(self.device)))
 
-    def _check_chunk(self, x, name, ndim):
+    def _check_chunk(self, x, name, ndim, dtype=None):
         if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
             raise ValueError("%s requires a gradient: the streaming calls keep state on the device and are not "
                              "differentiable -- use MDCTransformer.transform / inverse_transform" % name)
-        x = _host.check_device_tensor(x, name, self.mdct.compute_dtype, ndim)
+        x = _host.check_device_tensor(x, name, self.mdct.compute_dtype if dtype is None else dtype, ndim)
         if x.device != self.device:
             raise ValueError("%s lives on %s but the stream's state lives on %s" % (name, x.device, self.device))
         return x
@@ -736,28 +746,34 @@ class StreamingMDCT:
             return None
         return (self.psy.row_budget[0] + 31) // 32 * 4
 
-    def packed_chunk_launches(self, decode=False):
+    def packed_chunk_launches(self, decode=False, *, pcm16=False):
         """Library launches of :meth:`encode_packed_rows_chunk` (``decode=True``: of :meth:`decode_packed_chunk`) on this
         stream (``ac_stream_packed_launches``): 1 = one launch that carries the overlap state -- filters_n = 1024, 64 bands,
         mono / stereo, a budget of at most ``_lib.AC_PACK_ROWS_MAX_BITS``, and for the encode a kernel instance that passed
         the register gate (stereo with ``spreading="f32"`` did not) -- else the launches of the composition (everywhere
         while ``AC_ENCODE_PACKED_NOFUSE=1`` / ``AC_DECODE_PACKED_NOFUSE=1`` is set: read per call).  0 for the encode on a
-        stream without a row budget."""
+        stream without a row budget.  ``pcm16=True``: of the encode on a ``torch.int16`` chunk
+        (``ac_stream_packed_launches_pcm16``; its instances passed the gate with ``spreading="bf16x2_mfma"`` only)."""
         self._packed_ready("packed_chunk_launches", False)
+        if pcm16 and not decode:
+            return int(self._lib.ac_stream_packed_launches_pcm16(self._handle, self.psy._plan(self.device)))
         return int(self._lib.ac_stream_packed_launches(self._handle, self.psy._plan(self.device), 1 if decode else 0))
 
     def encode_packed_rows_chunk(self, x_chunk, drown=0.0, stream=None):
-        """On a stream of a codec made by ``with_bitrate()`` / ``with_row_budget()``: x_chunk [B, k*N, C] -> (data uint8
+        """On a stream of a codec made by ``with_bitrate()`` / ``with_row_budget()``: x_chunk [B, k*N, C] (float32, or
+        ``torch.int16`` PCM read as ``pcm / 32768``: the rows, and the state left, of that float32 chunk) -> (data uint8
         [B*k*C*row_bytes], index int64 [B, k, C], fits bool [B, k, C]) -- the rows ``AudioCodec.encode_packed_rows`` gives
         for the chunk's frames of the whole signal, byte for byte: frame ``f`` of the chunk is frame (blocks so far + f),
         ``index[b, f, c] = ((b*k + f)*C + c) * row_bytes``.  The overlap state advances as under :meth:`encode_chunk`, so
-        the chunk calls of every form may follow each other.  One launch where :meth:`packed_chunk_launches` is 1, else
+        the chunk calls of every form may follow each other.  One launch where :meth:`packed_chunk_launches` is 1
+        (``pcm16=True`` for int16; elsewhere an int16 chunk is converted and takes the float32 path), else
         :meth:`encode_chunk`, ``psy.quantize_to_budget`` and the packer: the same bytes.  Only enqueues, on ``stream`` or
         the current stream; float32 only, not differentiable."""
         self._packed_ready("encode_packed_rows_chunk", True)
         N, rb = self.mdct.filters_n, self.row_bytes
         with self._on(stream):
-            x = self._check_chunk(x_chunk, "x_chunk", 3)
+            pcm16 = isinstance(x_chunk, torch.Tensor) and x_chunk.dtype == torch.int16
+            x = self._check_chunk(x_chunk, "x_chunk", 3, torch.int16 if pcm16 else None)
             B, S, C = x.shape
             if (B, C) != (self.B, self.C) or S % N != 0:
                 raise ValueError("x_chunk must be [%d, k*%d, %d], got %s" % (self.B, N, self.C, tuple(x.shape)))
@@ -768,13 +784,17 @@ class StreamingMDCT:
                 return (torch.empty((0,), dtype=torch.uint8, device=dev), index,
                         torch.empty((B, k, C), dtype=torch.bool, device=dev))
             psy = self.psy._plan(dev)
-            if self._lib.ac_stream_packed_launches(self._handle, psy, 0) == 1:
+            if pcm16 and self._lib.ac_stream_packed_launches_pcm16(self._handle, psy) != 1:
+                x, pcm16 = x.to(torch.float32) / 32768, False
+            if pcm16 or self._lib.ac_stream_packed_launches(self._handle, psy, 0) == 1:
                 data = torch.empty((rows * rb,), dtype=torch.uint8, device=dev)
                 fits = torch.empty((B, k, C), dtype=torch.bool, device=dev)
                 out = _lib.PackedOut(data.data_ptr(), rb, fits.data_ptr())
                 with _host.on_device(dev):
                     _lib.check(self._lib.ac_stream_encode_typed(self._handle, psy, _host.ptr(x), ctypes.addressof(out), None,
-                                                                None, float(drown), _lib.AC_PACKED, k, self._stream(stream)))
+                                                                None, float(drown),
+                                                                _lib.AC_PACKED | (_lib.AC_IN_PCM16 if pcm16 else 0), k,
+                                                                self._stream(stream)))
                 return data, index, fits
             X, _, thr = self.encode_chunk(x, drown, stream=stream)
             data, fits = _pack_rows_of_spectra(self.psy, X, thr, index, rb)

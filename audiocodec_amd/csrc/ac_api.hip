@@ -742,10 +742,15 @@ int ac_encode_quantized_launches(const ac_mdct_plan* mdct, const ac_psy_plan* ps
   if (!mdct || !psy || mdct->N != psy->N || mdct->device != psy->device || C < 1) return 0;
   return encode_quantized_fuses(mdct, psy, C) ? 1 : 2;
 }
+// (16-bit PCM: every instance of k_fwd_fast_q16 / qb16 passed its register gate, so the one launch serves where the float32
+// one does)
+int ac_encode_quantized_launches_pcm16(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C) {
+  return ac_encode_quantized_launches(mdct, psy, C);
+}
 
-// ac_encode_fused_ex with AC_EMIT_CODES
-static int encode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
-                            float drown, int16_t* codes, int8_t* sf, int B, int K, int C, void* stream) {
+// ac_encode_fused_ex with AC_EMIT_CODES (pcm16: with AC_IN_PCM16, x is int16)
+static int encode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const void* x, bool pcm16, float* X, float* t,
+                            float* thr, float drown, int16_t* codes, int8_t* sf, int B, int K, int C, void* stream) {
   AC_REQUIRE(mdct != nullptr && psy != nullptr, "plan is NULL");
   AC_REQUIRE(mdct->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", mdct->N, psy->N);
   AC_REQUIRE(mdct->device == psy->device, "plans live on different devices");
@@ -758,15 +763,24 @@ static int encode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, co
     AC_REQUIRE(x != nullptr || K == 0, "NULL tensor pointer");
     AC_REQUIRE_ALIGNED(x, X, thr, codes, sf);
     DeviceGuard guard(mdct->device);
+    if (pcm16) {
+      const int16_t* xp = static_cast<const int16_t*>(x);
+      if (psy->row_bits)
+        return launch_fwd_fast_quant_budget_pcm16(mdct, psy, xp, X, t, thr, drown, psy->row_bits, psy->kmin, codes, sf, B, K,
+                                                  K + 1, C, (hipStream_t)stream);
+      return launch_fwd_fast_quant_pcm16(mdct, psy, xp, X, t, thr, drown, codes, sf, B, K, K + 1, C, (hipStream_t)stream);
+    }
+    const float* xf = static_cast<const float*>(x);
     if (psy->row_bits)
-      return launch_fwd_fast_quant_budget(mdct, psy, x, X, t, thr, drown, psy->row_bits, psy->kmin, codes, sf, B, K, K + 1, C,
+      return launch_fwd_fast_quant_budget(mdct, psy, xf, X, t, thr, drown, psy->row_bits, psy->kmin, codes, sf, B, K, K + 1, C,
                                           (hipStream_t)stream);
-    return launch_fwd_fast_quant(mdct, psy, x, X, t, thr, drown, codes, sf, B, K, K + 1, C, (hipStream_t)stream);
+    return launch_fwd_fast_quant(mdct, psy, xf, X, t, thr, drown, codes, sf, B, K, K + 1, C, (hipStream_t)stream);
   }
   AC_REQUIRE(X != nullptr && t != nullptr && thr != nullptr,
-             "AC_EMIT_CODES: X, t and thr are required as intermediates where ac_encode_quantized_launches() returns 2");
+             "AC_EMIT_CODES: X, t and thr are required as intermediates where ac_encode_quantized_launches%s() returns 2",
+             pcm16 ? "_pcm16" : "");
   AC_REQUIRE_ALIGNED(codes, sf);
-  st = encode_fused(mdct, psy, x, false, X, t, thr, drown, B, K, C, stream);
+  st = encode_fused(mdct, psy, x, pcm16, X, t, thr, drown, B, K, C, stream);
   if (st) return st;
   DeviceGuard guard(psy->device);
   return quantize_of_plan(psy, X, thr, codes, sf, B, K + 1, C, (hipStream_t)stream);
@@ -784,11 +798,15 @@ int ac_encode_packed_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
   if (!mdct || !psy || mdct->N != psy->N || mdct->device != psy->device || C < 1 || !psy->row_bits) return 0;
   return encode_packed_fuses(mdct, psy, C) ? 1 : ac_encode_launches(mdct, psy, C) + 2;
 }
+// (16-bit PCM: every instance of k_fwd_fast_qp16 passed its register gate)
+int ac_encode_packed_launches_pcm16(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C) {
+  return ac_encode_packed_launches(mdct, psy, C);
+}
 
-// ac_encode_fused_ex with AC_EMIT_PACKED
-static int encode_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, const float* X, const float* t,
-                              const float* thr, float drown, const ac_packed_out* out, const void* out1, int B, int K, int C,
-                              void* stream) {
+// ac_encode_fused_ex with AC_EMIT_PACKED (pcm16: with AC_IN_PCM16, x is int16)
+static int encode_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const void* x, bool pcm16, const float* X,
+                              const float* t, const float* thr, float drown, const ac_packed_out* out, const void* out1, int B,
+                              int K, int C, void* stream) {
   AC_REQUIRE(mdct != nullptr && psy != nullptr, "plan is NULL");
   AC_REQUIRE(mdct->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", mdct->N, psy->N);
   AC_REQUIRE(mdct->device == psy->device, "plans live on different devices");
@@ -806,30 +824,41 @@ static int encode_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
   if (B == 0 || C == 0) return AC_OK;
   if (!encode_packed_fuses(mdct, psy, C)) {
     set_error("AC_EMIT_PACKED: no kernel encodes to packed rows in one launch for filters_n = %d, bark_bands_n = %d, %d "
-              "channels, row budget %d here (ac_encode_packed_launches() != 1): use the composition -- ac_encode_fused, "
+              "channels, row budget %d here (ac_encode_packed_launches%s() != 1): use the composition -- %s, "
               "ac_quantize_budget, then ac_pack at row starts r * row_bytes into zero-filled data",
-              mdct->N, psy->M, C, psy->row_bits);
+              mdct->N, psy->M, C, psy->row_bits, pcm16 ? "_pcm16" : "", pcm16 ? "ac_encode_fused_pcm16" : "ac_encode_fused");
     return AC_EUNSUPPORTED;
   }
   AC_REQUIRE(po.data != nullptr && po.fits != nullptr && (x != nullptr || K == 0), "NULL tensor pointer");
   AC_REQUIRE_ALIGNED(x, po.data);
   DeviceGuard guard(mdct->device);
-  return launch_fwd_fast_pack_rows(mdct, psy, x, drown, po.data, row_bytes, po.fits, B, K, K + 1, C, (hipStream_t)stream);
+  if (pcm16)
+    return launch_fwd_fast_pack_rows_pcm16(mdct, psy, static_cast<const int16_t*>(x), drown, po.data, row_bytes, po.fits, B, K,
+                                           K + 1, C, (hipStream_t)stream);
+  return launch_fwd_fast_pack_rows(mdct, psy, static_cast<const float*>(x), drown, po.data, row_bytes, po.fits, B, K, K + 1, C,
+                                   (hipStream_t)stream);
 }
 
 int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
                        float drown, int flags, void* noisy_v, void* db_norm_v, uint64_t seed, int B, int K, int C,
                        void* stream) {
-  AC_REQUIRE((flags & ~(AC_EMIT_NOISY | AC_EMIT_DB_NORM | AC_EMIT_CODES | AC_EMIT_PACKED)) == 0, "unknown flags %#x", flags);
-  if (flags & AC_EMIT_PACKED) {
-    AC_REQUIRE(flags == AC_EMIT_PACKED, "AC_EMIT_PACKED excludes the other flags (got %#x)", flags);
-    return encode_packed_rows(mdct, psy, x, X, t, thr, drown, static_cast<const ac_packed_out*>(noisy_v), db_norm_v, B, K, C,
-                              stream);
+  AC_REQUIRE((flags & ~(AC_EMIT_NOISY | AC_EMIT_DB_NORM | AC_EMIT_CODES | AC_EMIT_PACKED | AC_IN_PCM16)) == 0, "unknown flags %#x",
+             flags);
+  // AC_IN_PCM16: x is int16, under AC_EMIT_CODES or AC_EMIT_PACKED only
+  const bool pcm16 = (flags & AC_IN_PCM16) != 0;
+  const int emit = flags & ~AC_IN_PCM16;
+  AC_REQUIRE(!pcm16 || emit == AC_EMIT_CODES || emit == AC_EMIT_PACKED,
+             "AC_IN_PCM16 goes with AC_EMIT_CODES or AC_EMIT_PACKED alone (got %#x): the encode of 16-bit PCM to X, t and thr is "
+             "ac_encode_fused_pcm16", flags);
+  if (emit & AC_EMIT_PACKED) {
+    AC_REQUIRE(emit == AC_EMIT_PACKED, "AC_EMIT_PACKED excludes the other output flags (got %#x)", flags);
+    return encode_packed_rows(mdct, psy, x, pcm16, X, t, thr, drown, static_cast<const ac_packed_out*>(noisy_v), db_norm_v, B, K,
+                              C, stream);
   }
-  if (flags & AC_EMIT_CODES) {
-    AC_REQUIRE(flags == AC_EMIT_CODES, "AC_EMIT_CODES excludes the other flags (got %#x)", flags);
-    return encode_quantized(mdct, psy, x, X, t, thr, drown, static_cast<int16_t*>(noisy_v), static_cast<int8_t*>(db_norm_v), B, K,
-                            C, stream);
+  if (emit & AC_EMIT_CODES) {
+    AC_REQUIRE(emit == AC_EMIT_CODES, "AC_EMIT_CODES excludes the other output flags (got %#x)", flags);
+    return encode_quantized(mdct, psy, x, pcm16, X, t, thr, drown, static_cast<int16_t*>(noisy_v), static_cast<int8_t*>(db_norm_v),
+                            B, K, C, stream);
   }
   float* noisy = static_cast<float*>(noisy_v);
   float* db_norm = static_cast<float*>(db_norm_v);
@@ -1503,8 +1532,17 @@ int ac_stream_packed_launches(const ac_stream* s, const ac_psy_plan* psy, int de
   return stream_encode_packed_fuses(s, psy) ? 1 : ac_encode_launches(s->plan, psy, s->C) + 2;
 }
 
-static int stream_encode_packed(ac_stream* s, const ac_psy_plan* psy, const void* x_chunk, const ac_packed_out* out, const void* t,
-                                const void* thr, double drown, int k, void* stream) {
+// (16-bit PCM chunks, AC_PACKED | AC_IN_PCM16: k_fwd_fast_qps16 has a register gate of its own)
+static bool stream_encode_packed_fuses_pcm16(const ac_stream* s, const ac_psy_plan* psy) {
+  return encode_packed_fuses(s->plan, psy, s->C) && fast_encode_pack_stream_pcm16_serves(s->plan, psy, s->C);
+}
+int ac_stream_packed_launches_pcm16(const ac_stream* s, const ac_psy_plan* psy) {
+  if (!stream_packed_args_match(s, psy) || !psy->row_bits) return 0;
+  return stream_encode_packed_fuses_pcm16(s, psy) ? 1 : ac_encode_launches(s->plan, psy, s->C) + 2;
+}
+
+static int stream_encode_packed(ac_stream* s, const ac_psy_plan* psy, const void* x_chunk, bool pcm16, const ac_packed_out* out,
+                                const void* t, const void* thr, double drown, int k, void* stream) {
   AC_REQUIRE(s != nullptr, "stream is NULL");
   AC_REQUIRE(psy != nullptr, "AC_PACKED needs the masking model's plan");
   AC_REQUIRE(k >= 0, "negative chunk length %d", k);
@@ -1519,11 +1557,12 @@ static int stream_encode_packed(ac_stream* s, const ac_psy_plan* psy, const void
   AC_REQUIRE(po.row_bytes == row_bytes, "row_bytes (%lld) is not the plan's ceil(%d / 32) * 4 = %lld", (long long)po.row_bytes,
              psy->row_bits, (long long)row_bytes);
   if (k == 0) return AC_OK;
-  if (!stream_encode_packed_fuses(s, psy)) {
-    set_error("AC_PACKED: no kernel encodes a chunk to packed rows in one launch for filters_n = %d, bark_bands_n = %d, %d "
-              "channels, row budget %d here (ac_stream_packed_launches() != 1): use the composition -- ac_stream_encode, "
+  if (!(pcm16 ? stream_encode_packed_fuses_pcm16(s, psy) : stream_encode_packed_fuses(s, psy))) {
+    set_error("AC_PACKED: no kernel encodes a chunk%s to packed rows in one launch for filters_n = %d, bark_bands_n = %d, %d "
+              "channels, row budget %d here (ac_stream_packed_launches%s() != 1): use the composition -- ac_stream_encode%s, "
               "ac_quantize_budget, then ac_pack at row starts r * row_bytes into zero-filled data",
-              p->N, psy->M, s->C, psy->row_bits);
+              pcm16 ? " of 16-bit PCM" : "", p->N, psy->M, s->C, psy->row_bits, pcm16 ? "_pcm16" : "",
+              pcm16 ? " on pcm / 32768 as float32" : "");
     return AC_EUNSUPPORTED;
   }
   int st = check_quant(psy, s->B, k, s->C);
@@ -1531,8 +1570,12 @@ static int stream_encode_packed(ac_stream* s, const ac_psy_plan* psy, const void
   AC_REQUIRE(po.data != nullptr && po.fits != nullptr && x_chunk != nullptr, "NULL tensor pointer");
   AC_REQUIRE_ALIGNED(x_chunk, po.data);
   DeviceGuard guard(s->device);
-  st = launch_fwd_fast_pack_rows_stream(p, psy, static_cast<const float*>(x_chunk), (float)drown, po.data, row_bytes, po.fits,
-                                        s->d_prev_block, s->d_prev_tmp, s->B, k, s->C, (hipStream_t)stream);
+  if (pcm16)
+    st = launch_fwd_fast_pack_rows_stream_pcm16(p, psy, static_cast<const int16_t*>(x_chunk), (float)drown, po.data, row_bytes,
+                                                po.fits, s->d_prev_block, s->d_prev_tmp, s->B, k, s->C, (hipStream_t)stream);
+  else
+    st = launch_fwd_fast_pack_rows_stream(p, psy, static_cast<const float*>(x_chunk), (float)drown, po.data, row_bytes, po.fits,
+                                          s->d_prev_block, s->d_prev_tmp, s->B, k, s->C, (hipStream_t)stream);
   if (st) return st;
   std::swap(s->d_prev_block, s->d_prev_tmp);
   return AC_OK;
@@ -1573,7 +1616,8 @@ static int stream_inverse_packed(ac_stream* s, const ac_stream_packed_in* in, vo
 
 int ac_stream_encode_typed(ac_stream* s, const ac_psy_plan* psy, const void* x_chunk, void* X, void* t, void* thr, double drown,
                            int dtype, int k, void* stream) {
-  if (dtype == AC_PACKED) return stream_encode_packed(s, psy, x_chunk, static_cast<const ac_packed_out*>(X), t, thr, drown, k, stream);
+  if (dtype == AC_PACKED || dtype == (AC_PACKED | AC_IN_PCM16))
+    return stream_encode_packed(s, psy, x_chunk, dtype != AC_PACKED, static_cast<const ac_packed_out*>(X), t, thr, drown, k, stream);
   AC_REQUIRE_DTYPE(dtype);
   if (dtype == AC_F32) {
     if (psy) return ac_stream_encode(s, psy, static_cast<const float*>(x_chunk), static_cast<float*>(X), static_cast<float*>(t),

@@ -1,6 +1,6 @@
 // Analysis of the wave-level kernels for filters_n = 1024 / 2048 (ac_fast_dev.h), with the fused masking model: the
 // body and the k_fwd_fast template.  Instantiated in ac_fast_fwd.hip, which also runs the body in k_duplex_fast, and in
-// ac_fast_fwd_q.hip (k_fwd_fast_q: the body with the quantiser as its last stage, ac_fast_quant_dev.h).
+// ac_fast_fwd_q.hip (k_fwd_fast_q: the body with the quantiser as its last stage, ac_fast_quant_dev.h) and its siblings.
 #pragma once
 #include <cmath>
 #include <cstdlib>
@@ -68,7 +68,8 @@ template <int R, int CMODE, bool PSY, int NW, int IOF = 0, int SPREAD = 0, bool 
 __device__ __forceinline__ void fwd_fast_body(const FwdArgs& a, char* lds, const int bid, const int nblocks, QUANT qz = QUANT()) {
   static_assert(!EPI || (PSY && CMODE == 0 && IOF == 0), "the element-wise epilogues ride on the stereo float32 fused encode");
   constexpr bool QNT = !std::is_same<QUANT, NoQuant>::value;
-  static_assert(!QNT || (PSY && !EPI && IOF == 0 && R == 8), "the quantiser rides on the float32 fused encode at 8 points per lane");
+  static_assert(!QNT || (PSY && !EPI && (IOF == 0 || IOF == 1) && R == 8),
+                "the quantiser rides on the float32 / 16-bit PCM fused encode at 8 points per lane");
   using G = Geo<R>;
   constexpr int WSTRIDE = PSY ? WAVE_LDS_PSY : WAVE_LDS;
   constexpr bool NOPRE = fwd_nopre<R, PSY, SPREAD>();
@@ -102,8 +103,10 @@ __device__ __forceinline__ void fwd_fast_body(const FwdArgs& a, char* lds, const
   using pcm_t = typename std::conditional<IOF != 0, int16_t, float>::type;
   const pcm_t* __restrict__ xin = static_cast<const pcm_t*>(a.x);
   const pcm_t* __restrict__ xstate = IOF != 0 ? nullptr : reinterpret_cast<const pcm_t*>(a.prev_block);
-  // bfloat16 tensors (IOF 2): the streaming state stays float32 (a bfloat16 block is exact in it)
-  const float* __restrict__ fstate = IOF == 2 ? a.prev_block : nullptr;
+  // bfloat16 tensors (IOF 2) and 16-bit PCM under the quantiser (IOF 1 with QUANT: the k_fwd_fast_*16 kernels): the
+  // streaming state stays float32 (a bfloat16 block, and pcm / 32768, are exact in it)
+  constexpr bool FSTATE = IOF == 2 || (IOF == 1 && QNT);
+  const float* __restrict__ fstate = FSTATE ? a.prev_block : nullptr;
 
   // loads block fn (WHICH 0) or block fn-1 (WHICH 1) of frame (pr, fn) in natural order.  A missing block (before the
   // first / after the last) is loaded from a neighbouring, valid address and zeroed when it is consumed (returns false),
@@ -118,7 +121,7 @@ __device__ __forceinline__ void fwd_fast_body(const FwdArgs& a, char* lds, const
       s0 = xin + row_off(q.b0, a.Kin, blkidx, blk, q.c0);
       s1 = xin + row_off(q.b1, a.Kin, blkidx, blk, q.c1);
     } else {
-      if constexpr (IOF == 2) {
+      if constexpr (FSTATE) {
         if (fn < 1 && fstate) {   // block -1 = the stored float32 state
           load_row<CMODE, R>(fstate + row_off(q.b0, 1, 0, blk, q.c0), fstate + row_off(q.b1, 1, 0, blk, q.c1), C, q.has1, lane, dst);
           return true;
@@ -161,7 +164,7 @@ __device__ __forceinline__ void fwd_fast_body(const FwdArgs& a, char* lds, const
       const bool prv_ok = issue_loads(kPrv, pair, n, pb);
       if (!cur_ok) zero_row(cb);   // edge frames only (wave-uniform)
       if (!prv_ok) zero_row(pb);
-      if constexpr (IOF != 1) {
+      if constexpr (IOF != 1 || QNT) {
         if (a.state_out && n == a.Kin - 1)   // streaming: the chunk's last block is the next chunk's block -1
           store_row<CMODE, R>(a.state_out + row_off(pq.b0, 1, 0, blk, pq.c0), a.state_out + row_off(pq.b1, 1, 0, blk, pq.c1),
                               C, pq.has1, lane, cb);
@@ -217,7 +220,7 @@ __device__ __forceinline__ void fwd_fast_body(const FwdArgs& a, char* lds, const
       v4f cb[R];
       const bool cur_ok = issue_loads(kCur, pair, n, cb);
       if (!cur_ok) zero_row(cb);
-      if constexpr (IOF != 1) {
+      if constexpr (IOF != 1 || QNT) {
         if (a.state_out && n == a.Kin - 1)
           store_row<CMODE, R>(a.state_out + row_off(pq.b0, 1, 0, blk, pq.c0), a.state_out + row_off(pq.b1, 1, 0, blk, pq.c1),
                               C, pq.has1, lane, cb);

@@ -287,6 +287,20 @@ bool fast_encode_pack_stream_serves(const ac_mdct_plan* p, const ac_psy_plan* ps
 int launch_fwd_fast_pack_rows_stream(const ac_mdct_plan* p, const ac_psy_plan* psy, const float* x, float drown, uint8_t* data,
                                      int64_t row_bytes, uint8_t* fits, const float* prev_block, float* state_out, int B, int k,
                                      int C, hipStream_t s);
+// the four above on 16-bit PCM (k_fwd_fast_q16 / qb16 / qp16 / qps16, ac_fast_fwd_*16.hip): x int16, read as pcm / 32768 in the
+// row loads -- the outputs of the float32 launch on pcm.to(float32) / 32768 bit for bit; the stream's state stays float32.  The
+// one-shot three serve where their float32 forms do; the stream form where its own instance passed the register gate
+int launch_fwd_fast_quant_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const int16_t* x, float* X, float* t, float* thr,
+                                float drown, int16_t* codes, int8_t* sf, int B, int Kin, int F, int C, hipStream_t s);
+int launch_fwd_fast_quant_budget_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const int16_t* x, float* X, float* t,
+                                       float* thr, float drown, int row_bits, int kmin, int16_t* codes, int8_t* sf, int B, int Kin,
+                                       int F, int C, hipStream_t s);
+int launch_fwd_fast_pack_rows_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const int16_t* x, float drown, uint8_t* data,
+                                    int64_t row_bytes, uint8_t* fits, int B, int Kin, int F, int C, hipStream_t s);
+bool fast_encode_pack_stream_pcm16_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);
+int launch_fwd_fast_pack_rows_stream_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const int16_t* x, float drown,
+                                           uint8_t* data, int64_t row_bytes, uint8_t* fits, const float* prev_block,
+                                           float* state_out, int B, int k, int C, hipStream_t s);
 int launch_inv_fast(const ac_mdct_plan* p, const float* X, void* x, int iof, const float* tail_in, float* tail_out,
                     int B, int Kp, int nblk, int C, hipStream_t s);
 // synthesis straight from quantised spectra (codes int16 [B,Kp,N,C], sf int8 [B,Kp,M,C]; ac_quant.hip), filters_n 1024 /

@@ -50,7 +50,8 @@ extern "C" {
                           * ac_decode_packed_launches) and its rate control (ac_quantize_budget, per clip
                           * ac_quantize_clip_budget, ac_clip_budget_scratch_bytes; in the plan: ac_psy_plan_with_row_budget,
                           * ac_psy_plan_row_budget; packed rows in a stream: AC_PACKED, ac_stream_packed_in,
-                          * ac_stream_packed_launches); additions only, so the number stays.
+                          * ac_stream_packed_launches; 16-bit PCM into the quantising encodes: AC_IN_PCM16,
+                          * ac_*_launches_pcm16); additions only, so the number stays.
                           * 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
                           * with a 5-smooth half up to 8192, float32); masking model for general band layouts up to 4096 bins.
                           * 0.1.7: only the ac_* entry points are exported; ac_stream_settle (home buffers for the streaming state);
@@ -246,9 +247,17 @@ AC_API int ac_encode_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
  *     with index[r] = r row_bytes.  A plan without a row budget is AC_EINVAL.  Served where ac_encode_packed_launches
  *     returns 1; AC_EUNSUPPORTED elsewhere: compose it from ac_encode_fused, ac_quantize_budget (row_bits_out > 8 row_bytes
  *     marks a row that does not fit: fill its sf with -128) and ac_pack at those row starts into zero-filled data.
+ *   AC_IN_PCM16      beside AC_EMIT_CODES or AC_EMIT_PACKED only: x is read as const int16_t* [B,K*N,C], x = pcm / 32768 (exact
+ *     in float32), and the outputs are what the same call gives on that float32 tensor, bit for bit.  Alone, or with
+ *     AC_EMIT_NOISY / AC_EMIT_DB_NORM, it is AC_EINVAL: the encode of 16-bit PCM to X, t and thr is ac_encode_fused_pcm16.
+ *     AC_EMIT_CODES | AC_IN_PCM16: ONE launch where ac_encode_quantized_launches_pcm16 returns 1, under the X / t / thr rules
+ *     above (each equals ac_encode_fused_pcm16's where given); where it returns 2, ac_encode_fused_pcm16's encode followed
+ *     by the quantiser (the budgeted one at a plan with a row budget), X, t and thr required, and AC_EUNSUPPORTED where
+ *     16-bit PCM has no encode.  AC_EMIT_PACKED | AC_IN_PCM16: ONE launch where ac_encode_packed_launches_pcm16 returns 1,
+ *     AC_EUNSUPPORTED elsewhere.
  * out0 / out1: float* noisy, float* db_norm under AC_EMIT_NOISY / AC_EMIT_DB_NORM; int16_t* codes, int8_t* sf under
  * AC_EMIT_CODES; ac_packed_out*, NULL under AC_EMIT_PACKED. */
-enum { AC_EMIT_NOISY = 1, AC_EMIT_DB_NORM = 2, AC_EMIT_CODES = 4, AC_EMIT_PACKED = 8 };
+enum { AC_EMIT_NOISY = 1, AC_EMIT_DB_NORM = 2, AC_EMIT_CODES = 4, AC_EMIT_PACKED = 8, AC_IN_PCM16 = 32 };
 /* The largest row budget the one launch of AC_EMIT_PACKED serves: a wave stages both rows of its frame pair in the 4 KB of
  * its LDS buffer that the masking model has left, 2 KB = 16384 bits each. */
 #define AC_PACK_ROWS_MAX_BITS 16384
@@ -271,6 +280,11 @@ AC_API int ac_encode_quantized_launches(const ac_mdct_plan* mdct, const ac_psy_p
  * above (also everywhere while AC_ENCODE_PACKED_NOFUSE=1 is set in the environment: read per call).  0 for NULL or
  * mismatched plans, C < 1, or a plan without a row budget.  The bytes do not depend on it. */
 AC_API int ac_encode_packed_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C);
+/* The two queries above for int16 input (AC_IN_PCM16), with the same return conventions: 1 = the fused kernel reads the 16-bit
+ * PCM itself (k_fwd_fast_q16 / qb16 / qp16: every instance passed its register gate, so wherever the float32 query returns
+ * 1), else the launches of the composition.  AC_ENCODE_QUANT_NOFUSE=1 / AC_ENCODE_PACKED_NOFUSE=1 apply (read per call). */
+AC_API int ac_encode_quantized_launches_pcm16(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C);
+AC_API int ac_encode_packed_launches_pcm16(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C);
 
 /* 16-bit PCM at the boundary (extension; the reference takes float PCM in [-1, 1] only, mdctransformer.py:104):
  * x = pcm / 32768 on the way in; on the way out pcm = 0 if x is NaN else clamp(rint(fp32(32768 x)), -32768, 32767), rint
@@ -563,7 +577,13 @@ AC_API int ac_stream_inverse_typed(ac_stream* s, const void* X_chunk, void* x, i
  *   ac_encode_packed_launches is 1 for the stream's channels and the kernel instance with streaming state passed its register
  *   gate (stereo with the f32 spreading product did not), else ac_encode_launches + 2.  decode != 0: 1 where
  *   ac_decode_packed_launches is 1, else 3.  AC_ENCODE_PACKED_NOFUSE=1 / AC_DECODE_PACKED_NOFUSE=1 apply as they do one-shot
- *   (read per call).  0 for NULL or mismatched arguments, or (decode = 0) a plan without a row budget. */
+ *   (read per call).  0 for NULL or mismatched arguments, or (decode = 0) a plan without a row budget.
+ * 16-bit PCM into the encoder: ac_stream_encode_typed(..., dtype = AC_PACKED | AC_IN_PCM16 (48), ...) takes x_chunk as int16
+ *   [B,k*N,C], x = pcm / 32768: the rows, and the float32 state it leaves, are those of the AC_PACKED call on that float32
+ *   chunk.  ONE launch where ac_stream_packed_launches_pcm16(s, psy) returns 1 -- where ac_encode_packed_launches is 1 and the
+ *   16-bit instance with streaming state passed its register gate (mono and stereo with the f32 spreading product did not) --
+ *   and AC_EUNSUPPORTED elsewhere, with the state untouched; the query then returns ac_encode_launches + 2 (convert the chunk
+ *   and compose as above), or 0 as ac_stream_packed_launches does.  No other *_typed entry point takes the value. */
 enum { AC_PACKED = 16 };   /* ac_stream_encode_typed / ac_stream_inverse_typed: the spectra are packed rows */
 typedef struct ac_stream_packed_in {
   ac_packed_rows rows;      /* data, nbytes, index [B,k,C] */
@@ -571,6 +591,7 @@ typedef struct ac_stream_packed_in {
   int32_t pcm16;            /* 0: x is float32 [B,k*N,C]; 1: int16 */
 } ac_stream_packed_in;
 AC_API int ac_stream_packed_launches(const ac_stream* s, const ac_psy_plan* psy, int decode);
+AC_API int ac_stream_packed_launches_pcm16(const ac_stream* s, const ac_psy_plan* psy);
 AC_API int ac_amplitude_to_db_typed(const void* a, void* out, size_t n, int norm, int dtype, void* stream);
 AC_API int ac_add_noise_typed(const void* X, const void* thr, void* out, size_t n, uint64_t seed, int dtype, void* stream);
 

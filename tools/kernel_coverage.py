@@ -17,7 +17,7 @@
       that launched it and how often; with --manifest, (re)writes that column of tests/kernel_coverage.txt.  With
       --part NAME instead, writes tests/kernel_coverage.d/NAME.txt from a traced run of the new test files alone: the rows
       of the kernels the manifest does not list yet and the code letters of the test files it does not name, and nothing
-      else -- how a change that adds kernels records them while every existing row stays as the last full trace wrote
+      else ("# sole-cover" lines added to a part by hand are read with the manifest's and kept when the part is rewritten) -- how a change that adds kernels records them while every existing row stays as the last full trace wrote
       it.  read_manifest() reads the manifest and every part; the next full re-trace (--manifest) takes the parts' rows
       and letters into the manifest and removes the part files.
 
@@ -179,7 +179,8 @@ def part_files():
 def read_manifest(path=MANIFEST, parts=True, skip=None):
     """(header lines, codes {code: test file}, rows {symbol: (parent codes, head codes)}) of the manifest and, for the
     manifest of the tree, of every part under tests/kernel_coverage.d (but ``skip``).  A part may only add: a code letter
-    or a kernel named twice is an error.  Of a part's comment lines only its code letters join the header."""
+    or a kernel named twice is an error.  Of a part's comment lines only its code letters and its "# sole-cover <kernel>
+    <file>::<test>" lines (added by hand, for a new family only one test reaches) join the header."""
     header, codes, rows = [], {}, {}
     files = [path]
     if parts and os.path.abspath(path) == os.path.abspath(MANIFEST):
@@ -192,7 +193,7 @@ def read_manifest(path=MANIFEST, parts=True, skip=None):
                 if code:
                     assert w[1] not in codes, "%s: code %s is defined twice" % (f, w[1])
                     codes[w[1]] = w[2]
-                if code or f == path:
+                if code or f == path or (len(w) == 3 and w[0] == "sole-cover"):
                     header.append(ln)
             elif ln.strip():
                 w = ln.split()
@@ -221,6 +222,8 @@ def write_part(cover, name):
             code = next_code(codes)
             codes[code], by_file[f] = f, code
             header.append("# code %s %s" % (code, f))
+    if os.path.exists(out):      # the sole covers named by hand survive a rewrite of the part
+        header += [ln for ln in open(out).read().splitlines() if ln.startswith("# sole-cover ")]
     os.makedirs(PARTS, exist_ok=True)
     with open(out, "w") as fh:
         fh.write("\n".join(header) + "\n")

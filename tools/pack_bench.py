@@ -11,8 +11,12 @@ launch of k_fwd_fast_qp; AC_ENCODE_PACKED_NOFUSE=1: the composition) and encode_
 chunk methods existed -- encode_chunk, quantize_to_budget, the mask, ac_pack; unpack, dequantize, inverse_chunk -- against
 encode_packed_rows_chunk / decode_packed_chunk where the package has them, so the same script times the baseline on an older
 commit.  Two workloads: one stereo clip in chunks of 256 blocks (per-chunk latency) and --clips x --blocks as one chunk.
+--pcm16: int16 PCM to packed rows (pcm16_rows()), one-shot at the bench workload and one stereo clip in chunks of 256 blocks:
+the one launch on int16 (k_fwd_fast_qp16 / qps16), the conversion to(float32) / 32768 followed by the float32 one launch (what a
+caller did before), and the float32 one launch on a resident float32 tensor; compared byte for byte, then alternating
+(profiles/pack/pack_bench_pcm16.txt).
 python tools/pack_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7] [--round-steps 30]
-                           [--row-bits 1365] [--only-rows] [--stream]"""
+                           [--row-bits 1365] [--only-rows] [--stream] [--pcm16]"""
 import argparse
 import ctypes
 import os
@@ -146,8 +150,56 @@ def stream_rows(a):
                   % (f, v[len(v) // 2], v[0], v[-1], len(v), a.round_steps))
 
 
+def pcm16_rows(a):
+    B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    cbr = audiocodec_amd.AudioCodec(48000, N).with_row_budget(a.row_bits)
+
+    def alternate(forms, unit, scale):
+        runs = dict((n, []) for n, _ in forms)
+        for _ in range(a.rounds):
+            for n, fn in forms:
+                runs[n].append(timed(fn, a.round_steps, 1) * scale)
+        med = []
+        for n, _ in forms:
+            v = sorted(runs[n])
+            med.append(v[len(v) // 2])
+            print("  %-50s median %9.3f %s  min %9.3f  max %9.3f  (%d alternating rounds of %d)"
+                  % (n, med[-1], unit, v[0], v[-1], len(v), a.round_steps))
+        print("  int16 / (convert + float32) = %.3f   int16 / float32 resident = %.3f" % (med[0] / med[1], med[0] / med[2]))
+
+    x = (torch.rand((B, K * N, C), device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * 2 - 1)
+    p = torch.round(x * 32767).to(torch.int16)
+    x = p.to(torch.float32) / 32768
+    one, flt = cbr.encode_packed_rows(p), cbr.encode_packed_rows(x)
+    assert all(torch.equal(g, r) for g, r in zip(one, flt)), "the int16 and the float32 rows differ"
+    del one, flt
+    print("packed rows from int16: B=%d K=%d N=%d C=%d  %d bits per row  launches: int16 %d, float32 %d  the rows agree byte for byte  %s"
+          % (B, K, N, C, a.row_bits, cbr.encode_packed_rows_launches(C, pcm16=True), cbr.encode_packed_rows_launches(C),
+             torch.cuda.get_device_name()))
+    alternate([("encode_packed_rows(int16)", lambda: cbr.encode_packed_rows(p)),
+               ("encode_packed_rows(int16.to(float32) / 32768)", lambda: cbr.encode_packed_rows(p.to(torch.float32) / 32768)),
+               ("encode_packed_rows(float32 resident)", lambda: cbr.encode_packed_rows(x))], "ms", 1.0)
+    del x, p
+    # one stereo clip in chunks of 256 blocks
+    k, n = 256, 8
+    g = torch.Generator("cuda").manual_seed(1)
+    ps = [torch.round((torch.rand((1, k * N, C), device="cuda", generator=g) * 2 - 1) * 32767).to(torch.int16) for _ in range(n)]
+    xs = [q.to(torch.float32) / 32768 for q in ps]
+    a16, a32 = cbr.stream(1, C), cbr.stream(1, C)
+    for q, xf in zip(ps, xs):
+        assert torch.equal(a16.encode_packed_rows_chunk(q)[0], a32.encode_packed_rows_chunk(xf)[0]), "the int16 and the float32 chunks differ"
+    print("one clip, chunks of %d blocks (%d per pass)  launches: int16 %d, float32 %d  the rows agree byte for byte"
+          % (k, n, a16.packed_chunk_launches(pcm16=True), a16.packed_chunk_launches()))
+    alternate([("encode_packed_rows_chunk(int16)", lambda: [a16.encode_packed_rows_chunk(q) for q in ps]),
+               ("encode_packed_rows_chunk(int16.to(float32) / 32768)",
+                lambda: [a16.encode_packed_rows_chunk(q.to(torch.float32) / 32768) for q in ps]),
+               ("encode_packed_rows_chunk(float32 resident)", lambda: [a16.encode_packed_rows_chunk(xf) for xf in xs])],
+              "us per chunk", 1e3 / n)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--pcm16", action="store_true", help="only int16 PCM to packed rows, one-shot and chunk by chunk")
     ap.add_argument("--stream", action="store_true", help="only the packed rows of a stream, chunk by chunk")
     ap.add_argument("--row-bits", type=int, default=1365, help="the row budget of the packed-rows section (64 kbit/s)")
     ap.add_argument("--only-rows", action="store_true", help="only the packed-rows section")
@@ -161,6 +213,8 @@ def main():
     ap.add_argument("--round-steps", type=int, default=30)
     a = ap.parse_args()
     B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    if a.pcm16:
+        return pcm16_rows(a)
     if a.stream:
         return stream_rows(a)
     if a.only_rows:

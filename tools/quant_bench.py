@@ -5,7 +5,12 @@ quantize() (AC_ENCODE_QUANT_NOFUSE=1, two launches) and the one launch of k_fwd_
 codes + sf out; then the two forms alternating over --rounds rounds, with the spread of the rounds.  Likewise at a row budget
 (--row-bits): encode_quantized_budget() -- encode() + k_quantize_budget, two launches -- against
 encode_quantized() of the codec with_row_budget(), the one launch of k_fwd_fast_qb.
-python tools/quant_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7] [--row-bits 1365]"""
+--pcm16 (this section alone): encode_quantized on int16 PCM, plain and at the row budget -- the one launch of k_fwd_fast_q16 /
+qb16, the two launches it replaces (AC_ENCODE_QUANT_NOFUSE=1: encode(int16) + the quantiser) and the float32 one launch on a
+resident float32 tensor of the same samples, compared bit for bit, then alternating over --rounds rounds of --round-steps
+(profiles/quant/quant_bench_pcm16.txt).
+python tools/quant_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7] [--row-bits 1365]
+                            [--pcm16 [--round-steps 30]]"""
 import argparse
 import os
 import sys
@@ -29,8 +34,44 @@ def timed(fn, steps, warmup):
     return e0.elapsed_time(e1) / steps
 
 
+def pcm16_rows(a):
+    B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    plain = audiocodec_amd.AudioCodec(48000, N)
+    x = (torch.rand((B, K * N, C), device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * 2 - 1)
+    p = torch.round(x * 32767).to(torch.int16)
+    x = p.to(torch.float32) / 32768
+    print("quant_bench --pcm16: B=%d K=%d N=%d C=%d  %s" % (B, K, N, C, torch.cuda.get_device_name()))
+    for label, codec in (("encode_quantized", plain), ("encode_quantized at %d bits" % a.row_bits, plain.with_row_budget(a.row_bits))):
+        def two_launches():
+            os.environ["AC_ENCODE_QUANT_NOFUSE"] = "1"   # (read per call)
+            try:
+                return codec.encode_quantized(p)
+            finally:
+                del os.environ["AC_ENCODE_QUANT_NOFUSE"]
+
+        one, two, flt = codec.encode_quantized(p), two_launches(), codec.encode_quantized(x)
+        assert all(torch.equal(g, r) for g, r in zip(one, two)) and all(torch.equal(g, r) for g, r in zip(one, flt)), "the forms differ"
+        del one, two, flt
+        forms = [("int16, %d launch" % codec.encode_quantized_launches(C, pcm16=True), lambda: codec.encode_quantized(p)),
+                 ("int16, two launches (encode + quantiser)", two_launches),
+                 ("float32 resident, %d launch" % codec.encode_quantized_launches(C), lambda: codec.encode_quantized(x))]
+        print("%s: the three forms agree bit for bit" % label)
+        runs = dict((n, []) for n, _ in forms)
+        for _ in range(a.rounds):
+            for n, fn in forms:
+                runs[n].append(timed(fn, a.round_steps, 1))
+        med = []
+        for n, _ in forms:
+            v = sorted(runs[n])
+            med.append(v[len(v) // 2])
+            print("  %-44s median %.3f ms  min %.3f  max %.3f  (%d alternating rounds of %d)" % (n, med[-1], v[0], v[-1], len(v), a.round_steps))
+        print("  one launch / two launches = %.3f   int16 / float32 = %.3f" % (med[0] / med[1], med[0] / med[2]))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--pcm16", action="store_true", help="only the int16 section")
+    ap.add_argument("--round-steps", type=int, default=30)
     ap.add_argument("--clips", type=int, default=256)
     ap.add_argument("--blocks", type=int, default=468)
     ap.add_argument("--filters", type=int, default=1024)
@@ -40,6 +81,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--row-bits", type=int, default=1365)
     a = ap.parse_args()
+    if a.pcm16:
+        return pcm16_rows(a)
     B, K, N, C = a.clips, a.blocks, a.filters, a.channels
     codec = audiocodec_amd.AudioCodec(48000, N)
     M = codec.psy.bark_bands_n
