@@ -73,6 +73,21 @@ def _put(bits, pos, val, width):
         bits[pos[m] + k] = (val[m] >> k) & 1
 
 
+def np_code_fields(w, off):
+    """Where a row's code fields lie: widths w [R, M] -> (pos [R, N]: first bit of bin i's field, counted from the row's
+    start; width [R, N]; keep [R, N]: the bin's band is stored)."""
+    off = np.asarray(off, dtype=np.int64)
+    M = len(off) - 1
+    L = np.diff(off)
+    st = _stored(w)
+    cb = np.where(st, w * L, 0)
+    boff = np.cumsum(cb, axis=1) - cb
+    base = 5 * M + 8 * st.sum(axis=1, keepdims=True)
+    band = np.repeat(np.arange(M), L)
+    i = np.arange(int(off[-1]))
+    return base + boff[:, band] + w[:, band] * (i - off[band]), w[:, band], st[:, band]
+
+
 def np_pack(codes, sf, off):
     """codes int16 [B, F, N, C], sf int8 [B, F, M, C] -> (data uint8 [nbytes], index int64 [B, F, C])."""
     codes, sf = np.asarray(codes, dtype=np.int16), np.asarray(sf, dtype=np.int8)
@@ -95,14 +110,9 @@ def np_pack(codes, sf, off):
     cnt = np.cumsum(st, axis=1) - st
     _put(bits, (start + 5 * M + 8 * cnt)[st], (sr.astype(np.int64) & 0xFF)[st], np.full(int(st.sum()), 8))
     # 3. codes of the stored bands
-    cb = np.where(st, w * L, 0)
-    boff = np.cumsum(cb, axis=1) - cb
-    base = start + 5 * M + 8 * st.sum(axis=1, keepdims=True)
-    band = np.repeat(np.arange(M), L)
-    i = np.arange(N)
-    pos = base + boff[:, band] + w[:, band] * (i - off[band])
-    keep = st[:, band]
-    _put(bits, pos[keep], zz(cr)[keep], w[:, band][keep])
+    pos, wb, keep = np_code_fields(w, off)
+    pos = start + pos
+    _put(bits, pos[keep], zz(cr)[keep], wb[keep])
     data = np.packbits(bits, bitorder="little")
     return data, index.reshape(B, F, C)
 

@@ -111,9 +111,9 @@ def test_encoded_signals(C, B, K, bitrate, monkeypatch):
     _hold_to_composition(codec, data, index)
 
 
-def _designed_rows(C):
+def _designed_rows(C, sample_rate=48000):
     """Rows of every width 0..16 and 31 with the extreme codes, rows of the least and of the greatest length between them."""
-    psy = audiocodec_amd.PsychoacousticModel(48000, filter_bands_n=1024, bark_bands_n=64)
+    psy = audiocodec_amd.PsychoacousticModel(sample_rate, filter_bands_n=1024, bark_bands_n=64)
     off = psy.scale_band_offsets
     B, F = 5, 40
     codes, sf = designed(np.random.default_rng(17 + C), off, B, F, C)

@@ -230,17 +230,23 @@ def test_dequantize_bit_exact_on_random_codes():
     np.testing.assert_array_equal(Xh.view(np.uint32)[keep], ref.view(np.uint32)[keep])
 
 
-@gpu
-@pytest.mark.parametrize("N,C,launches", [(1024, 2, 1), (1024, 1, 1), (2048, 2, 1), (2048, 1, 1), (960, 2, 2), (1024, 3, 2),
-                                          (512, 1, 2)])
-def test_decode_quantized_bit_equal(N, C, launches):
-    codec, _, X, thr = _encoded(N, C, B=3, K=7)
+def decode_quantized_bit_equal(N, C, launches, sr=48000):
+    """The body of test_decode_quantized_bit_equal at a sample rate; returns (codec, codes, sf) for further checks."""
+    codec, _, X, thr = _encoded(N, C, B=3, K=7, sr=sr)
     assert codec.decode_quantized_launches(C) == launches
     codes, sf = codec.psy.quantize(X, thr)
     Xh = codec.psy.dequantize(codes, sf)
     assert torch.equal(codec.decode_quantized(codes, sf), codec.decode(Xh))
     if N in (1024, 2048, 960):   # (16-bit PCM sizes of both paths)
         assert torch.equal(codec.decode_quantized(codes, sf, pcm16=True), codec.decode(Xh, pcm16=True))
+    return codec, codes, sf
+
+
+@gpu
+@pytest.mark.parametrize("N,C,launches", [(1024, 2, 1), (1024, 1, 1), (2048, 2, 1), (2048, 1, 1), (960, 2, 2), (1024, 3, 2),
+                                          (512, 1, 2)])
+def test_decode_quantized_bit_equal(N, C, launches):
+    decode_quantized_bit_equal(N, C, launches)
 
 
 @gpu
