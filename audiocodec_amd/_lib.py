@@ -19,7 +19,8 @@ AC_EMIT_NOISY, AC_EMIT_DB_NORM, AC_EMIT_CODES, AC_EMIT_PACKED = 1, 2, 4, 8   # f
 AC_PACKED = 16   # spectrum-side format of ac_stream_encode_typed / ac_stream_inverse_typed: packed rows
 AC_IN_PCM16 = 32   # x is int16 PCM: flag of ac_encode_fused_ex beside AC_EMIT_CODES / AC_EMIT_PACKED, and of
                    # ac_stream_encode_typed's dtype beside AC_PACKED
-AC_PACK_ROWS_MAX_BITS = 16384   # the largest row budget AC_EMIT_PACKED serves in one launch (the header's macro)
+AC_IN_PACKED = 64  # x is one ac_packed_rows: flag of ac_encode_fused_ex beside AC_EMIT_PACKED alone (transrating)
+AC_PACK_ROWS_MAX_BITS = 16384  # the largest row budget AC_EMIT_PACKED serves in one launch (the header's macro)
 WINDOW_IDS = {"vorbis": 0, "sine": 1}   # anything else -> 2 (rectangular), mdctransformer.py:199-211
 WINDOW_RECT = 2
 
@@ -118,6 +119,7 @@ PROTOTYPES = {
     "ac_encode_quantized_launches_pcm16": (c_int, [c_void_p, c_void_p, c_int]),
     "ac_encode_packed_launches_pcm16": (c_int, [c_void_p, c_void_p, c_int]),
     "ac_stream_packed_launches_pcm16": (c_int, [c_void_p, c_void_p]),
+    "ac_transrate_launches": (c_int, [c_void_p, c_int]),
     "ac_pack_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ac_pack_index": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ac_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
@@ -139,6 +141,11 @@ class PackedRows(ctypes.Structure):
 class PackedOut(ctypes.Structure):
     """``ac_packed_out``: what ``ac_encode_fused_ex`` takes for ``out0`` under ``AC_EMIT_PACKED``."""
     _fields_ = [("data", c_void_p), ("row_bytes", ctypes.c_int64), ("fits", c_void_p)]
+
+
+class QuantizedRows(ctypes.Structure):
+    """``ac_quantized_rows``: what ``ac_quantize_budget`` takes for ``X`` when ``thr`` is NULL (the requantiser)."""
+    _fields_ = [("codes", c_void_p), ("sf", c_void_p)]
 
 
 class StreamPackedIn(ctypes.Structure):

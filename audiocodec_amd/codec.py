@@ -394,6 +394,71 @@ class AudioCodec:
         data, fits = _pack_rows_of_spectra(self.psy, X, thr, index, rb)
         return data, index, fits
 
+    # ---- transrating packed rows (extension) ----------------------------------------------
+    def transrate_packed_rows_launches(self, channels_n=2, device=None):
+        """Library launches :meth:`transrate_packed_rows` takes for rows of ``channels_n`` channels
+        (``ac_transrate_launches``): 1 = one kernel reads, requantises and packs each row (filters_n = 1024, bark_bands_n =
+        64, a budget of at most ``_lib.AC_PACK_ROWS_MAX_BITS``; any channel count), else 3: :meth:`PsychoacousticModel.unpack`,
+        :meth:`PsychoacousticModel.requantize_to_budget` and the packer (everywhere while ``AC_TRANSRATE_NOFUSE=1`` is set:
+        read per call).  0 on a codec without a row budget."""
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return int(self._lib.ac_transrate_launches(self.psy._plan(dev), int(channels_n)))
+
+    def transrate_packed_rows(self, data, index, return_offset=False):
+        """On a codec made by :meth:`with_bitrate` / :meth:`with_row_budget`: packed rows at a higher bitrate -> the same
+        frames at this codec's, without decoding.  data uint8 [nbytes], index int64 [B, F, C] -> (data' uint8
+        [B*F*C*row_bytes], index' int64 [B, F, C], fits' bool [B, F, C]), and offset int16 [B, F, C] with
+        ``return_offset=True`` -- the fixed-stride layout of :meth:`encode_packed_rows`.
+
+        ``index`` holds any row starts: :meth:`encode_packed` output, the rows of :meth:`encode_packed_rows`, a slice of
+        frames, a chunk's rows of ``encode_packed_rows_chunk``; rows are read as :meth:`PsychoacousticModel.unpack` reads them,
+        damaged ones included.  Each row's stored scale factors are raised by the smallest offset in [0, 254] at which the
+        row is at most ``row_bits`` long and its codes are quantised again at those steps
+        (:meth:`PsychoacousticModel.requantize_to_budget`): a row that fits already keeps its fields.  The masking model,
+        the filter bank and the frame grid are untouched; the codec's own ``min_offset`` is not used (it is relative to a
+        threshold the rows no longer carry).  A row longer than its slot at offset 254 is stored as the marked row, ``fits``
+        False.  ``fits`` reports only whether this call's row fitted: a marked input row comes out as the same marked
+        bytes with ``fits`` True.  One launch where :meth:`transrate_packed_rows_launches` is 1, else the composition: the
+        same bytes.  The size of ``data'`` is known before the call: it never synchronises with the device, only enqueues on
+        the current stream, and can be captured in a graph.  Raising a bitrate is not possible.  float32 only."""
+        _host.require_float32(self.compute_dtype, "transrate_packed_rows")
+        if self.row_bits is None:
+            raise ValueError("transrate_packed_rows needs a codec with a row budget: make one with with_bitrate() or "
+                             "with_row_budget()")
+        data = self.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
+        index = self.psy._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
+        B, F, C = index.shape
+        dev, rb = data.device, self.row_bytes
+        rows = B * F * C
+        index_out = (torch.arange(rows, dtype=torch.int64, device=dev) * rb).view(B, F, C)
+        if rows == 0:
+            out = (torch.empty((0,), dtype=torch.uint8, device=dev), index_out, torch.empty((B, F, C), dtype=torch.bool, device=dev))
+            return out + (torch.empty((B, F, C), dtype=torch.int16, device=dev),) if return_offset else out
+        psy = self.psy._plan(dev)
+        if self._lib.ac_transrate_launches(psy, C) == 1:
+            out_data = torch.empty((rows * rb,), dtype=torch.uint8, device=dev)
+            fits = torch.empty((B, F, C), dtype=torch.bool, device=dev)
+            offset = torch.empty((B, F, C), dtype=torch.int16, device=dev) if return_offset else None
+            src = _lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr())
+            dst = _lib.PackedOut(out_data.data_ptr(), rb, fits.data_ptr())
+            with _host.on_device(dev):
+                _lib.check(self._lib.ac_encode_fused_ex(self.mdct._plan(dev), psy, ctypes.addressof(src), None, None, None, 0.0,
+                                                        _lib.AC_IN_PACKED | _lib.AC_EMIT_PACKED, ctypes.addressof(dst),
+                                                        _host.ptr(offset) if return_offset else None, 0, B, F - 1, C,
+                                                        _host.stream_ptr(dev)))
+            return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
+        # the composition: the rows unpacked, requantised at the budget from offset 0, rows longer than their slot marked, then
+        # the packer at the fixed row starts (on plain allocations: nothing here may wait for the device)
+        codes, sf = self.psy.unpack(data, index)
+        codes, sf, offset, bits = self.psy.requantize_to_budget(codes, sf, self.row_bits, 0)
+        fits = bits <= 8 * rb
+        sf.masked_fill_(~fits.unsqueeze(2), -128)   # width 31 follows whatever the codes are
+        out_data = torch.zeros((rows * rb,), dtype=torch.uint8, device=dev)
+        with _host.on_device(dev):
+            _lib.check(self._lib.ac_pack(psy, _host.ptr(codes), _host.ptr(sf), _host.ptr(index_out), _host.ptr(out_data), B, F, C,
+                                         _host.stream_ptr(dev)))
+        return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
+
     # ---- rate control per clip (extension; DESIGN.md section 8d) ------------------------------------------------
     def clip_bits_for_bitrate(self, bits_per_second, frames_n, channels_n):
         """The clip budget of a per-channel bitrate: frames_n * channels_n rows of :meth:`row_bits_for_bitrate` bits each,

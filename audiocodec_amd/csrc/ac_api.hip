@@ -839,11 +839,65 @@ static int encode_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
                                    (hipStream_t)stream);
 }
 
+// whether packed rows are transrated in one launch (k_transrate_p); AC_TRANSRATE_NOFUSE=1 sends every configuration down the
+// composition (A/B measurements: read per call, so that one process can time both forms)
+static bool transrate_fuses(const ac_psy_plan* psy) {
+  const char* e = getenv("AC_TRANSRATE_NOFUSE");
+  if (e && atoi(e) == 1) return false;
+  return !g_force_generic && transrate_serves(psy);
+}
+
+int ac_transrate_launches(const ac_psy_plan* psy, int C) {
+  if (!psy || C < 1 || !psy->row_bits) return 0;
+  return transrate_fuses(psy) ? 1 : 3;   // ac_unpack, ac_quantize_budget (thr == NULL), ac_pack
+}
+
+// ac_encode_fused_ex with AC_IN_PACKED | AC_EMIT_PACKED: rows [B,K+1,C] of `in` to slots of `out` at the plan's row budget
+static int transrate_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const ac_packed_rows* in, const float* X,
+                                 const float* t, const float* thr, const ac_packed_out* out, int16_t* offset, int B, int K,
+                                 int C, void* stream) {
+  AC_REQUIRE(mdct != nullptr && psy != nullptr, "plan is NULL");
+  AC_REQUIRE(mdct->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", mdct->N, psy->N);
+  AC_REQUIRE(mdct->device == psy->device, "plans live on different devices");
+  int st = check_dims(B, K, C);
+  if (!st) st = check_quant(psy, B, K + 1, C);
+  if (st) return st;
+  AC_REQUIRE(psy->row_bits != 0, "AC_IN_PACKED needs a plan with a row budget (ac_psy_plan_with_row_budget)");
+  AC_REQUIRE(X == nullptr && t == nullptr && thr == nullptr, "AC_IN_PACKED writes no X, t or thr: they must be NULL");
+  AC_REQUIRE(in != nullptr, "AC_IN_PACKED without its ac_packed_rows (x)");
+  AC_REQUIRE(out != nullptr, "AC_IN_PACKED without its ac_packed_out (out0)");
+  const ac_packed_rows rows = *in;
+  const ac_packed_out po = *out;
+  const int64_t row_bytes = (int64_t)((psy->row_bits + 31) / 32) * 4;
+  AC_REQUIRE(po.row_bytes == row_bytes, "row_bytes (%lld) is not the plan's ceil(%d / 32) * 4 = %lld", (long long)po.row_bytes,
+             psy->row_bits, (long long)row_bytes);
+  AC_REQUIRE(rows.nbytes >= 0, "negative nbytes (%lld)", (long long)rows.nbytes);
+  if (B == 0 || C == 0) return AC_OK;
+  if (!transrate_fuses(psy)) {
+    set_error("AC_IN_PACKED: no kernel transrates packed rows in one launch for filters_n = %d, bark_bands_n = %d, row budget "
+              "%d here (ac_transrate_launches() != 1): use the composition -- ac_unpack, ac_quantize_budget with thr == NULL "
+              "at kmin 0, then ac_pack at row starts r * row_bytes into zero-filled data", psy->N, psy->M, psy->row_bits);
+    return AC_EUNSUPPORTED;
+  }
+  AC_REQUIRE(rows.index != nullptr && po.data != nullptr && po.fits != nullptr, "NULL tensor pointer");
+  AC_REQUIRE(rows.data != nullptr || rows.nbytes == 0, "data is NULL");
+  AC_REQUIRE_ALIGNED(rows.data, rows.index, po.data, offset);
+  DeviceGuard guard(psy->device);
+  return launch_transrate(psy, rows.data, rows.nbytes, rows.index, po.data, row_bytes, po.fits, offset,
+                          (long long)B * (K + 1) * C, (hipStream_t)stream);
+}
+
 int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
                        float drown, int flags, void* noisy_v, void* db_norm_v, uint64_t seed, int B, int K, int C,
                        void* stream) {
-  AC_REQUIRE((flags & ~(AC_EMIT_NOISY | AC_EMIT_DB_NORM | AC_EMIT_CODES | AC_EMIT_PACKED | AC_IN_PCM16)) == 0, "unknown flags %#x",
-             flags);
+  AC_REQUIRE((flags & ~(AC_EMIT_NOISY | AC_EMIT_DB_NORM | AC_EMIT_CODES | AC_EMIT_PACKED | AC_IN_PCM16 | AC_IN_PACKED)) == 0,
+             "unknown flags %#x", flags);
+  if (flags & AC_IN_PACKED) {
+    AC_REQUIRE(flags == (AC_IN_PACKED | AC_EMIT_PACKED),
+               "AC_IN_PACKED goes with AC_EMIT_PACKED alone (got %#x): packed rows are transrated to packed rows", flags);
+    return transrate_packed_rows(mdct, psy, reinterpret_cast<const ac_packed_rows*>(x), X, t, thr,
+                                 static_cast<const ac_packed_out*>(noisy_v), static_cast<int16_t*>(db_norm_v), B, K, C, stream);
+  }
   // AC_IN_PCM16: x is int16, under AC_EMIT_CODES or AC_EMIT_PACKED only
   const bool pcm16 = (flags & AC_IN_PCM16) != 0;
   const int emit = flags & ~AC_IN_PCM16;
@@ -1181,6 +1235,18 @@ int ac_quantize_budget(const ac_psy_plan* psy, const float* X, const float* thr,
   AC_REQUIRE(kmin >= -254 && kmin <= 254, "kmin (%d) outside [-254, 254]", kmin);
   AC_REQUIRE(row_bits_per_row != nullptr || row_bits >= 5 * psy->M,
              "row_bits (%d) below 5 * bark_bands_n = %d, the length of a row that stores no band", row_bits, 5 * psy->M);
+  if (thr == nullptr && X != nullptr) {   // X addresses one ac_quantized_rows: the requantiser
+    AC_REQUIRE(kmin >= 0, "kmin (%d) outside [0, 254]: thr is NULL (requantising), and an offset below 0 cannot restore what "
+               "the first quantiser dropped", kmin);
+    if (B == 0 || F == 0 || C == 0) return AC_OK;
+    const ac_quantized_rows in = *reinterpret_cast<const ac_quantized_rows*>(X);
+    AC_REQUIRE(in.codes != nullptr && in.sf != nullptr && codes != nullptr && sf != nullptr && offset != nullptr,
+               "NULL tensor pointer");
+    AC_REQUIRE_ALIGNED(in.codes, in.sf, codes, sf, offset, row_bits_per_row, row_bits_out);
+    DeviceGuard guard(psy->device);
+    return launch_requantize_budget(psy, in.codes, in.sf, row_bits, row_bits_per_row, kmin, codes, sf, offset, row_bits_out, B,
+                                    F, C, (hipStream_t)stream);
+  }
   if (B == 0 || F == 0 || C == 0) return AC_OK;
   AC_REQUIRE(X != nullptr && thr != nullptr && codes != nullptr && sf != nullptr && offset != nullptr, "NULL tensor pointer");
   AC_REQUIRE_ALIGNED(X, thr, codes, sf, offset, row_bits_per_row, row_bits_out);

@@ -406,6 +406,18 @@ int launch_dequantize(const ac_psy_plan* p, const int16_t* codes, const int8_t* 
 int launch_quantize_budget(const ac_psy_plan* p, const float* X, const float* thr, int budget, const int32_t* row_budget,
                            int kmin, int16_t* codes, int8_t* sf, int16_t* offset, int32_t* row_bits, int B, int F, int C,
                            hipStream_t s);
+// the requantiser (ac_requant.hip): launch_quantize_budget's search on rows that are already quantised
+// -- the stored sf for sf0, fp32(code * step(sf)) for X; kmin in [0, 254]; the inputs must not overlap the outputs
+int launch_requantize_budget(const ac_psy_plan* p, const int16_t* codes_in, const int8_t* sf_in, int budget,
+                             const int32_t* row_budget, int kmin, int16_t* codes, int8_t* sf, int16_t* offset,
+                             int32_t* row_bits, int B, int F, int C, hipStream_t s);
+// ... from packed rows to fixed-stride packed rows at the plan's row budget in one launch (k_transrate_p, ac_transrate.hip):
+// rows of data [nbytes] at index [rows] -> out [rows row_bytes], fits [rows], offset [rows] (or NULL); the bytes of
+// launch_unpack, launch_requantize_budget(row_bits, nullptr, 0), rows longer than the slot marked, launch_pack at
+// r row_bytes into zero-filled data.  Serves float32 plans with N = 1024, M = 64 and a budget of at most kPackRowsMaxBits
+bool transrate_serves(const ac_psy_plan* psy);
+int launch_transrate(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes, const int64_t* index, uint8_t* out,
+                     int64_t row_bytes, uint8_t* fits, int16_t* offset, long long rows, hipStream_t s);
 // rate control per clip (ac_clip_rate.hip): one budget for the F*C rows of a clip (clip_budget [B] int64,
 // or the scalar budget where it is NULL); row_bits, clip_offset and clip_bits may be NULL; scratch of
 // clip_budget_scratch_bytes(p, B, F*C) bytes

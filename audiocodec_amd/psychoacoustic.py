@@ -448,17 +448,7 @@ class PsychoacousticModel:
         X, thr = self._check_quant_inputs(mdct_amplitudes, masking_threshold)
         B, F, N, C = X.shape
         self._check_min_offset(min_offset)
-        per_row = None
-        scalar = 0
-        if isinstance(row_bits, torch.Tensor):
-            per_row = self._check_quant_tensor(row_bits, "row_bits", torch.int32, (B, F, C), X.device, ndim=3)
-        elif isinstance(row_bits, (int, np.integer)) and not isinstance(row_bits, bool):
-            if not 5 * self.bark_bands_n <= int(row_bits) <= 2 ** 31 - 1:
-                raise ValueError("row_bits (%d) below 5 * bark_bands_n = %d, the length of a row that stores no band, or "
-                                 "above int32" % (row_bits, 5 * self.bark_bands_n))
-            scalar = int(row_bits)
-        else:
-            raise TypeError("row_bits must be an int or an int32 tensor [B, F, C], got %s" % type(row_bits).__name__)
+        scalar, per_row = self._check_row_bits(row_bits, (B, F, C), X.device)
         dev = X.device
         codes, sf, offset, bits = self._alloc_codes(X, rate=True)
         with _host.on_device(dev):
@@ -467,6 +457,48 @@ class PsychoacousticModel:
                 int(min_offset), _host.ptr(codes), _host.ptr(sf), _host.ptr(offset), _host.ptr(bits), B, F, C,
                 _host.stream_ptr(dev)))
         return codes, sf, offset, bits
+
+    def _check_row_bits(self, row_bits, shape, device):
+        """A row budget as the entry points take it: (scalar, None) for an int, (0, int32 tensor of ``shape``) per row."""
+        if isinstance(row_bits, torch.Tensor):
+            return 0, self._check_quant_tensor(row_bits, "row_bits", torch.int32, shape, device, ndim=3)
+        if isinstance(row_bits, (int, np.integer)) and not isinstance(row_bits, bool):
+            if not 5 * self.bark_bands_n <= int(row_bits) <= 2 ** 31 - 1:
+                raise ValueError("row_bits (%d) below 5 * bark_bands_n = %d, the length of a row that stores no band, or "
+                                 "above int32" % (row_bits, 5 * self.bark_bands_n))
+            return int(row_bits), None
+        raise TypeError("row_bits must be an int or an int32 tensor [B, F, C], got %s" % type(row_bits).__name__)
+
+    # ---- requantiser (extension; DESIGN.md section 8e) --------------------------------------------------
+    def requantize_to_budget(self, codes, sf, row_bits, min_offset=0):
+        """:meth:`quantize_to_budget` on rows that are already quantised: codes int16 [B, F, N, C], sf int8 [B, F, M, C] ->
+        (codes, sf, offset int16 [B, F, C], row_bits_out int32 [B, F, C]) in new tensors.
+
+        The stored scale factors stand where the quantiser's own stood and ``fp32(code * 2^(sf/4))`` where the spectrum
+        stood, so no spectrum and no threshold is needed: every scale factor of a row is raised by the smallest offset in
+        ``[min_offset, 254]`` at which the packed row is at most ``row_bits`` long, and the codes are quantised again at
+        those steps.  A row that fits already keeps offset 0 and comes back as it was (a code of -32768 as -32767).
+        ``row_bits`` as in :meth:`quantize_to_budget`; ``min_offset`` in [0, 254] -- an offset below 0 cannot restore
+        what the first quantiser dropped.  The input need not be canonical: codes under ``sf = -128`` count as 0 and an
+        all-zero band as ``sf = 0``, as :meth:`unpack` returns them.  One launch; not differentiable; float32 only."""
+        _host.require_float32(self.compute_dtype, "the quantiser")
+        self._check_min_offset(min_offset)
+        if int(min_offset) < 0:
+            raise ValueError("min_offset (%d) outside [0, 254]: requantising cannot lower a scale factor" % min_offset)
+        codes, sf = self._check_codes(codes, sf)
+        B, F, N, C = codes.shape
+        scalar, per_row = self._check_row_bits(row_bits, (B, F, C), codes.device)
+        dev = codes.device
+        out_codes, out_sf, offset, bits = self._alloc_codes(codes, rate=True)
+        rows = _lib.QuantizedRows(codes.data_ptr(), sf.data_ptr())
+        if codes.numel() == 0:
+            return out_codes, out_sf, offset, bits
+        with _host.on_device(dev):
+            _lib.check(self._lib.ac_quantize_budget(
+                self._plans.get(dev), ctypes.addressof(rows), None, scalar, _host.ptr(per_row) if per_row is not None else None,
+                int(min_offset), _host.ptr(out_codes), _host.ptr(out_sf), _host.ptr(offset), _host.ptr(bits), B, F, C,
+                _host.stream_ptr(dev)))
+        return out_codes, out_sf, offset, bits
 
     # ---- rate control per clip (extension; DESIGN.md section 8d) ---------------------------------------
     def quantize_to_clip_budget(self, mdct_amplitudes, masking_threshold, clip_bits, min_offset=0):

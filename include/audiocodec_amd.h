@@ -51,7 +51,8 @@ extern "C" {
                           * ac_quantize_clip_budget, ac_clip_budget_scratch_bytes; in the plan: ac_psy_plan_with_row_budget,
                           * ac_psy_plan_row_budget; packed rows in a stream: AC_PACKED, ac_stream_packed_in,
                           * ac_stream_packed_launches; 16-bit PCM into the quantising encodes: AC_IN_PCM16,
-                          * ac_*_launches_pcm16); additions only, so the number stays.
+                          * ac_*_launches_pcm16; rows to a lower budget without decoding: ac_quantized_rows, AC_IN_PACKED,
+                          * ac_transrate_launches); additions only, so the number stays.
                           * 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
                           * with a 5-smooth half up to 8192, float32); masking model for general band layouts up to 4096 bins.
                           * 0.1.7: only the ac_* entry points are exported; ac_stream_settle (home buffers for the streaming state);
@@ -255,9 +256,22 @@ AC_API int ac_encode_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
  *     by the quantiser (the budgeted one at a plan with a row budget), X, t and thr required, and AC_EUNSUPPORTED where
  *     16-bit PCM has no encode.  AC_EMIT_PACKED | AC_IN_PCM16: ONE launch where ac_encode_packed_launches_pcm16 returns 1,
  *     AC_EUNSUPPORTED elsewhere.
+ *   AC_IN_PACKED     transrating, valid only as AC_IN_PACKED | AC_EMIT_PACKED: packed rows in, fixed-
+ *     stride packed rows at the plan's (lower) row budget out, in ONE launch that never decodes.  x addresses one
+ *     ac_packed_rows (a host struct of device pointers, read during the call) whose index is [B,K+1,C] -- any int64 row
+ *     starts, read as ac_unpack reads them, damaged rows included; out0 addresses one ac_packed_out as under AC_EMIT_PACKED;
+ *     out1 is NULL or int16_t* offset [B,K+1,C]; X, t and thr must be NULL; drown and seed are ignored.  The mdct plan is
+ *     checked as in every other form (same filters_n and device) and not used.  Slot r of data holds what this composition
+ *     writes: ac_unpack, ac_quantize_budget in its thr == NULL form at the plan's row_bits with kmin 0 (the plan's own kmin is
+ *     not used: it is relative to a threshold the rows no longer carry), sf = -128 in rows with row_bits_out > 8 row_bytes,
+ *     ac_pack at r row_bytes into zero-filled data.  fits[r] reports only whether this call's row fitted: a marked input row
+ *     (every width 31) comes out as the same marked bytes with fits[r] = 1.  offset[r] is the row's offset of that
+ *     ac_quantize_budget call.  Any other combination with the bit, or a plan without a row budget, is AC_EINVAL; a refused
+ *     call writes nothing.  Served where ac_transrate_launches returns 1; AC_EUNSUPPORTED elsewhere (run the composition).
+ *     The input and output buffers must not overlap.
  * out0 / out1: float* noisy, float* db_norm under AC_EMIT_NOISY / AC_EMIT_DB_NORM; int16_t* codes, int8_t* sf under
- * AC_EMIT_CODES; ac_packed_out*, NULL under AC_EMIT_PACKED. */
-enum { AC_EMIT_NOISY = 1, AC_EMIT_DB_NORM = 2, AC_EMIT_CODES = 4, AC_EMIT_PACKED = 8, AC_IN_PCM16 = 32 };
+ * AC_EMIT_CODES; ac_packed_out*, NULL under AC_EMIT_PACKED (NULL or int16_t* offset with AC_IN_PACKED). */
+enum { AC_EMIT_NOISY = 1, AC_EMIT_DB_NORM = 2, AC_EMIT_CODES = 4, AC_EMIT_PACKED = 8, AC_IN_PCM16 = 32, AC_IN_PACKED = 64 };
 /* The largest row budget the one launch of AC_EMIT_PACKED serves: a wave stages both rows of its frame pair in the 4 KB of
  * its LDS buffer that the masking model has left, 2 KB = 16384 bits each. */
 #define AC_PACK_ROWS_MAX_BITS 16384
@@ -285,6 +299,12 @@ AC_API int ac_encode_packed_launches(const ac_mdct_plan* mdct, const ac_psy_plan
  * 1), else the launches of the composition.  AC_ENCODE_QUANT_NOFUSE=1 / AC_ENCODE_PACKED_NOFUSE=1 apply (read per call). */
 AC_API int ac_encode_quantized_launches_pcm16(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C);
 AC_API int ac_encode_packed_launches_pcm16(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C);
+/* Library launches of transrating rows of C channels to the plan's row budget: 1 = ac_encode_fused_ex with AC_IN_PACKED |
+ * AC_EMIT_PACKED serves it (float32 plans with filters_n = 1024, bark_bands_n = 64 and a row budget of at most
+ * AC_PACK_ROWS_MAX_BITS; any C, rows being independent), else 3: ac_unpack, ac_quantize_budget's thr == NULL form and ac_pack
+ * of the composition above (also everywhere while AC_TRANSRATE_NOFUSE=1 is set in the environment: read per call).  0 for a
+ * NULL plan, C < 1, or a plan without a row budget.  The bytes do not depend on it. */
+AC_API int ac_transrate_launches(const ac_psy_plan* psy, int C);
 
 /* 16-bit PCM at the boundary (extension; the reference takes float PCM in [-1, 1] only, mdctransformer.py:104):
  * x = pcm / 32768 on the way in; on the way out pcm = 0 if x is NaN else clamp(rint(fp32(32768 x)), -32768, 32767), rint
@@ -363,7 +383,16 @@ AC_API int ac_unpack(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes
  *   row_bits_out int32 [B,F,C] (may be NULL) = bits(offset), where offset is the smallest k in [kmin, 254] with
  *   bits(k) <= the row's budget, else 254 (a budget not met shows as row_bits_out > budget).  The budget is
  *   row_bits_per_row[b,f,c] (int32 [B,F,C], entries not checked) or, where that is NULL, row_bits (>= 5M).  kmin = 0 with a
- *   budget of 16N + 13M gives ac_quantize's output.  kmin in [-254, 254]; plans as ac_quantize. */
+ *   budget of 16N + 13M gives ac_quantize's output.  kmin in [-254, 254]; plans as ac_quantize.
+ *   With thr == NULL, X addresses one ac_quantized_rows (a host struct of device pointers, read during the call) and the call
+ *   requantises: the row's stored scale factors stand for sf0 and fp32(code * step(sf)) for X, so the
+ *   rules above run on a row that is already quantised -- codes under sf = -128 count as 0 and an all-zero band as sf 0, as
+ *   ac_unpack returns them.  At an offset of 0 a row comes back as it was (-32768 as -32767).  kmin in [0, 254] in this form:
+ *   an offset below 0 cannot restore what the first quantiser dropped.  The inputs must not overlap the outputs. */
+typedef struct ac_quantized_rows {
+  const int16_t* codes; /* [B,F,N,C] (device) */
+  const int8_t* sf;     /* [B,F,M,C] (device) */
+} ac_quantized_rows;
 AC_API int ac_quantize_budget(const ac_psy_plan* psy, const float* X, const float* thr, int row_bits,
                               const int32_t* row_bits_per_row, int kmin, int16_t* codes, int8_t* sf, int16_t* offset,
                               int32_t* row_bits_out, int B, int F, int C, void* stream);

@@ -16,7 +16,8 @@ the one launch on int16 (k_fwd_fast_qp16 / qps16), the conversion to(float32) / 
 caller did before), and the float32 one launch on a resident float32 tensor; compared byte for byte, then alternating
 (profiles/pack/pack_bench_pcm16.txt).
 python tools/pack_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7] [--round-steps 30]
-                           [--row-bits 1365] [--only-rows] [--stream] [--pcm16]"""
+                           [--row-bits 1365] [--only-rows] [--stream] [--pcm16] [--transrate [--targets 1365 682]]
+--transrate: rows at 2730 bits transrated to each of --targets (transrate_rows(); profiles/pack/pack_bench_transrate.txt)."""
 import argparse
 import ctypes
 import os
@@ -197,8 +198,80 @@ def pcm16_rows(a):
               "us per chunk", 1e3 / n)
 
 
+def transrate_rows(a):
+    """Transrating: rows of encode_packed_rows at --row-bits (2730 with --transrate) to each budget of
+    --targets.  (a) transrate_packed_rows in its one launch; (b) its composition (AC_TRANSRATE_NOFUSE=1, read per call);
+    (c) decode_packed + encode_packed_rows at the target, what a caller did before; (d) decode_packed alone, the floor of
+    reading the rows.  Compared byte for byte first, then alternating, --rounds rounds of --round-steps.  Also the share of
+    rows at offset 0 and the mean offset, and on one small batch the RMS error against the spectrum X of transrated rows
+    beside rows encoded at the target."""
+    B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    base = audiocodec_amd.AudioCodec(48000, N)
+    src = base.with_row_budget(a.row_bits)
+    x = (torch.rand((B, K * N, C), device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * 2 - 1)
+    data, index, _ = src.encode_packed_rows(x)
+    rows = index.numel()
+    print("transrate: B=%d K=%d N=%d C=%d  rows=%d at %d bits (%.1f MB)  %s"
+          % (B, K, N, C, rows, a.row_bits, data.numel() / 1e6, torch.cuda.get_device_name()))
+    for R2 in a.targets:
+        dst = base.with_row_budget(R2)
+
+        def composition():
+            os.environ["AC_TRANSRATE_NOFUSE"] = "1"   # (read per call)
+            try:
+                return dst.transrate_packed_rows(data, index, True)
+            finally:
+                del os.environ["AC_TRANSRATE_NOFUSE"]
+
+        def recode():
+            return dst.encode_packed_rows(dst.decode_packed(data, index))   # (the decoded signal as it comes: K + 2 blocks)
+
+        one, two = dst.transrate_packed_rows(data, index, True), composition()
+        assert all(torch.equal(g, r) for g, r in zip(one, two)), "the two forms differ"
+        off = one[3].to(torch.float32)
+        print("-> %d bits per row, row_bytes %d (%.1f MB)  launches=%d  %d rows do not fit  offset 0: %.1f %% of the rows  mean "
+              "offset %.2f  max %d  the one launch and the composition agree byte for byte"
+              % (R2, dst.row_bytes, rows * dst.row_bytes / 1e6, dst.transrate_packed_rows_launches(C), int((~one[2]).sum()),
+                 100.0 * float((off == 0).float().mean()), float(off.mean()), int(off.max())))
+        del one, two, off
+        forms = [("(a) transrate_packed_rows, %d launch" % dst.transrate_packed_rows_launches(C),
+                  lambda: dst.transrate_packed_rows(data, index)),
+                 ("(b) transrate_packed_rows, composition", composition),
+                 ("(c) decode_packed + encode_packed_rows", recode),
+                 ("(d) decode_packed alone", lambda: dst.decode_packed(data, index))]
+        runs = dict((n, []) for n, _ in forms)
+        for _ in range(a.rounds):
+            for n, fn in forms:
+                runs[n].append(timed(fn, a.round_steps, 1))
+        med = []
+        for n, _ in forms:
+            v = sorted(runs[n])
+            med.append(v[len(v) // 2])
+            print("  %-42s median %.3f ms  min %.3f  max %.3f  (%d alternating rounds of %d)" % (n, med[-1], v[0], v[-1], len(v), a.round_steps))
+        print("  (a) / (b) = %.3f   (a) / (c) = %.3f   (a) / (d) = %.3f" % (med[0] / med[1], med[0] / med[2], med[0] / med[3]))
+    # an observation, not a criterion: the error of transrated rows against the spectrum beside rows encoded at the target
+    xs = x[:4, :16 * N].contiguous()
+    del x, data, index
+    X = base.encode(xs)[0]
+    d0, i0, _ = src.encode_packed_rows(xs)
+    for R2 in a.targets:
+        dst = base.with_row_budget(R2)
+        td, ti, tf = dst.transrate_packed_rows(d0, i0)
+        ed, ei, ef = dst.encode_packed_rows(xs)
+        ok = (tf & ef).unsqueeze(2)
+        err = []
+        for dd, ii in ((td, ti), (ed, ei)):
+            Xh = base.psy.dequantize(*base.psy.unpack(dd, ii))
+            e = torch.where(ok, (Xh - X).double() ** 2, torch.zeros((), dtype=torch.float64, device=X.device))
+            err.append(float((e.sum() / (ok.sum() * N)).sqrt()))
+        print("RMS error against X at %d bits (4 clips x 16 blocks, rows that fit in both): transrated from %d %.4f, encoded "
+              "directly %.4f" % (R2, a.row_bits, err[0], err[1]))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--transrate", action="store_true", help="only transrating: rows at --row-bits (default 2730 here) to --targets")
+    ap.add_argument("--targets", type=int, nargs="+", default=[1365, 682], help="the target budgets of --transrate")
     ap.add_argument("--pcm16", action="store_true", help="only int16 PCM to packed rows, one-shot and chunk by chunk")
     ap.add_argument("--stream", action="store_true", help="only the packed rows of a stream, chunk by chunk")
     ap.add_argument("--row-bits", type=int, default=1365, help="the row budget of the packed-rows section (64 kbit/s)")
@@ -213,6 +286,10 @@ def main():
     ap.add_argument("--round-steps", type=int, default=30)
     a = ap.parse_args()
     B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    if a.transrate:
+        if a.row_bits == 1365:
+            a.row_bits = 2730   # the source rows: 128 kbit/s
+        return transrate_rows(a)
     if a.pcm16:
         return pcm16_rows(a)
     if a.stream:
