@@ -21,6 +21,8 @@ AC_IN_PCM16 = 32   # x is int16 PCM: flag of ac_encode_fused_ex beside AC_EMIT_C
                    # ac_stream_encode_typed's dtype beside AC_PACKED
 AC_IN_PACKED = 64  # x is one ac_packed_rows: flag of ac_encode_fused_ex beside AC_EMIT_PACKED alone (transrating)
 AC_PACK_ROWS_MAX_BITS = 16384  # the largest row budget AC_EMIT_PACKED serves in one launch (the header's macro)
+AC_CONCEAL_FADE = 4       # scale-factor units a concealed row loses per frame of age (the header's macro)
+AC_CONCEAL_MAX_AGE = 31   # the largest max_age of ac_conceal (the header's macro)
 WINDOW_IDS = {"vorbis": 0, "sine": 1}   # anything else -> 2 (rectangular), mdctransformer.py:199-211
 WINDOW_RECT = 2
 
@@ -136,6 +138,11 @@ PROTOTYPES = {
 class PackedRows(ctypes.Structure):
     """``ac_packed_rows``: what ``ac_decode_quantized`` takes for ``codes`` when ``sf`` is NULL."""
     _fields_ = [("data", c_void_p), ("nbytes", ctypes.c_int64), ("index", c_void_p)]
+
+
+class Conceal(ctypes.Structure):
+    """``ac_conceal``: what ``ac_decode_quantized`` takes for ``scratch`` when ``sf`` is NULL (lost rows concealed)."""
+    _fields_ = [("lost", c_void_p), ("max_age", ctypes.c_int32)]
 
 
 class PackedOut(ctypes.Structure):

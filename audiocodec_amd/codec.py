@@ -495,14 +495,24 @@ class AudioCodec:
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         return int(self._lib.ac_decode_packed_launches(self.mdct._plan(dev), self.psy._plan(dev), int(channels_n)))
 
-    def decode_packed(self, data, index, pcm16=False):
+    def decode_packed(self, data, index, pcm16=False, *, lost=None, max_age=8):
         """data uint8 [nbytes], index int64 [B, K', C] -> x [B, (K'+1)*N, C] (``torch.int16`` with ``pcm16=True``);
         bit-equal to ``decode_quantized(*psy.unpack(data, index), pcm16)``, that is to ``decode_quantized`` on the codes
         that were packed.  One launch that reads the bitstream in the synthesis -- no codes or scale factors are
         allocated -- where :meth:`decode_packed_launches` is 1; :meth:`PsychoacousticModel.unpack`, then
         :meth:`decode_quantized` elsewhere.  ``index`` may hold any row starts (a slice of frames, channels in another
-        order, a strided view), and damaged rows read as :meth:`PsychoacousticModel.unpack` reads them.  float32 only."""
+        order, a strided view), and damaged rows read as :meth:`PsychoacousticModel.unpack` reads them.  float32 only.
+
+        ``lost`` uint8 / bool [B, K', C] marks rows that did not arrive (nonzero), and they are concealed (DESIGN.md section
+        8f): a lost row is read from the last row of its clip and channel that arrived, at most ``max_age`` (0 .. 31)
+        frames back, with its scale factors lowered by 4 -- the spectrum halved, exactly -- per frame of age; a row
+        without such a source is silence, so ``max_age=0`` is zero-filling.  Sources are looked for in this call's
+        ``index`` only.  Bit-equal to :meth:`PsychoacousticModel.conceal_plan`, ``unpack`` at its row starts,
+        :meth:`PsychoacousticModel.conceal_fade` and :meth:`decode_quantized`, which is what runs where
+        :meth:`decode_packed_launches` is not 1; one launch where it is.  Only enqueues on the current stream."""
         _host.require_float32(self.compute_dtype, "decode_packed")
+        if lost is not None:
+            return self._decode_packed_concealed(data, index, pcm16, lost, max_age)
         if (isinstance(data, torch.Tensor) and isinstance(index, torch.Tensor) and data.is_cuda and index.dim() == 3
                 and index.shape[1] >= 1 and self.decode_packed_launches(index.shape[2], data.device) == 1):
             data = self.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
@@ -519,6 +529,29 @@ class AudioCodec:
             return x
         codes, sf = self.psy.unpack(data, index)
         return self.decode_quantized(codes, sf, pcm16)
+
+    def _decode_packed_concealed(self, data, index, pcm16, lost, max_age):
+        """:meth:`decode_packed` with ``lost`` given: the concealing kernel where packed rows are decoded in one launch, the
+        composition elsewhere."""
+        max_age = self.psy._check_max_age(max_age)
+        data = self.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
+        index = self.psy._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
+        lost = self.psy._check_lost(lost, index)
+        B, Kp, C = index.shape
+        dev = data.device
+        if B >= 1 and Kp >= 1 and C >= 1 and self.decode_packed_launches(C, dev) == 1:
+            x = torch.empty((B, (Kp + 1) * self.filters_n, C), dtype=torch.int16 if pcm16 else torch.float32, device=dev)
+            rows = _lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr())
+            conceal = _lib.Conceal(lost.data_ptr(), max_age)
+            with _host.on_device(dev):
+                _lib.check(self._lib.ac_decode_quantized(
+                    self.mdct._plan(dev), self.psy._plan(dev), ctypes.addressof(rows), None,
+                    None if pcm16 else _host.ptr(x), _host.ptr(x) if pcm16 else None, ctypes.addressof(conceal), B, Kp, C,
+                    _host.stream_ptr(dev)))
+            return x
+        src_index, age = self.psy.conceal_plan(index, lost, data.numel(), max_age)
+        codes, sf = self.psy.unpack(data, src_index)
+        return self.decode_quantized(codes, self.psy.conceal_fade(sf, age), pcm16)
 
     def decode_into(self, X, x):
         """:meth:`decode` into a caller-owned PCM tensor ``x [B, (K'+1)*N, C]`` (``torch.int16`` selects 16-bit PCM);

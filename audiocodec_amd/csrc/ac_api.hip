@@ -1325,7 +1325,20 @@ int ac_decode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const 
     AC_REQUIRE(Kp == 0 || rows.index != nullptr, "NULL tensor pointer");
     AC_REQUIRE(rows.data != nullptr || rows.nbytes == 0, "data is NULL");
     AC_REQUIRE_ALIGNED(rows.data, rows.index, out);
+    // scratch addresses one ac_conceal: rows that did not arrive are concealed
+    const uint8_t* lost = nullptr;
+    int max_age = 0;
+    if (scratch != nullptr) {
+      const ac_conceal cl = *reinterpret_cast<const ac_conceal*>(scratch);
+      AC_REQUIRE(cl.max_age >= 0 && cl.max_age <= AC_CONCEAL_MAX_AGE, "max_age (%d) outside [0, %d]", (int)cl.max_age,
+                 AC_CONCEAL_MAX_AGE);
+      lost = cl.lost;
+      max_age = cl.max_age;
+    }
     DeviceGuard guard(mdct->device);
+    if (Kp >= 1 && lost != nullptr)
+      return launch_inv_fast_packed_conceal(mdct, psy, rows.data, rows.nbytes, rows.index, lost, max_age, out, pcm16 != nullptr,
+                                            B, Kp, C, (hipStream_t)stream);
     if (Kp >= 1)
       return launch_inv_fast_packed(mdct, psy, rows.data, rows.nbytes, rows.index, out, pcm16 != nullptr, nullptr, nullptr, B, Kp,
                                     Kp + 1, C, (hipStream_t)stream);

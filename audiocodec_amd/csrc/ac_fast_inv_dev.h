@@ -69,12 +69,14 @@ struct QuantRows {
 
 template <int R, int CMODE, int NW, int IOF = 0>
 __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const int bid, const int nblocks,
-                                              const QuantRows* qr = nullptr, const PackedRows* pr = nullptr) {
+                                              const QuantRows* qr = nullptr, const PackedRows* pr = nullptr,
+                                              const ConcealRows* cl = nullptr) {
   using G = Geo<R>;
   constexpr bool QUANT = IOF >= 3;
   constexpr bool PACKED = IOF >= 5;   // (IOF 5 / 6) the quantised spectra come as rows of the packed bitstream
+  constexpr bool CONCEAL = IOF >= 7;  // (IOF 7 / 8) ... and a row that did not arrive is concealed (ConcealRows)
   static_assert(!PACKED || R == 8, "packed rows: filters_n = 1024");
-  constexpr int OIOF = PACKED ? IOF - 5 : QUANT ? IOF - 3 : IOF;   // format of the PCM side
+  constexpr int OIOF = PACKED ? (IOF - 5) % 2 : QUANT ? IOF - 3 : IOF;   // format of the PCM side
   constexpr int FH = G::FH;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   load_tables<NW, WAVE_LDS, G::I_LDS, 0>(lds, a.tab + G::I_TOTAL, nullptr);
@@ -171,8 +173,8 @@ __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const
   if constexpr (PACKED) {
     // slot 0 is frame n0-1, read only by a wave that transforms it itself
     if (valid)
-      parse_strip_p(*pr, pq.b0, pq.b1, pq.c0, pq.c1, a.Kp, C, n0 - 1, (left && !deferred) ? 0 : 1, min(n1, a.Kp) - (n0 - 1),
-                    has1, lane, buf, rec);
+      parse_strip_p<CONCEAL>(*pr, pq.b0, pq.b1, pq.c0, pq.c1, a.Kp, C, n0 - 1, (left && !deferred) ? 0 : 1,
+                             min(n1, a.Kp) - (n0 - 1), has1, lane, buf, rec, cl);
   }
   if (valid) {
     hold_t ahead[R];
@@ -324,6 +326,27 @@ static int prep_inv_fast(const ac_mdct_plan* p, const float* X, void* x, int iof
   a.rev = inv_rev;
   // one strip per wave, workgroups dispatched in order (persistent waves drift apart and measured slower here)
   return grid_for(a.ntasks, AC_WAVES, &grid);
+}
+
+// ... and of the kernels that read packed rows (k_inv_fast_p, k_inv_fast_pl): strips of at most P_SLOTS - 1 blocks
+static int prep_inv_fast_packed(const ac_mdct_plan* p, const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes,
+                                const int64_t* index, void* x, bool pcm16, const float* tail_in, float* tail_out, int B, int Kp,
+                                int nblk, int C, InvArgs& a, PackedRows& pr, unsigned& grid) {
+  int st = prep_inv_fast(p, nullptr, x, pcm16 ? 1 : 0, tail_in, tail_out, B, Kp, nblk, C, a, grid);
+  if (st) return st;
+  if (a.seglen > P_SLOTS - 1) {   // (AC_SEGLEN asked for longer strips than a wave holds band records for)
+    a.seglen = P_SLOTS - 1;
+    a.nseg = (a.nblk + a.seglen - 1) / a.seglen;
+    a.ntasks = a.npairs * a.nseg;
+    st = grid_for(a.ntasks, AC_WAVES, &grid);
+    if (st) return st;
+  }
+  pr.data = data;
+  pr.nbytes = nbytes;
+  pr.index = index;
+  pr.band32 = reinterpret_cast<const uint32_t*>(psy->d_qband);
+  pr.off = psy->d_qoff;
+  return AC_OK;
 }
 
 }  // namespace

@@ -24,22 +24,10 @@ int launch_inv_fast_packed(const ac_mdct_plan* p, const ac_psy_plan* psy, const 
     return AC_EUNSUPPORTED;
   }
   InvArgs a;
-  unsigned grid;
-  int st = prep_inv_fast(p, nullptr, x, pcm16 ? 1 : 0, tail_in, tail_out, B, Kp, nblk, C, a, grid);
-  if (st) return st;
-  if (a.seglen > P_SLOTS - 1) {   // (AC_SEGLEN asked for longer strips than a wave holds band records for)
-    a.seglen = P_SLOTS - 1;
-    a.nseg = (a.nblk + a.seglen - 1) / a.seglen;
-    a.ntasks = a.npairs * a.nseg;
-    st = grid_for(a.ntasks, AC_WAVES, &grid);
-    if (st) return st;
-  }
   PackedRows pr;
-  pr.data = data;
-  pr.nbytes = nbytes;
-  pr.index = index;
-  pr.band32 = reinterpret_cast<const uint32_t*>(psy->d_qband);
-  pr.off = psy->d_qoff;
+  unsigned grid;
+  const int st = prep_inv_fast_packed(p, psy, data, nbytes, index, x, pcm16, tail_in, tail_out, B, Kp, nblk, C, a, pr, grid);
+  if (st) return st;
   if (pcm16) launch_inv_p<6>(a, pr, C, grid, s);
   else launch_inv_p<5>(a, pr, C, grid, s);
   AC_HIP_CHECK(hipGetLastError());

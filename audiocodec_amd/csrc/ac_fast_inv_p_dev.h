@@ -15,6 +15,11 @@
 // Row semantics are ac_unpack's (k_unpack): a width of 17 .. 30 reads as 31; width 31 gives codes 0 and sf -128, width 0 sf 0;
 // bits outside [0, nbytes) read as 0 and are never loaded; a row start may be any int64.  A row whose words all lie inside
 // data at a 4-byte phase takes plain dword loads; any other row (the last one of data, damaged input) takes p_load_word.
+//
+// Concealment of lost rows (parse_strip_p<true>, k_inv_fast_pl in ac_fast_inv_pl.hip): a row that did not
+// arrive is read from the last row of its clip and channel that did, at most max_age frames back, with every scale factor
+// lowered by AC_CONCEAL_FADE per frame of age; a row with no such source reads as a row that starts at nbytes (silence).
+// Only the row start and the sf byte of the band records change: load_row_p and extract_row_p see a row like any other.
 #pragma once
 #include "ac_fast_dev.h"
 
@@ -29,11 +34,16 @@ struct PackedRows {
   const int32_t* off;      // [M + 1]: first bin of every band
 };
 
+struct ConcealRows {
+  const uint8_t* lost;     // [B, Kp, C]: nonzero = the row did not arrive
+  int max_age;             // 0 .. AC_CONCEAL_MAX_AGE (31: a lane of half a wave per frame looked back at)
+};
+
 constexpr int P_M = 64;                       // bands of a row = lanes of a wave
 constexpr int P_SLOTS = 4;                    // frames a strip reads: at most 3 output blocks and the frame before them
 constexpr int P_ROWS = 2 * P_SLOTS;           // row r = 2 slot + signal
 constexpr int P_HDR_WORDS = (13 * P_M) / 32;  // words that can hold widths and scale factors
-constexpr int P_REC_BYTES = P_ROWS * (P_M * 4 + 16);   // per wave: the records [P_ROWS][64], then (start lo, hi, fast, -) per row
+constexpr int P_REC_BYTES = P_ROWS * (P_M * 4 + 16);   // per wave: the records [P_ROWS][64], then (start lo, hi, fast, age) per row
 
 struct PGran {   // the two-dword window of a granule, per signal
   uint32_t lo0, hi0, lo1, hi1;
@@ -64,26 +74,52 @@ __device__ __forceinline__ uint32_t p_pos(uint32_t rec, uint32_t d) {
 }
 
 // The records of the rows of frames base + slot, slot in [slot_lo, slot_hi), of the wave's two signals.  buf: the wave's FFT
-// buffer (free before the frame loop); rec: the wave's record region.
+// buffer (free before the frame loop); rec: the wave's record region.  CONCEAL: the rows are looked up through cl (above).
+template <bool CONCEAL = false>
 __device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0, long long b1, int c0, int c1, int Kp, int C,
                                               int base, int slot_lo, int slot_hi, bool has1, int lane, char* buf,
-                                              uint32_t* rec) {
+                                              uint32_t* rec, const ConcealRows* cl = nullptr) {
   uint32_t* st = reinterpret_cast<uint32_t*>(buf);   // [P_ROWS][P_HDR_WORDS]
   uint32_t* info = rec + P_ROWS * P_M;
   const int sig = lane >> 5, k = lane & 31;          // half a wave per row: slot t, signal sig
 #pragma unroll
   for (int t = 0; t < P_SLOTS; ++t) {
+    int age = 0;         // (CONCEAL) frames back to the row that is read in this one's place ...
+    bool muted = false;  // ... or there is none
+    int64_t own = 0;     // (CONCEAL) the row's own start, loaded beside `lost`: the start of every row that arrived
+    if constexpr (CONCEAL) {
+      // lane k of the row's half wave looks at frame f - k: the first one that arrived is the source
+      const bool on = t >= slot_lo && t < slot_hi && (sig == 0 || has1);
+      const long long b = sig ? b1 : b0;
+      const int c = sig ? c1 : c0;
+      const int f = base + t;
+      if (on && k < P_HDR_WORDS) own = pr.index[((size_t)b * (size_t)Kp + (size_t)f) * (size_t)C + (size_t)c];
+      const bool there = on && k <= min(cl->max_age, f) &&
+                         cl->lost[((size_t)b * (size_t)Kp + (size_t)(f - k)) * (size_t)C + (size_t)c] == 0;
+      const uint64_t m = __builtin_amdgcn_ballot_w64(there);
+      const uint32_t mh = sig ? (uint32_t)(m >> 32) : (uint32_t)m;
+      muted = mh == 0u;
+      age = muted ? 0 : __builtin_ctz(mh);
+    }
     if (t >= slot_lo && t < slot_hi && (sig == 0 || has1) && k < P_HDR_WORDS) {
       const int r = 2 * t + sig;
       const long long b = sig ? b1 : b0;
       const int c = sig ? c1 : c0;
-      int64_t a = pr.index[((size_t)b * (size_t)Kp + (size_t)(base + t)) * (size_t)C + (size_t)c];
+      int64_t a;
+      if constexpr (CONCEAL) {
+        a = own;
+        if (age != 0) a = pr.index[((size_t)b * (size_t)Kp + (size_t)(base + t - age)) * (size_t)C + (size_t)c];
+        if (muted) a = pr.nbytes;
+      } else {
+        a = pr.index[((size_t)b * (size_t)Kp + (size_t)(base + t)) * (size_t)C + (size_t)c];
+      }
       // a row start beyond the buffer reads nothing; clamping it keeps start + 4 k from overflowing
       a = a > pr.nbytes ? pr.nbytes : (a < -(1ll << 40) ? -(1ll << 40) : a);
       st[r * P_HDR_WORDS + k] = p_load_word(pr.data, pr.nbytes, a + 4ll * k);
       if (k == 0) {
         info[4 * r] = (uint32_t)(uint64_t)a;
         info[4 * r + 1] = (uint32_t)((uint64_t)a >> 32);
+        if constexpr (CONCEAL) info[4 * r + 3] = (uint32_t)age;
       }
     }
   }
@@ -108,6 +144,10 @@ __device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0
     uint32_t sfb = 0;
     if (w == 31) sfb = 0x80u;
     else if (p_stores(w)) sfb = p_get_bits(sr, 5u * P_M + 8u * (ex >> 16), 8);
+    if constexpr (CONCEAL) {   // every sf but -128 fades: max(s - AC_CONCEAL_FADE * age, -127)
+      const int fade = 4 * __builtin_amdgcn_readfirstlane((int)info[4 * r + 3]);
+      if (sfb != 0x80u) sfb = (uint32_t)max((int)(int8_t)sfb - fade, -127) & 0xffu;
+    }
     rec[r * P_M + lane] = ((cbase + (ex & 0xffffu)) << 13) | (sfb << 5) | w;
     if (lane == 0) {
       // plain loads where every word a window of this row can touch -- its ceil(bits / 32) words and two more -- is in data

@@ -315,6 +315,11 @@ bool fast_inv_packed_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C
 int launch_inv_fast_packed(const ac_mdct_plan* p, const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes,
                            const int64_t* index, void* x, bool pcm16, const float* tail_in, float* tail_out, int B, int Kp,
                            int nblk, int C, hipStream_t s);
+// ... with the rows marked in lost [B,Kp,C] (nonzero: did not arrive) concealed (k_inv_fast_pl, ac_fast_inv_pl.hip; DESIGN.md
+// section 8f), where fast_inv_packed_serves(); the one-shot synthesis only.  max_age in [0, AC_CONCEAL_MAX_AGE]
+int launch_inv_fast_packed_conceal(const ac_mdct_plan* p, const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes,
+                                   const int64_t* index, const uint8_t* lost, int max_age, void* x, bool pcm16, int B, int Kp,
+                                   int C, hipStream_t s);
 int launch_psy_fast(const ac_psy_plan* p, const float* X, const float* t_in, float* t_out, float* thr, float drown,
                     int B, int F, int C, hipStream_t s, int iof = 0);
 // streaming duplex: the analysis of a chunk of k_fwd blocks (psy: with the fused masking model) and the synthesis of a

@@ -583,6 +583,54 @@ class PsychoacousticModel:
                                            _host.ptr(codes), _host.ptr(sf), B, F, C, _host.stream_ptr(dev)))
         return codes, sf
 
+    # ---- concealment of lost rows (extension) -------------------------------------
+    @staticmethod
+    def _check_max_age(max_age):
+        if isinstance(max_age, bool) or not isinstance(max_age, (int, np.integer)):
+            raise TypeError("max_age must be an int, got %s" % type(max_age).__name__)
+        if not 0 <= int(max_age) <= _lib.AC_CONCEAL_MAX_AGE:
+            raise ValueError("max_age (%d) outside [0, %d]" % (max_age, _lib.AC_CONCEAL_MAX_AGE))
+        return int(max_age)
+
+    def _check_lost(self, lost, index):
+        """``lost`` uint8 / bool with ``index``'s shape and device -> uint8, ready for the kernels."""
+        if not isinstance(lost, torch.Tensor):
+            raise TypeError("lost must be a torch.Tensor, got %s" % type(lost).__name__)
+        if lost.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("lost has dtype %s, expected torch.uint8 or torch.bool" % lost.dtype)
+        lost = self._check_quant_tensor(lost, "lost", lost.dtype, index.shape, index.device, ndim=3)
+        return lost.view(torch.uint8)
+
+    def conceal_plan(self, index, lost, nbytes, max_age=8):
+        """Where each row of a stream with lost rows is read from: index int64 [B, F, C], lost uint8 / bool [B, F, C]
+        (nonzero: the row did not arrive) -> (src_index int64 [B, F, C], age uint8 [B, F, C]).
+
+        ``age`` is the smallest a in [0, min(max_age, f)] with ``lost[b, f-a, c] == 0`` and ``src_index`` is
+        ``index[b, f-a, c]``: the last row of the same clip and channel that arrived.  Where there is none -- a run of
+        lost rows longer than ``max_age``, or lost rows before the first good one -- the row is muted: ``src_index`` is
+        ``nbytes``, a row :meth:`unpack` reads as silence, and ``age`` 0.  Torch ops on the current stream."""
+        max_age = self._check_max_age(max_age)
+        index = self._check_quant_tensor(index, "index", torch.int64, ndim=3)
+        lost = self._check_lost(lost, index)
+        B, F, C = index.shape
+        if F == 0:
+            return index.clone(), torch.zeros((B, F, C), dtype=torch.uint8, device=index.device)
+        f = torch.arange(F, dtype=torch.int64, device=index.device).view(1, F, 1)
+        last = f.expand(B, F, C).masked_fill(lost != 0, -1).cummax(dim=1).values   # the last frame <= f that arrived
+        found = (last >= 0) & (f - last <= max_age)
+        src_index = index.gather(1, last.clamp(min=0)).masked_fill(~found, int(nbytes))
+        age = (f - last).masked_fill(~found, 0).to(torch.uint8)
+        return src_index, age
+
+    def conceal_fade(self, sf, age):
+        """The scale factors of concealed rows: sf int8 [B, F, M, C], age uint8 [B, F, C] -> every ``s != -128`` replaced
+        by ``max(s - AC_CONCEAL_FADE * age, -127)``: the spectrum times ``2^-age``.  ``-128`` stays."""
+        sf = self._check_quant_tensor(sf, "sf", torch.int8)
+        B, F, _, C = sf.shape
+        age = self._check_quant_tensor(age, "age", torch.uint8, (B, F, C), sf.device, ndim=3)
+        low = (sf.to(torch.int16) - _lib.AC_CONCEAL_FADE * age.to(torch.int16).unsqueeze(2)).clamp(min=-127).to(torch.int8)
+        return torch.where(sf == -128, sf, low)
+
     # ---- Bark scale (host precompute helpers, psychoacoustic.py:333-339) ------------------------------
     def freq2bark(self, frequencies):
         """Empirical Bark scale (``:333-335``)."""

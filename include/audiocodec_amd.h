@@ -335,7 +335,17 @@ AC_API int ac_encode_fused_pcm16(const ac_mdct_plan* mdct, const ac_psy_plan* ps
  *   the packed bitstream (below) at index [B,Kp,C], contiguous, are decoded in ONE launch that reads the bitstream where the
  *   synthesis above reads codes and sf -- bit-equal to ac_unpack followed by ac_decode_quantized, with ac_unpack's reading
  *   of damaged rows and of row starts outside data.  Served where ac_decode_packed_launches returns 1; AC_EUNSUPPORTED
- *   elsewhere (unpack the rows with ac_unpack and pass codes and sf).  scratch is not used.  codes == NULL stays an error.
+ *   elsewhere (unpack the rows with ac_unpack and pass codes and sf).  codes == NULL stays an error.
+ *   Concealment of lost rows: with sf == NULL, a scratch that is not NULL addresses one ac_conceal (a
+ *   host struct, read during the call); scratch == NULL is the call above, on the same kernel.  lost uint8 [B,Kp,C] (device),
+ *   nonzero = the row did not arrive; lost == NULL: no row is lost.  max_age outside [0, AC_CONCEAL_MAX_AGE] is AC_EINVAL.
+ *   Row (b,f,c) is read from the row at index[b,f-age,c], age = the smallest a in [0, min(max_age, f)] with
+ *   lost[b,f-a,c] == 0, with ac_unpack's reading of it, and every scale factor s != -128 replaced by
+ *   max(s - AC_CONCEAL_FADE * age, -127): the spectrum of the source row times 2^-age, exactly, wherever the clamp is not
+ *   met (step(s - 4) = step(s) / 2).  A band with sf = -128 stays one.  Where no such a exists -- a run of lost rows longer
+ *   than max_age, or lost rows before the first one of a clip and channel that arrived -- the row reads as a row that
+ *   starts at nbytes: silence.  Sources are looked for in this call's index only.  Still one launch; served where
+ *   ac_decode_packed_launches returns 1 and AC_EUNSUPPORTED elsewhere.  Streams (ac_stream_inverse_typed) do not conceal.
  * ac_decode_packed_launches: 1 where that form is served (float32 plans on the wave-level kernels, filters_n = 1024,
  *   bark_bands_n = 64, mono / stereo), else 1 + ac_decode_quantized_launches: ac_unpack, then ac_decode_quantized (also
  *   everywhere while AC_DECODE_PACKED_NOFUSE=1 is set in the environment: read per call).  0 for NULL or mismatched plans. */
@@ -344,6 +354,12 @@ typedef struct ac_packed_rows {
   int64_t nbytes;
   const int64_t* index; /* [B,Kp,C] byte offset of every row in data (device); any int64 */
 } ac_packed_rows;
+#define AC_CONCEAL_FADE 4     /* scale-factor units a concealed row loses per frame of age: 6.02 dB, an exact halving */
+#define AC_CONCEAL_MAX_AGE 31 /* the largest max_age */
+typedef struct ac_conceal {
+  const uint8_t* lost;  /* [B,Kp,C] nonzero = the row did not arrive (device); NULL: none is lost */
+  int32_t max_age;      /* frames a row may be repeated over, 0 .. AC_CONCEAL_MAX_AGE; 0 = zero-filling */
+} ac_conceal;
 AC_API int ac_quantize(const ac_psy_plan* psy, const float* X, const float* thr, int16_t* codes, int8_t* sf, int B, int F,
                        int C, void* stream);
 AC_API int ac_dequantize(const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, float* X, int B, int F, int C,

@@ -16,8 +16,10 @@ the one launch on int16 (k_fwd_fast_qp16 / qps16), the conversion to(float32) / 
 caller did before), and the float32 one launch on a resident float32 tensor; compared byte for byte, then alternating
 (profiles/pack/pack_bench_pcm16.txt).
 python tools/pack_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7] [--round-steps 30]
-                           [--row-bits 1365] [--only-rows] [--stream] [--pcm16] [--transrate [--targets 1365 682]]
---transrate: rows at 2730 bits transrated to each of --targets (transrate_rows(); profiles/pack/pack_bench_transrate.txt)."""
+                           [--row-bits 1365] [--only-rows] [--stream] [--pcm16] [--transrate [--targets 1365 682]] [--conceal]
+--transrate: rows at 2730 bits transrated to each of --targets (transrate_rows(); profiles/pack/pack_bench_transrate.txt).
+--conceal: decode_packed with lost rows concealed -- none lost, and 1 % lost at random -- against decode_packed without `lost`
+(conceal_rows(); profiles/pack/pack_bench_conceal.txt)."""
 import argparse
 import ctypes
 import os
@@ -268,8 +270,59 @@ def transrate_rows(a):
               "directly %.4f" % (R2, a.row_bits, err[0], err[1]))
 
 
+def conceal_rows(a):
+    """Concealment of lost rows on the rows of encode_packed_rows at --row-bits: (a) decode_packed
+    without `lost`, the yardstick; (b) with `lost` all false; (c) with 1 % of the rows lost at random, max_age 8 -- both the
+    one launch of k_inv_fast_pl; (d) the composition of (c) (AC_DECODE_PACKED_NOFUSE=1, read per call: conceal_plan, unpack,
+    conceal_fade, decode_quantized).  Compared bit for bit first, then alternating, --rounds rounds of --round-steps,
+    float32 and 16-bit PCM out."""
+    B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    cbr = audiocodec_amd.AudioCodec(48000, N).with_row_budget(a.row_bits)
+    x = (torch.rand((B, K * N, C), device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * 2 - 1)
+    data, index, _ = cbr.encode_packed_rows(x)
+    del x
+    none = torch.zeros(index.shape, dtype=torch.uint8, device="cuda")
+    some = (torch.rand(index.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(1)) < 0.01).to(torch.uint8)
+    print("conceal: B=%d K=%d N=%d C=%d  rows=%d at %d bits (%.1f MB)  %d rows lost (%.2f %%)  max_age 8  decode_packed "
+          "launches=%d  %s" % (B, K, N, C, index.numel(), a.row_bits, data.numel() / 1e6, int(some.sum()),
+                               100.0 * float(some.float().mean()), cbr.decode_packed_launches(C), torch.cuda.get_device_name()))
+
+    def composition(lost, pcm16):
+        os.environ["AC_DECODE_PACKED_NOFUSE"] = "1"   # (read per call)
+        try:
+            return cbr.decode_packed(data, index, pcm16, lost=lost, max_age=8)
+        finally:
+            del os.environ["AC_DECODE_PACKED_NOFUSE"]
+
+    for pcm16 in (False, True):
+        v = torch.int16
+        plain = cbr.decode_packed(data, index, pcm16)
+        assert torch.equal(cbr.decode_packed(data, index, pcm16, lost=none).view(v), plain.view(v)), "none lost != the plain decode"
+        one, two = cbr.decode_packed(data, index, pcm16, lost=some, max_age=8), composition(some, pcm16)
+        assert one.dtype == two.dtype and torch.equal(one.view(v), two.view(v)), "the two forms differ"
+        del plain, one, two
+    print("none lost equals the plain decode; the one launch and the composition agree bit for bit (float32 and 16-bit PCM)")
+    for pcm16 in (False, True):
+        forms = [("(a) decode_packed", lambda: cbr.decode_packed(data, index, pcm16)),
+                 ("(b) lost all false, %d launch" % cbr.decode_packed_launches(C), lambda: cbr.decode_packed(data, index, pcm16, lost=none)),
+                 ("(c) 1 %% lost, %d launch" % cbr.decode_packed_launches(C), lambda: cbr.decode_packed(data, index, pcm16, lost=some)),
+                 ("(d) 1 % lost, composition", lambda: composition(some, pcm16))]
+        runs = dict((n, []) for n, _ in forms)
+        for _ in range(a.rounds):
+            for n, fn in forms:
+                runs[n].append(timed(fn, a.round_steps, 1))
+        med = []
+        print("%s out:" % ("16-bit PCM" if pcm16 else "float32"))
+        for n, _ in forms:
+            v = sorted(runs[n])
+            med.append(v[len(v) // 2])
+            print("  %-32s median %.3f ms  min %.3f  max %.3f  (%d alternating rounds of %d)" % (n, med[-1], v[0], v[-1], len(v), a.round_steps))
+        print("  (b) / (a) = %.3f   (c) / (a) = %.3f   (c) / (d) = %.3f" % (med[1] / med[0], med[2] / med[0], med[2] / med[3]))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--conceal", action="store_true", help="only decode_packed with lost rows concealed, against without")
     ap.add_argument("--transrate", action="store_true", help="only transrating: rows at --row-bits (default 2730 here) to --targets")
     ap.add_argument("--targets", type=int, nargs="+", default=[1365, 682], help="the target budgets of --transrate")
     ap.add_argument("--pcm16", action="store_true", help="only int16 PCM to packed rows, one-shot and chunk by chunk")
@@ -286,6 +339,8 @@ def main():
     ap.add_argument("--round-steps", type=int, default=30)
     a = ap.parse_args()
     B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    if a.conceal:
+        return conceal_rows(a)
     if a.transrate:
         if a.row_bits == 1365:
             a.row_bits = 2730   # the source rows: 128 kbit/s
