@@ -560,6 +560,24 @@ static int check_dims(int B, int K, int C) {
   AC_REQUIRE(B >= 0 && K >= 0 && C >= 0, "negative dimension (B=%d, blocks=%d, C=%d)", B, K, C);
   return AC_OK;
 }
+// a transform plan and a masking-model plan that one call takes together
+static int check_plan_pair(const ac_mdct_plan* mdct, const ac_psy_plan* psy) {
+  AC_REQUIRE(mdct != nullptr && psy != nullptr, "plan is NULL");
+  AC_REQUIRE(mdct->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", mdct->N, psy->N);
+  AC_REQUIRE(mdct->device == psy->device, "plans live on different devices");
+  return AC_OK;
+}
+// the slot length of a caller's ac_packed_out: the one the plan's row budget gives
+static int check_row_bytes(const ac_packed_out& po, const ac_psy_plan* psy) {
+  AC_REQUIRE(po.row_bytes == plan_row_bytes(psy), "row_bytes (%lld) is not the plan's ceil(%d / 32) * 4 = %lld",
+             (long long)po.row_bytes, psy->row_bits, (long long)plan_row_bytes(psy));
+  return AC_OK;
+}
+static int refuse_pcm16() {
+  set_error("16-bit PCM is served at filters_n 64 ... 2048 in powers of two ('vorbis' or 'sine' window; below 1024: mono / "
+            "stereo) and at 120 / 240 / 480 / 960 / 1920 / 576 / 1152 (mono / stereo)");
+  return AC_EUNSUPPORTED;
+}
 
 static int mdct_forward(const ac_mdct_plan* p, const void* x, bool pcm16, float* X, int B, int K, int C, void* stream) {
   AC_REQUIRE(p != nullptr, "plan is NULL");
@@ -574,9 +592,7 @@ static int mdct_forward(const ac_mdct_plan* p, const void* x, bool pcm16, float*
     return launch_fwd_fast(p, nullptr, x, pcm16, X, nullptr, nullptr, 0.f, nullptr, B, K, K + 1, C, s);
   if (pcm16) {
     if (lds_fft_serves_pcm16(p, C)) return launch_fwd_lds_pcm16(p, static_cast<const int16_t*>(x), X, B, K, C, s);
-    set_error("16-bit PCM is served at filters_n 64 ... 2048 in powers of two ('vorbis' or 'sine' window; below 1024: mono / "
-              "stereo) and at 120 / 240 / 480 / 960 / 1920 / 576 / 1152 (mono / stereo)");
-    return AC_EUNSUPPORTED;
+    return refuse_pcm16();
   }
   return launch_fwd_generic(p, static_cast<const float*>(x), X, nullptr, B, K, K + 1, C, s);
 }
@@ -593,9 +609,7 @@ static int mdct_inverse(const ac_mdct_plan* p, const float* X, void* x, bool pcm
   if (wave_level(p, C, pcm16 ? 1 : 0, Kp)) return launch_inv_fast(p, X, x, pcm16, nullptr, nullptr, B, Kp, Kp + 1, C, s);
   if (pcm16) {
     if (lds_fft_serves_pcm16(p, C)) return launch_inv_lds_pcm16(p, X, static_cast<int16_t*>(x), B, Kp, C, s);
-    set_error("16-bit PCM is served at filters_n 64 ... 2048 in powers of two ('vorbis' or 'sine' window; below 1024: mono / "
-              "stereo) and at 120 / 240 / 480 / 960 / 1920 / 576 / 1152 (mono / stereo)");
-    return AC_EUNSUPPORTED;
+    return refuse_pcm16();
   }
   return launch_inv_generic(p, X, static_cast<float*>(x), nullptr, nullptr, B, Kp, Kp + 1, C, s);
 }
@@ -674,10 +688,8 @@ int ac_mask_threshold_backward(const ac_psy_plan* p, const float* X, const float
 
 static int encode_fused(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const void* x, bool pcm16, float* X, float* t,
                         float* thr, float drown, int B, int K, int C, void* stream) {
-  AC_REQUIRE(mdct != nullptr && psy != nullptr, "plan is NULL");
-  AC_REQUIRE(mdct->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", mdct->N, psy->N);
-  AC_REQUIRE(mdct->device == psy->device, "plans live on different devices");
-  int st = check_dims(B, K, C);
+  int st = check_plan_pair(mdct, psy);
+  if (!st) st = check_dims(B, K, C);
   if (st) return st;
   if (B == 0 || C == 0) return AC_OK;
   AC_REQUIRE(X != nullptr && t != nullptr && thr != nullptr && (x != nullptr || K == 0), "NULL tensor pointer");
@@ -751,10 +763,8 @@ int ac_encode_quantized_launches_pcm16(const ac_mdct_plan* mdct, const ac_psy_pl
 // ac_encode_fused_ex with AC_EMIT_CODES (pcm16: with AC_IN_PCM16, x is int16)
 static int encode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const void* x, bool pcm16, float* X, float* t,
                             float* thr, float drown, int16_t* codes, int8_t* sf, int B, int K, int C, void* stream) {
-  AC_REQUIRE(mdct != nullptr && psy != nullptr, "plan is NULL");
-  AC_REQUIRE(mdct->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", mdct->N, psy->N);
-  AC_REQUIRE(mdct->device == psy->device, "plans live on different devices");
-  int st = check_dims(B, K, C);
+  int st = check_plan_pair(mdct, psy);
+  if (!st) st = check_dims(B, K, C);
   if (!st) st = check_quant(psy, B, K + 1, C);
   if (st) return st;
   if (B == 0 || C == 0) return AC_OK;
@@ -763,18 +773,10 @@ static int encode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, co
     AC_REQUIRE(x != nullptr || K == 0, "NULL tensor pointer");
     AC_REQUIRE_ALIGNED(x, X, thr, codes, sf);
     DeviceGuard guard(mdct->device);
-    if (pcm16) {
-      const int16_t* xp = static_cast<const int16_t*>(x);
-      if (psy->row_bits)
-        return launch_fwd_fast_quant_budget_pcm16(mdct, psy, xp, X, t, thr, drown, psy->row_bits, psy->kmin, codes, sf, B, K,
-                                                  K + 1, C, (hipStream_t)stream);
-      return launch_fwd_fast_quant_pcm16(mdct, psy, xp, X, t, thr, drown, codes, sf, B, K, K + 1, C, (hipStream_t)stream);
-    }
-    const float* xf = static_cast<const float*>(x);
-    if (psy->row_bits)
-      return launch_fwd_fast_quant_budget(mdct, psy, xf, X, t, thr, drown, psy->row_bits, psy->kmin, codes, sf, B, K, K + 1, C,
-                                          (hipStream_t)stream);
-    return launch_fwd_fast_quant(mdct, psy, xf, X, t, thr, drown, codes, sf, B, K, K + 1, C, (hipStream_t)stream);
+    // at the plan's row budget where it has one, as quantize_of_plan
+    const auto launch = psy->row_bits ? (pcm16 ? launch_fwd_fast_quant_budget_pcm16 : launch_fwd_fast_quant_budget)
+                                      : (pcm16 ? launch_fwd_fast_quant_pcm16 : launch_fwd_fast_quant);
+    return launch(mdct, psy, x, X, t, thr, drown, codes, sf, B, K, K + 1, C, (hipStream_t)stream);
   }
   AC_REQUIRE(X != nullptr && t != nullptr && thr != nullptr,
              "AC_EMIT_CODES: X, t and thr are required as intermediates where ac_encode_quantized_launches%s() returns 2",
@@ -807,10 +809,8 @@ int ac_encode_packed_launches_pcm16(const ac_mdct_plan* mdct, const ac_psy_plan*
 static int encode_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const void* x, bool pcm16, const float* X,
                               const float* t, const float* thr, float drown, const ac_packed_out* out, const void* out1, int B,
                               int K, int C, void* stream) {
-  AC_REQUIRE(mdct != nullptr && psy != nullptr, "plan is NULL");
-  AC_REQUIRE(mdct->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", mdct->N, psy->N);
-  AC_REQUIRE(mdct->device == psy->device, "plans live on different devices");
-  int st = check_dims(B, K, C);
+  int st = check_plan_pair(mdct, psy);
+  if (!st) st = check_dims(B, K, C);
   if (!st) st = check_quant(psy, B, K + 1, C);
   if (st) return st;
   AC_REQUIRE(psy->row_bits != 0, "AC_EMIT_PACKED needs a plan with a row budget (ac_psy_plan_with_row_budget)");
@@ -818,9 +818,8 @@ static int encode_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
   AC_REQUIRE(out1 == nullptr, "AC_EMIT_PACKED takes one ac_packed_out as out0: out1 must be NULL");
   AC_REQUIRE(out != nullptr, "AC_EMIT_PACKED without its ac_packed_out");
   const ac_packed_out po = *out;
-  const int64_t row_bytes = (int64_t)((psy->row_bits + 31) / 32) * 4;
-  AC_REQUIRE(po.row_bytes == row_bytes, "row_bytes (%lld) is not the plan's ceil(%d / 32) * 4 = %lld", (long long)po.row_bytes,
-             psy->row_bits, (long long)row_bytes);
+  st = check_row_bytes(po, psy);
+  if (st) return st;
   if (B == 0 || C == 0) return AC_OK;
   if (!encode_packed_fuses(mdct, psy, C)) {
     set_error("AC_EMIT_PACKED: no kernel encodes to packed rows in one launch for filters_n = %d, bark_bands_n = %d, %d "
@@ -832,11 +831,8 @@ static int encode_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
   AC_REQUIRE(po.data != nullptr && po.fits != nullptr && (x != nullptr || K == 0), "NULL tensor pointer");
   AC_REQUIRE_ALIGNED(x, po.data);
   DeviceGuard guard(mdct->device);
-  if (pcm16)
-    return launch_fwd_fast_pack_rows_pcm16(mdct, psy, static_cast<const int16_t*>(x), drown, po.data, row_bytes, po.fits, B, K,
-                                           K + 1, C, (hipStream_t)stream);
-  return launch_fwd_fast_pack_rows(mdct, psy, static_cast<const float*>(x), drown, po.data, row_bytes, po.fits, B, K, K + 1, C,
-                                   (hipStream_t)stream);
+  return (pcm16 ? launch_fwd_fast_pack_rows_pcm16 : launch_fwd_fast_pack_rows)(mdct, psy, x, drown, po.data, po.row_bytes, po.fits,
+                                                                              B, K, K + 1, C, (hipStream_t)stream);
 }
 
 // whether packed rows are transrated in one launch (k_transrate_p); AC_TRANSRATE_NOFUSE=1 sends every configuration down the
@@ -856,10 +852,8 @@ int ac_transrate_launches(const ac_psy_plan* psy, int C) {
 static int transrate_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const ac_packed_rows* in, const float* X,
                                  const float* t, const float* thr, const ac_packed_out* out, int16_t* offset, int B, int K,
                                  int C, void* stream) {
-  AC_REQUIRE(mdct != nullptr && psy != nullptr, "plan is NULL");
-  AC_REQUIRE(mdct->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", mdct->N, psy->N);
-  AC_REQUIRE(mdct->device == psy->device, "plans live on different devices");
-  int st = check_dims(B, K, C);
+  int st = check_plan_pair(mdct, psy);
+  if (!st) st = check_dims(B, K, C);
   if (!st) st = check_quant(psy, B, K + 1, C);
   if (st) return st;
   AC_REQUIRE(psy->row_bits != 0, "AC_IN_PACKED needs a plan with a row budget (ac_psy_plan_with_row_budget)");
@@ -868,9 +862,8 @@ static int transrate_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* ps
   AC_REQUIRE(out != nullptr, "AC_IN_PACKED without its ac_packed_out (out0)");
   const ac_packed_rows rows = *in;
   const ac_packed_out po = *out;
-  const int64_t row_bytes = (int64_t)((psy->row_bits + 31) / 32) * 4;
-  AC_REQUIRE(po.row_bytes == row_bytes, "row_bytes (%lld) is not the plan's ceil(%d / 32) * 4 = %lld", (long long)po.row_bytes,
-             psy->row_bits, (long long)row_bytes);
+  st = check_row_bytes(po, psy);
+  if (st) return st;
   AC_REQUIRE(rows.nbytes >= 0, "negative nbytes (%lld)", (long long)rows.nbytes);
   if (B == 0 || C == 0) return AC_OK;
   if (!transrate_fuses(psy)) {
@@ -883,7 +876,7 @@ static int transrate_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* ps
   AC_REQUIRE(rows.data != nullptr || rows.nbytes == 0, "data is NULL");
   AC_REQUIRE_ALIGNED(rows.data, rows.index, po.data, offset);
   DeviceGuard guard(psy->device);
-  return launch_transrate(psy, rows.data, rows.nbytes, rows.index, po.data, row_bytes, po.fits, offset,
+  return launch_transrate(psy, rows.data, rows.nbytes, rows.index, po.data, po.row_bytes, po.fits, offset,
                           (long long)B * (K + 1) * C, (hipStream_t)stream);
 }
 
@@ -921,10 +914,8 @@ int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const f
   float* o_noisy = (flags & AC_EMIT_NOISY) ? noisy : nullptr;
   float* o_dbn = (flags & AC_EMIT_DB_NORM) ? db_norm : nullptr;
   if (!o_noisy && !o_dbn) return encode_fused(mdct, psy, x, false, X, t, thr, drown, B, K, C, stream);
-  AC_REQUIRE(mdct != nullptr && psy != nullptr, "plan is NULL");
-  AC_REQUIRE(mdct->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", mdct->N, psy->N);
-  AC_REQUIRE(mdct->device == psy->device, "plans live on different devices");
-  int st = check_dims(B, K, C);
+  int st = check_plan_pair(mdct, psy);
+  if (!st) st = check_dims(B, K, C);
   if (st) return st;
   if (B == 0 || C == 0) return AC_OK;
   AC_REQUIRE(X != nullptr && t != nullptr && thr != nullptr && (x != nullptr || K == 0), "NULL tensor pointer");
@@ -1025,14 +1016,14 @@ static int stream_analysis(ac_stream* s, const ac_psy_plan* psy, const float* x_
   AC_REQUIRE(x_chunk != nullptr && X != nullptr, "NULL tensor pointer");
   AC_REQUIRE_ALIGNED(x_chunk, X, thr);
   const ac_mdct_plan* p = s->plan;
+  int st = AC_OK;
   if (psy) {
     AC_REQUIRE(t != nullptr && thr != nullptr, "NULL tensor pointer");
-    AC_REQUIRE(p->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", p->N, psy->N);
-    AC_REQUIRE(p->device == psy->device, "plans live on different devices");
+    st = check_plan_pair(p, psy);
   }
+  if (st) return st;
   DeviceGuard guard(s->device);
   hipStream_t hs = (hipStream_t)stream;
-  int st;
   const bool fast = wave_level(p, s->C, 0, k);
   // (filters_n = 2048 mono: the fused kernel is not instantiated, see encode_fused; filters_n 64 ... 512: the masking model
   // for general band layouts rides in the several-frames-per-wave kernels)
@@ -1135,11 +1126,8 @@ int ac_stream_run(ac_stream* s, const ac_psy_plan* psy, int nchunks, int k, cons
   // the ~7 us kernel it would hide; DESIGN_LOG.md section 7.)  Same kernel bodies: the results equal the chain's.
   const ac_mdct_plan* p = s->plan;
   hipStream_t hs = (hipStream_t)stream;
-  if (psy) {
-    AC_REQUIRE(p->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", p->N, psy->N);
-    AC_REQUIRE(p->device == psy->device, "plans live on different devices");
-  }
-  int st = settle_state(s, hs);   // the state at its home buffers on entry and again on exit
+  int st = psy ? check_plan_pair(p, psy) : AC_OK;
+  if (!st) st = settle_state(s, hs);   // the state at its home buffers on entry and again on exit
   if (st) return st;
   bool duplex = xhat_chunks && nchunks >= 2 && wave_level(p, s->C, 0, k) && fast_duplex_serves(p, psy, s->B, s->C, k, k);
   if (duplex) {
@@ -1305,10 +1293,8 @@ int ac_decode_packed_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
 
 int ac_decode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, float* x,
                         int16_t* pcm16, float* scratch, int B, int Kp, int C, void* stream) {
-  AC_REQUIRE(mdct != nullptr && psy != nullptr, "plan is NULL");
-  AC_REQUIRE(mdct->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", mdct->N, psy->N);
-  AC_REQUIRE(mdct->device == psy->device, "plans live on different devices");
-  int st = check_quant(psy, B, Kp, C);
+  int st = check_plan_pair(mdct, psy);
+  if (!st) st = check_quant(psy, B, Kp, C);
   if (st) return st;
   AC_REQUIRE((x != nullptr) != (pcm16 != nullptr), "exactly one of x (float32) and pcm16 must be given");
   if (B == 0 || C == 0) return AC_OK;
@@ -1539,10 +1525,8 @@ int ac_encode_fused_typed(const ac_mdct_plan* mdct, const ac_psy_plan* psy, cons
   if (dtype == AC_F32)
     return ac_encode_fused(mdct, psy, static_cast<const float*>(x), static_cast<float*>(X), static_cast<float*>(t),
                            static_cast<float*>(thr), (float)drown, B, K, C, stream);
-  AC_REQUIRE(mdct != nullptr && psy != nullptr, "plan is NULL");
-  AC_REQUIRE(mdct->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", mdct->N, psy->N);
-  AC_REQUIRE(mdct->device == psy->device, "plans live on different devices");
-  int st = check_dims(B, K, C);
+  int st = check_plan_pair(mdct, psy);
+  if (!st) st = check_dims(B, K, C);
   if (st) return st;
   if (B == 0 || C == 0) return AC_OK;
   AC_REQUIRE(X != nullptr && t != nullptr && thr != nullptr && (x != nullptr || K == 0), "NULL tensor pointer");
@@ -1599,8 +1583,10 @@ static int stream_typed_check(const ac_stream* s, int dtype, int k) {
 static bool stream_packed_args_match(const ac_stream* s, const ac_psy_plan* psy) {
   return s && psy && s->plan && s->plan->N == psy->N && s->plan->device == psy->device;
 }
-static bool stream_encode_packed_fuses(const ac_stream* s, const ac_psy_plan* psy) {
-  return encode_packed_fuses(s->plan, psy, s->C) && fast_encode_pack_stream_serves(s->plan, psy, s->C);
+// (16-bit PCM chunks, AC_PACKED | AC_IN_PCM16: k_fwd_fast_qps16 has a register gate of its own)
+static bool stream_encode_packed_fuses(const ac_stream* s, const ac_psy_plan* psy, bool pcm16) {
+  return encode_packed_fuses(s->plan, psy, s->C) &&
+         (pcm16 ? fast_encode_pack_stream_pcm16_serves : fast_encode_pack_stream_serves)(s->plan, psy, s->C);
 }
 
 int ac_stream_packed_launches(const ac_stream* s, const ac_psy_plan* psy, int decode) {
@@ -1608,16 +1594,12 @@ int ac_stream_packed_launches(const ac_stream* s, const ac_psy_plan* psy, int de
   if (decode) return decode_packed_fuses(s->plan, psy, s->C) ? 1 : 3;   // ac_unpack, ac_dequantize, ac_stream_inverse
   if (!psy->row_bits) return 0;
   // ac_stream_encode, ac_quantize_budget, ac_pack
-  return stream_encode_packed_fuses(s, psy) ? 1 : ac_encode_launches(s->plan, psy, s->C) + 2;
+  return stream_encode_packed_fuses(s, psy, false) ? 1 : ac_encode_launches(s->plan, psy, s->C) + 2;
 }
 
-// (16-bit PCM chunks, AC_PACKED | AC_IN_PCM16: k_fwd_fast_qps16 has a register gate of its own)
-static bool stream_encode_packed_fuses_pcm16(const ac_stream* s, const ac_psy_plan* psy) {
-  return encode_packed_fuses(s->plan, psy, s->C) && fast_encode_pack_stream_pcm16_serves(s->plan, psy, s->C);
-}
 int ac_stream_packed_launches_pcm16(const ac_stream* s, const ac_psy_plan* psy) {
   if (!stream_packed_args_match(s, psy) || !psy->row_bits) return 0;
-  return stream_encode_packed_fuses_pcm16(s, psy) ? 1 : ac_encode_launches(s->plan, psy, s->C) + 2;
+  return stream_encode_packed_fuses(s, psy, true) ? 1 : ac_encode_launches(s->plan, psy, s->C) + 2;
 }
 
 static int stream_encode_packed(ac_stream* s, const ac_psy_plan* psy, const void* x_chunk, bool pcm16, const ac_packed_out* out,
@@ -1626,17 +1608,16 @@ static int stream_encode_packed(ac_stream* s, const ac_psy_plan* psy, const void
   AC_REQUIRE(psy != nullptr, "AC_PACKED needs the masking model's plan");
   AC_REQUIRE(k >= 0, "negative chunk length %d", k);
   const ac_mdct_plan* p = s->plan;
-  AC_REQUIRE(p->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", p->N, psy->N);
-  AC_REQUIRE(p->device == psy->device, "plans live on different devices");
+  int st = check_plan_pair(p, psy);
+  if (st) return st;
   AC_REQUIRE(psy->row_bits != 0, "AC_PACKED needs a plan with a row budget (ac_psy_plan_with_row_budget)");
   AC_REQUIRE(t == nullptr && thr == nullptr, "AC_PACKED writes no t or thr: they must be NULL");
   AC_REQUIRE(out != nullptr, "AC_PACKED without its ac_packed_out (X)");
   const ac_packed_out po = *out;
-  const int64_t row_bytes = (int64_t)((psy->row_bits + 31) / 32) * 4;
-  AC_REQUIRE(po.row_bytes == row_bytes, "row_bytes (%lld) is not the plan's ceil(%d / 32) * 4 = %lld", (long long)po.row_bytes,
-             psy->row_bits, (long long)row_bytes);
+  st = check_row_bytes(po, psy);
+  if (st) return st;
   if (k == 0) return AC_OK;
-  if (!(pcm16 ? stream_encode_packed_fuses_pcm16(s, psy) : stream_encode_packed_fuses(s, psy))) {
+  if (!stream_encode_packed_fuses(s, psy, pcm16)) {
     set_error("AC_PACKED: no kernel encodes a chunk%s to packed rows in one launch for filters_n = %d, bark_bands_n = %d, %d "
               "channels, row budget %d here (ac_stream_packed_launches%s() != 1): use the composition -- ac_stream_encode%s, "
               "ac_quantize_budget, then ac_pack at row starts r * row_bytes into zero-filled data",
@@ -1644,17 +1625,13 @@ static int stream_encode_packed(ac_stream* s, const ac_psy_plan* psy, const void
               pcm16 ? " on pcm / 32768 as float32" : "");
     return AC_EUNSUPPORTED;
   }
-  int st = check_quant(psy, s->B, k, s->C);
+  st = check_quant(psy, s->B, k, s->C);
   if (st) return st;
   AC_REQUIRE(po.data != nullptr && po.fits != nullptr && x_chunk != nullptr, "NULL tensor pointer");
   AC_REQUIRE_ALIGNED(x_chunk, po.data);
   DeviceGuard guard(s->device);
-  if (pcm16)
-    st = launch_fwd_fast_pack_rows_stream_pcm16(p, psy, static_cast<const int16_t*>(x_chunk), (float)drown, po.data, row_bytes,
-                                                po.fits, s->d_prev_block, s->d_prev_tmp, s->B, k, s->C, (hipStream_t)stream);
-  else
-    st = launch_fwd_fast_pack_rows_stream(p, psy, static_cast<const float*>(x_chunk), (float)drown, po.data, row_bytes, po.fits,
-                                          s->d_prev_block, s->d_prev_tmp, s->B, k, s->C, (hipStream_t)stream);
+  st = (pcm16 ? launch_fwd_fast_pack_rows_stream_pcm16 : launch_fwd_fast_pack_rows_stream)(
+      p, psy, x_chunk, (float)drown, po.data, po.row_bytes, po.fits, s->d_prev_block, s->d_prev_tmp, s->B, k, s->C, (hipStream_t)stream);
   if (st) return st;
   std::swap(s->d_prev_block, s->d_prev_tmp);
   return AC_OK;
@@ -1668,8 +1645,8 @@ static int stream_inverse_packed(ac_stream* s, const ac_stream_packed_in* in, vo
   const ac_psy_plan* psy = pin.psy;
   const ac_mdct_plan* p = s->plan;
   AC_REQUIRE(psy != nullptr, "ac_stream_packed_in: psy is NULL");
-  AC_REQUIRE(p->N == psy->N, "mdct filters_n (%d) != psychoacoustic filter_bands_n (%d)", p->N, psy->N);
-  AC_REQUIRE(p->device == psy->device, "plans live on different devices");
+  int st = check_plan_pair(p, psy);
+  if (st) return st;
   AC_REQUIRE(pin.pcm16 == 0 || pin.pcm16 == 1, "ac_stream_packed_in: pcm16 must be 0 or 1 (got %d)", (int)pin.pcm16);
   if (k == 0) return AC_OK;
   if (!decode_packed_fuses(p, psy, s->C)) {
@@ -1679,7 +1656,7 @@ static int stream_inverse_packed(ac_stream* s, const ac_stream_packed_in* in, vo
               p->N, psy->M, s->C);
     return AC_EUNSUPPORTED;
   }
-  int st = check_quant(psy, s->B, k, s->C);
+  st = check_quant(psy, s->B, k, s->C);
   if (st) return st;
   AC_REQUIRE(pin.rows.nbytes >= 0, "negative nbytes (%lld)", (long long)pin.rows.nbytes);
   AC_REQUIRE(pin.rows.index != nullptr && x != nullptr, "NULL tensor pointer");

@@ -24,36 +24,18 @@ __global__ __launch_bounds__(AC_WAVES_PSY * 64, 2) void k_fwd_fast_q16(FwdArgs a
 
 // Served where k_fwd_fast_q serves: every instance passed the register gate of DESIGN.md section 8a -- 2 waves per SIMD and no
 // more scratch than the k_fwd_fast_q instance of the same parameters (profiles/pack/kernel_resources_pcm16.txt).
-template <int CMODE, int SPREAD>
-static void launch_q16(const FwdArgs& a, const QuantOut& q, unsigned grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_fwd_fast_q16<CMODE, SPREAD>), dim3(grid), dim3(AC_WAVES_PSY * 64), 0, s, a, q);
-}
-
-int launch_fwd_fast_quant_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const int16_t* x, float* X, float* t, float* thr,
+int launch_fwd_fast_quant_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, float* X, float* t, float* thr,
                                 float drown, int16_t* codes, int8_t* sf, int B, int Kin, int F, int C, hipStream_t s) {
   if (B <= 0 || C <= 0 || F <= 0) return AC_OK;
   if (!fast_encode_quant_serves(p, psy, C)) {
     set_error("internal: no quantising fused encode of 16-bit PCM for filters_n = %d, %d channels", p->N, C);
     return AC_EUNSUPPORTED;
   }
-  FwdArgs a;
-  unsigned grid;
-  const int st = prep_fwd_fast(p, psy, x, 1, X, t, thr, drown, nullptr, B, Kin, F, C, nullptr, nullptr, nullptr, 0, a, grid);
-  if (st) return st;
-  QuantOut q;
-  q.codes = codes;
-  q.sf = sf;
-  q.band = psy->d_qband;
-  q.off = psy->d_qoff;
-  if (C == 2) {
-    if (psy->spread == 2) launch_q16<0, 2>(a, q, grid, s);
-    else launch_q16<0, 0>(a, q, grid, s);
-  } else {
-    if (psy->spread == 2) launch_q16<2, 2>(a, q, grid, s);
-    else launch_q16<2, 0>(a, q, grid, s);
-  }
-  AC_HIP_CHECK(hipGetLastError());
-  return AC_OK;
+  return launch_fwd_fast_quant_family<kEveryInstance>(
+      p, psy, x, 1, X, t, thr, drown, codes, sf, nullptr, nullptr, B, Kin, F, C,
+      [&](auto cmode, auto spread, dim3 grid, dim3 blk, const FwdArgs& a, const QuantOut& q) {
+        hipLaunchKernelGGL((k_fwd_fast_q16<cmode, spread>), grid, blk, 0, s, a, q);
+      });
 }
 
 }  // namespace ac

@@ -29,43 +29,21 @@ __global__ __launch_bounds__(AC_WAVES_PSY * 64, 2) void k_fwd_fast_qp16(FwdArgs 
 
 // Served where k_fwd_fast_qp serves: every instance passed the register gate of DESIGN.md section 8b -- 2 waves per SIMD and no
 // more scratch than the k_fwd_fast_qp instance of the same parameters (profiles/pack/kernel_resources_pcm16.txt).
-template <int CMODE, int SPREAD>
-static void launch_qp16(const FwdArgs& a, const QuantOut& q, const PackOut& po, int row_bits, int kmin, unsigned grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_fwd_fast_qp16<CMODE, SPREAD>), dim3(grid), dim3(AC_WAVES_PSY * 64), 0, s, a, q, po, row_bits, kmin);
-}
-
-int launch_fwd_fast_pack_rows_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const int16_t* x, float drown, uint8_t* data,
+int launch_fwd_fast_pack_rows_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, float drown, uint8_t* data,
                                     int64_t row_bytes, uint8_t* fits, int B, int Kin, int F, int C, hipStream_t s) {
   if (B <= 0 || C <= 0 || F <= 0) return AC_OK;
-  if (!fast_encode_pack_serves(p, psy, C) || row_bytes != (int64_t)((psy->row_bits + 31) / 32) * 4) {
+  if (!fast_encode_pack_serves(p, psy, C) || row_bytes != plan_row_bytes(psy)) {
     set_error("internal: no packing fused encode of 16-bit PCM for filters_n = %d, %d channels, row budget %d", p->N, C,
               psy->row_bits);
     return AC_EUNSUPPORTED;
   }
-  FwdArgs a;
-  unsigned grid;
-  const int st = prep_fwd_fast(p, psy, x, 1, nullptr, nullptr, nullptr, drown, nullptr, B, Kin, F, C, nullptr, nullptr, nullptr,
-                               0, a, grid);
-  if (st) return st;
-  QuantOut q;
-  q.codes = nullptr;
-  q.sf = nullptr;
-  q.band = psy->d_qband;
-  q.off = psy->d_qoff;
-  PackOut po;
-  po.data = data;
-  po.fits = fits;
-  po.row_bytes = (int)row_bytes;
+  const PackOut po{data, fits, (int)row_bytes};
   const int row_bits = psy->row_bits, kmin = psy->kmin;
-  if (C == 2) {
-    if (psy->spread == 2) launch_qp16<0, 2>(a, q, po, row_bits, kmin, grid, s);
-    else launch_qp16<0, 0>(a, q, po, row_bits, kmin, grid, s);
-  } else {
-    if (psy->spread == 2) launch_qp16<2, 2>(a, q, po, row_bits, kmin, grid, s);
-    else launch_qp16<2, 0>(a, q, po, row_bits, kmin, grid, s);
-  }
-  AC_HIP_CHECK(hipGetLastError());
-  return AC_OK;
+  return launch_fwd_fast_quant_family<kEveryInstance>(
+      p, psy, x, 1, nullptr, nullptr, nullptr, drown, nullptr, nullptr, nullptr, nullptr, B, Kin, F, C,
+      [&](auto cmode, auto spread, dim3 grid, dim3 blk, const FwdArgs& a, const QuantOut& q) {
+        hipLaunchKernelGGL((k_fwd_fast_qp16<cmode, spread>), grid, blk, 0, s, a, q, po, row_bits, kmin);
+      });
 }
 
 }  // namespace ac

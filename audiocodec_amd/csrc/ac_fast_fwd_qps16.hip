@@ -43,46 +43,23 @@ bool fast_encode_pack_stream_pcm16_serves(const ac_mdct_plan* p, const ac_psy_pl
   return fast_encode_pack_serves(p, psy, C) && kStreamRows16Gate[C == 1][psy->spread == 2];
 }
 
-template <int CMODE, int SPREAD>
-static void launch_qps16(const FwdArgs& a, const QuantOut& q, const PackOut& po, int row_bits, int kmin, unsigned grid, hipStream_t s) {
-  if constexpr (kStreamRows16Gate[CMODE == 2][SPREAD == 2])
-    hipLaunchKernelGGL((k_fwd_fast_qps16<CMODE, SPREAD>), dim3(grid), dim3(AC_WAVES_PSY * 64), 0, s, a, q, po, row_bits, kmin);
-}
-
-int launch_fwd_fast_pack_rows_stream_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const int16_t* x, float drown,
+int launch_fwd_fast_pack_rows_stream_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, float drown,
                                            uint8_t* data, int64_t row_bytes, uint8_t* fits, const float* prev_block,
                                            float* state_out, int B, int k, int C, hipStream_t s) {
   if (B <= 0 || C <= 0 || k <= 0) return AC_OK;
-  if (!fast_encode_pack_stream_pcm16_serves(p, psy, C) || row_bytes != (int64_t)((psy->row_bits + 31) / 32) * 4 || !prev_block ||
-      !state_out || prev_block == state_out) {
+  if (!fast_encode_pack_stream_pcm16_serves(p, psy, C) || row_bytes != plan_row_bytes(psy) || !prev_block || !state_out ||
+      prev_block == state_out) {
     set_error("internal: no packing fused encode of 16-bit PCM with streaming state for filters_n = %d, %d channels, row budget %d",
               p->N, C, psy->row_bits);
     return AC_EUNSUPPORTED;
   }
-  FwdArgs a;
-  unsigned grid;
-  const int st = prep_fwd_fast(p, psy, x, 1, nullptr, nullptr, nullptr, drown, prev_block, B, k, k, C, state_out, nullptr, nullptr,
-                               0, a, grid);
-  if (st) return st;
-  QuantOut q;
-  q.codes = nullptr;
-  q.sf = nullptr;
-  q.band = psy->d_qband;
-  q.off = psy->d_qoff;
-  PackOut po;
-  po.data = data;
-  po.fits = fits;
-  po.row_bytes = (int)row_bytes;
+  const PackOut po{data, fits, (int)row_bytes};
   const int row_bits = psy->row_bits, kmin = psy->kmin;
-  if (C == 2) {
-    if (psy->spread == 2) launch_qps16<0, 2>(a, q, po, row_bits, kmin, grid, s);
-    else launch_qps16<0, 0>(a, q, po, row_bits, kmin, grid, s);
-  } else {
-    if (psy->spread == 2) launch_qps16<2, 2>(a, q, po, row_bits, kmin, grid, s);
-    else launch_qps16<2, 0>(a, q, po, row_bits, kmin, grid, s);
-  }
-  AC_HIP_CHECK(hipGetLastError());
-  return AC_OK;
+  return launch_fwd_fast_quant_family<kStreamRows16Gate>(
+      p, psy, x, 1, nullptr, nullptr, nullptr, drown, nullptr, nullptr, prev_block, state_out, B, k, k, C,
+      [&](auto cmode, auto spread, dim3 grid, dim3 blk, const FwdArgs& a, const QuantOut& q) {
+        hipLaunchKernelGGL((k_fwd_fast_qps16<cmode, spread>), grid, blk, 0, s, a, q, po, row_bits, kmin);
+      });
 }
 
 }  // namespace ac

@@ -283,5 +283,41 @@ __global__ __launch_bounds__(AC_WAVES_PSY * 64, 2) void k_fwd_fast_qb(FwdArgs a,
   fwd_fast_body<8, CMODE, true, AC_WAVES_PSY, 0, SPREAD, false, QuantStage<8, CMODE, SPREAD, true>>(a, lds, (int)blockIdx.x, (int)gridDim.x, qz);
 }
 
+// (host) The launcher of every kernel of this family -- k_fwd_fast_q / qb / qp / qps and their 16-bit PCM forms, each in a
+// unit of its own: the arguments and grid of prep_fwd_fast, QuantOut from the plan, then the instance of the call's channel
+// count and spreading product through `launch(cmode, spread, grid, block, a, q)`, cmode and spread being
+// std::integral_constant.  GATE[mono][split-bf16 spreading]: the instances the unit builds; `launch` is not instantiated
+// for the others, so they are not compiled either (the unit's *_serves predicate keeps their calls away).
+constexpr bool kEveryInstance[2][2] = {{true, true}, {true, true}};
+
+template <const bool (&GATE)[2][2], typename Launch>
+int launch_fwd_fast_quant_family(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, int iof, float* X, float* t,
+                                 float* thr, float drown, int16_t* codes, int8_t* sf, const float* prev_block, float* state_out,
+                                 int B, int Kin, int F, int C, Launch launch) {
+  FwdArgs a;
+  unsigned grid;
+  const int st = prep_fwd_fast(p, psy, x, iof, X, t, thr, drown, prev_block, B, Kin, F, C, state_out, nullptr, nullptr, 0, a, grid);
+  if (st) return st;
+  QuantOut q;
+  q.codes = codes;
+  q.sf = sf;
+  q.band = psy->d_qband;
+  q.off = psy->d_qoff;
+  auto one = [&](auto cmode, auto spread) {
+    if constexpr (GATE[decltype(cmode)::value == 2][decltype(spread)::value == 2])
+      launch(cmode, spread, dim3(grid), dim3(AC_WAVES_PSY * 64), a, q);
+  };
+  using std::integral_constant;
+  if (C == 2) {
+    if (psy->spread == 2) one(integral_constant<int, 0>(), integral_constant<int, 2>());
+    else one(integral_constant<int, 0>(), integral_constant<int, 0>());
+  } else {
+    if (psy->spread == 2) one(integral_constant<int, 2>(), integral_constant<int, 2>());
+    else one(integral_constant<int, 2>(), integral_constant<int, 0>());
+  }
+  AC_HIP_CHECK(hipGetLastError());
+  return AC_OK;
+}
+
 }  // namespace
 }  // namespace ac

@@ -261,44 +261,45 @@ int launch_fwd_fast(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x
                     float* state_out = nullptr, float* noisy = nullptr, float* dbn = nullptr, uint64_t seed = 0);
 // noisy / dbn (either may be null): the element-wise epilogues of ac_encode_fused_ex, where fast_epilogue_supported()
 bool fast_epilogue_supported(const ac_mdct_plan* p, const ac_psy_plan* psy, int iof, int C);
-// the fused encode that quantises in the same launch (k_fwd_fast_q, ac_fast_fwd_q.hip): float32 PCM, filters_n = 1024, mono /
-// stereo, f32 or split-bf16 spreading.  codes int16 [B,F,N,C] and sf int8 [B,F,M,C] equal launch_quantize on launch_fwd_fast's
-// X and thr bit for bit; X, t and thr may each be null (not written)
-bool fast_encode_quant_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);
-int launch_fwd_fast_quant(const ac_mdct_plan* p, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
-                          float drown, int16_t* codes, int8_t* sf, int B, int Kin, int F, int C, hipStream_t s);
-// ... at a row budget (k_fwd_fast_qb, ac_fast_fwd_qb.hip; the same plans and shapes): codes and sf equal
-// launch_quantize_budget(row_bits, nullptr, kmin) on launch_fwd_fast's X and thr bit for bit
-int launch_fwd_fast_quant_budget(const ac_mdct_plan* p, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
-                                 float drown, int row_bits, int kmin, int16_t* codes, int8_t* sf, int B, int Kin, int F, int C,
-                                 hipStream_t s);
-// ... straight to fixed-stride packed rows (k_fwd_fast_qp, ac_fast_fwd_qp.hip; the same plans and shapes, a plan with a row
-// budget of at most kPackRowsMaxBits): data [B F C row_bytes] and fits [B,F,C] are all it writes; row r = (b F + f) C + c at
-// byte r row_bytes holds what launch_pack writes for launch_fwd_fast_quant_budget's codes and sf, zero-padded, or the marked
-// row (every width 31) where that is longer than the slot
+// The fused encode at filters_n = 1024 that quantises in the same launch (ac_fast_quant_dev.h, ac_fast_fwd_qp_dev.h): float32
+// or 16-bit PCM, mono / stereo, f32 or split-bf16 spreading, 64 bands.  Eight kernels, a unit each (ac_fast_fwd_q*.hip), one
+// host launcher (launch_fwd_fast_quant_family).  x is float32, in the *_pcm16 forms int16, read as pcm / 32768 in the row
+// loads: their outputs equal the float32 launch's on pcm.to(float32) / 32768 bit for bit.  A call the unit does not serve is
+// refused with an "internal:" error.
+//   quant           k_fwd_fast_q / q16: codes int16 [B,F,N,C] and sf int8 [B,F,M,C] equal launch_quantize on launch_fwd_fast's
+//                   X and thr bit for bit; X, t and thr may each be null (not written)
+//   quant_budget    k_fwd_fast_qb / qb16, a plan with a row budget: ... equal launch_quantize_budget(psy->row_bits, nullptr,
+//                   psy->kmin) on them
+//   pack_rows       k_fwd_fast_qp / qp16, a budget of at most kPackRowsMaxBits: data [B F C row_bytes] and fits [B,F,C] are all
+//                   it writes; row r = (b F + f) C + c at byte r row_bytes, row_bytes = plan_row_bytes(psy), holds what
+//                   launch_pack writes for quant_budget's codes and sf, zero-padded, or the marked row (every width 31) where
+//                   that is longer than the slot
+//   pack_rows_stream  k_fwd_fast_qps / qps16, a chunk of k blocks of a stream: k frames per signal, frame 0 pairs block 0 with
+//                   prev_block [B,N,C] (float32 whatever x is); state_out (another buffer) receives block k - 1.  Serves where
+//                   pack_rows does and its own instance passed the register gate
 constexpr int kPackRowsMaxBits = AC_PACK_ROWS_MAX_BITS;
-bool fast_encode_pack_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);
-int launch_fwd_fast_pack_rows(const ac_mdct_plan* p, const ac_psy_plan* psy, const float* x, float drown, uint8_t* data,
-                              int64_t row_bytes, uint8_t* fits, int B, int Kin, int F, int C, hipStream_t s);
-// ... for a chunk of k blocks of a stream (k_fwd_fast_qps, ac_fast_fwd_qps.hip): k frames per signal, frame 0 pairs block 0 with
-// prev_block [B,N,C]; state_out (another buffer) receives block k - 1.  Serves where fast_encode_pack_serves() and the
-// instance passed the register gate
+inline int64_t plan_row_bytes(const ac_psy_plan* psy) { return (int64_t)((psy->row_bits + 31) / 32) * 4; }   // ceil(row_bits / 32) * 4
+bool fast_encode_quant_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);   // quant, quant_budget, their pcm16 forms
+bool fast_encode_pack_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);    // pack_rows, pack_rows_pcm16
 bool fast_encode_pack_stream_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);
-int launch_fwd_fast_pack_rows_stream(const ac_mdct_plan* p, const ac_psy_plan* psy, const float* x, float drown, uint8_t* data,
+bool fast_encode_pack_stream_pcm16_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);
+int launch_fwd_fast_quant(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, float* X, float* t, float* thr,
+                          float drown, int16_t* codes, int8_t* sf, int B, int Kin, int F, int C, hipStream_t s);
+int launch_fwd_fast_quant_budget(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, float* X, float* t, float* thr,
+                                 float drown, int16_t* codes, int8_t* sf, int B, int Kin, int F, int C, hipStream_t s);
+int launch_fwd_fast_pack_rows(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, float drown, uint8_t* data,
+                              int64_t row_bytes, uint8_t* fits, int B, int Kin, int F, int C, hipStream_t s);
+int launch_fwd_fast_pack_rows_stream(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, float drown, uint8_t* data,
                                      int64_t row_bytes, uint8_t* fits, const float* prev_block, float* state_out, int B, int k,
                                      int C, hipStream_t s);
-// the four above on 16-bit PCM (k_fwd_fast_q16 / qb16 / qp16 / qps16, ac_fast_fwd_*16.hip): x int16, read as pcm / 32768 in the
-// row loads -- the outputs of the float32 launch on pcm.to(float32) / 32768 bit for bit; the stream's state stays float32.  The
-// one-shot three serve where their float32 forms do; the stream form where its own instance passed the register gate
-int launch_fwd_fast_quant_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const int16_t* x, float* X, float* t, float* thr,
+int launch_fwd_fast_quant_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, float* X, float* t, float* thr,
                                 float drown, int16_t* codes, int8_t* sf, int B, int Kin, int F, int C, hipStream_t s);
-int launch_fwd_fast_quant_budget_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const int16_t* x, float* X, float* t,
-                                       float* thr, float drown, int row_bits, int kmin, int16_t* codes, int8_t* sf, int B, int Kin,
-                                       int F, int C, hipStream_t s);
-int launch_fwd_fast_pack_rows_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const int16_t* x, float drown, uint8_t* data,
+int launch_fwd_fast_quant_budget_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, float* X, float* t,
+                                       float* thr, float drown, int16_t* codes, int8_t* sf, int B, int Kin, int F, int C,
+                                       hipStream_t s);
+int launch_fwd_fast_pack_rows_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, float drown, uint8_t* data,
                                     int64_t row_bytes, uint8_t* fits, int B, int Kin, int F, int C, hipStream_t s);
-bool fast_encode_pack_stream_pcm16_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);
-int launch_fwd_fast_pack_rows_stream_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const int16_t* x, float drown,
+int launch_fwd_fast_pack_rows_stream_pcm16(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, float drown,
                                            uint8_t* data, int64_t row_bytes, uint8_t* fits, const float* prev_block,
                                            float* state_out, int B, int k, int C, hipStream_t s);
 int launch_inv_fast(const ac_mdct_plan* p, const float* X, void* x, int iof, const float* tail_in, float* tail_out,

@@ -14,7 +14,7 @@ bool transrate_serves(const ac_psy_plan* psy) {
 int launch_transrate(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes, const int64_t* index, uint8_t* out,
                      int64_t row_bytes, uint8_t* fits, int16_t* offset, long long rows, hipStream_t s) {
   if (rows <= 0) return AC_OK;
-  if (!transrate_serves(psy) || row_bytes != (int64_t)((psy->row_bits + 31) / 32) * 4) {
+  if (!transrate_serves(psy) || row_bytes != plan_row_bytes(psy)) {
     set_error("internal: no transrating kernel for filters_n = %d, %d bands, row budget %d", psy->N, psy->M, psy->row_bits);
     return AC_EUNSUPPORTED;
   }
