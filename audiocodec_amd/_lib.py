@@ -20,7 +20,8 @@ AC_PACKED = 16   # spectrum-side format of ac_stream_encode_typed / ac_stream_in
 AC_IN_PCM16 = 32   # x is int16 PCM: flag of ac_encode_fused_ex beside AC_EMIT_CODES / AC_EMIT_PACKED, and of
                    # ac_stream_encode_typed's dtype beside AC_PACKED
 AC_IN_PACKED = 64  # x is one ac_packed_rows: flag of ac_encode_fused_ex beside AC_EMIT_PACKED alone (transrating)
-AC_PACK_ROWS_MAX_BITS = 16384  # the largest row budget AC_EMIT_PACKED serves in one launch (the header's macro)
+AC_CONCEAL = 128   # beside AC_PACKED in ac_stream_inverse_typed's dtype: X_chunk is one ac_stream_packed_lost_in
+AC_PACK_ROWS_MAX_BITS = 16384 # the largest row budget AC_EMIT_PACKED serves in one launch (the header's macro)
 AC_CONCEAL_FADE = 4       # scale-factor units a concealed row loses per frame of age (the header's macro)
 AC_CONCEAL_MAX_AGE = 31   # the largest max_age of ac_conceal (the header's macro)
 WINDOW_IDS = {"vorbis": 0, "sine": 1}   # anything else -> 2 (rectangular), mdctransformer.py:199-211
@@ -158,6 +159,11 @@ class QuantizedRows(ctypes.Structure):
 class StreamPackedIn(ctypes.Structure):
     """``ac_stream_packed_in``: what ``ac_stream_inverse_typed`` takes for ``X_chunk`` under ``AC_PACKED``."""
     _fields_ = [("rows", PackedRows), ("psy", c_void_p), ("pcm16", ctypes.c_int32)]
+
+
+class StreamPackedLostIn(ctypes.Structure):
+    """``ac_stream_packed_lost_in``: what ``ac_stream_inverse_typed`` takes for ``X_chunk`` under ``AC_PACKED | AC_CONCEAL``."""
+    _fields_ = [("inner", StreamPackedIn), ("lost", c_void_p), ("max_age", ctypes.c_int32)]
 
 
 _lock = threading.Lock()

@@ -617,6 +617,7 @@ class StreamingMDCT:
             _lib.check(self._lib.ac_stream_create(mdct._plan(self.device), self.B, self.C, ctypes.byref(handle)))
         self._handle = handle
         self._graphs = {}       # run(..., graph=True): captured calls by input buffers and arguments
+        self._conceal = None    # decode_packed_chunk(lost=...) where it is composed: (carried codes, sf, gap), None = no source
 
     def close(self):
         self._graphs = {}       # (the graphs hold launches that address the stream's state)
@@ -631,6 +632,7 @@ class StreamingMDCT:
             pass
 
     def reset(self):
+        self._conceal = None
         with _host.on_device(self.device):
             _lib.check(self._lib.ac_stream_reset(self._handle, _host.stream_ptr(self.device)))
 
@@ -712,6 +714,7 @@ class StreamingMDCT:
         go (one stereo clip in chunks of 256 blocks: 7.9 us per chunk against 11.9).  A replay reads the CURRENT contents
         of the same input buffers and overwrites the output tensors of the first call, which are returned again."""
         _host.require_float32(self.mdct.compute_dtype, "StreamingMDCT.run (use the chunk calls for bfloat16 / float64 streams)")
+        self._conceal = None    # (the synthesis state moves on without a source for concealment)
         if graph:
             return self._run_graph(x, blocks_per_chunk, masking, synthesis, drown)
         k, N = int(blocks_per_chunk), self.mdct.filters_n
@@ -820,6 +823,7 @@ class StreamingMDCT:
             raise ValueError("X_chunk must be [%d, k, %d, %d], got %s" % (self.B, self.mdct.filters_n, self.C,
                                                                          tuple(X.shape)))
         x = self._out(out, "out", (B, k * N, C), X, stream)
+        self._conceal = None    # (as the library does: a chunk that does not conceal leaves no source)
         with _host.on_device(X.device):
             _lib.check(self._lib.ac_stream_inverse_typed(self._handle, _host.ptr(X), _host.ptr(x), self.mdct._dtype_id, k,
                                                          self._stream(stream)))
@@ -844,15 +848,21 @@ class StreamingMDCT:
             return None
         return (self.psy.row_budget[0] + 31) // 32 * 4
 
-    def packed_chunk_launches(self, decode=False, *, pcm16=False):
+    def packed_chunk_launches(self, decode=False, *, conceal=False, pcm16=False):
         """Library launches of :meth:`encode_packed_rows_chunk` (``decode=True``: of :meth:`decode_packed_chunk`) on this
         stream (``ac_stream_packed_launches``): 1 = one launch that carries the overlap state -- filters_n = 1024, 64 bands,
         mono / stereo, a budget of at most ``_lib.AC_PACK_ROWS_MAX_BITS``, and for the encode a kernel instance that passed
         the register gate (stereo with ``spreading="f32"`` did not) -- else the launches of the composition (everywhere
         while ``AC_ENCODE_PACKED_NOFUSE=1`` / ``AC_DECODE_PACKED_NOFUSE=1`` is set: read per call).  0 for the encode on a
         stream without a row budget.  ``pcm16=True``: of the encode on a ``torch.int16`` chunk
-        (``ac_stream_packed_launches_pcm16``; its instances passed the gate with ``spreading="bf16x2_mfma"`` only)."""
+        (``ac_stream_packed_launches_pcm16``; its instances passed the gate with ``spreading="bf16x2_mfma"`` only).
+        ``decode=True, conceal=True``: of :meth:`decode_packed_chunk` with ``lost`` given -- 1 wherever the plain decode is
+        1, else the 3 library launches of its composition."""
         self._packed_ready("packed_chunk_launches", False)
+        if conceal:
+            if not decode:
+                raise ValueError("conceal=True is a form of the decode: pass decode=True")
+            return int(self._lib.ac_stream_packed_launches(self._handle, self.psy._plan(self.device), 2))
         if pcm16 and not decode:
             return int(self._lib.ac_stream_packed_launches_pcm16(self._handle, self.psy._plan(self.device)))
         return int(self._lib.ac_stream_packed_launches(self._handle, self.psy._plan(self.device), 1 if decode else 0))
@@ -898,20 +908,32 @@ class StreamingMDCT:
             data, fits = _pack_rows_of_spectra(self.psy, X, thr, index, rb)
             return data, index, fits
 
-    def decode_packed_chunk(self, data, index, pcm16=False, out=None, stream=None):
+    def decode_packed_chunk(self, data, index, pcm16=False, out=None, stream=None, *, lost=None, max_age=8):
         """data uint8 [nbytes], index int64 [B, k, C] -> x [B, k*N, C] (``torch.int16`` with ``pcm16=True``): the next k
         blocks of the signal, bit-equal to ``inverse_chunk(psy.dequantize(*psy.unpack(data, index)))`` -- with ``pcm16``
         through the store of ``AudioCodec.decode``: ``0 if NaN else clamp(rint(fp32(32768 * x)), -32768, 32767)``.
         ``index`` may hold any row starts and damaged rows read as ``psy.unpack`` reads them.  One launch where
         ``packed_chunk_launches(decode=True)`` is 1, else that composition.  Only enqueues, on ``stream`` or the current
-        stream; float32 only."""
+        stream; float32 only.
+
+        ``lost`` uint8 / bool [B, k, C] marks rows that did not arrive, and they are concealed as
+        ``AudioCodec.decode_packed(..., lost=, max_age=)`` conceals them, with the last row that
+        arrived carried from chunk to chunk: however a signal is split into chunks, the outputs are the blocks of that
+        one-shot call on the whole signal, bit for bit; each row takes the ``max_age`` of its own call.  The carried row
+        is the stream's state: :meth:`reset`, and every chunk that is decoded or inverted without ``lost``, leave no
+        source behind.  One launch where ``packed_chunk_launches(decode=True, conceal=True)`` is 1, else the
+        composition with the same state kept in tensors."""
         self._packed_ready("decode_packed_chunk", False)
         N = self.mdct.filters_n
         with self._on(stream):
+            if lost is not None:
+                max_age = self.psy._check_max_age(max_age)
             data = self.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
             if data.device != self.device:
                 raise ValueError("data lives on %s but the stream's state lives on %s" % (data.device, self.device))
             index = self.psy._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
+            if lost is not None:
+                lost = self.psy._check_lost(lost, index)
             B, k, C = index.shape
             if (B, C) != (self.B, self.C):
                 raise ValueError("index must be [%d, k, %d], got %s" % (self.B, self.C, tuple(index.shape)))
@@ -920,6 +942,9 @@ class StreamingMDCT:
                 return x
             dev = data.device
             psy = self.psy._plan(dev)
+            if lost is not None:
+                return self._decode_packed_chunk_concealed(data, index, lost, max_age, pcm16, x, psy, stream)
+            self._conceal = None   # (a chunk that does not conceal leaves no source; the library marks its own state)
             if self._lib.ac_stream_packed_launches(self._handle, psy, 1) == 1:
                 rows = _lib.StreamPackedIn(_lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr()), psy.value,
                                            1 if pcm16 else 0)
@@ -927,9 +952,58 @@ class StreamingMDCT:
                     _lib.check(self._lib.ac_stream_inverse_typed(self._handle, ctypes.addressof(rows), _host.ptr(x),
                                                                  _lib.AC_PACKED, k, self._stream(stream)))
                 return x
-            X = self.psy.dequantize(*self.psy.unpack(data, index))
-            if not pcm16:
-                return self.inverse_chunk(X, out=x, stream=stream)
-            p = torch.nan_to_num(self.inverse_chunk(X, stream=stream) * 32768.0, nan=0.0)   # the float32 product
-            x.copy_(p.round_().clamp_(-32768.0, 32767.0).to(torch.int16))                   # round: half to even
+            return self._inverse_chunk_into(self.psy.dequantize(*self.psy.unpack(data, index)), x, pcm16, stream)
+
+    def _inverse_chunk_into(self, X, x, pcm16, stream):
+        """:meth:`inverse_chunk` of X into x, through the 16-bit PCM store where x is int16."""
+        if not pcm16:
+            return self.inverse_chunk(X, out=x, stream=stream)
+        p = torch.nan_to_num(self.inverse_chunk(X, stream=stream) * 32768.0, nan=0.0)   # the float32 product
+        x.copy_(p.round_().clamp_(-32768.0, 32767.0).to(torch.int16))                   # round: half to even
+        return x
+
+    def _decode_packed_chunk_concealed(self, data, index, lost, max_age, pcm16, x, psy, stream):
+        """:meth:`decode_packed_chunk` with ``lost`` given (checked; under the stream the work runs on): the one launch where
+        the library has it, else the composition, which keeps the state the kernel keeps -- the carried row as
+        ``psy.unpack`` read it, and the gap (frames since that row at the end of the chunk before; 32: none in reach) -- in
+        ``self._conceal``.  Nothing here waits for the device."""
+        B, k, C = index.shape
+        dev = data.device
+        if self._lib.ac_stream_packed_launches(self._handle, psy, 2) in (1, 2):
+            self._conceal = None   # (the state lives in the library from here on)
+            rows = _lib.StreamPackedLostIn(
+                _lib.StreamPackedIn(_lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr()), psy.value,
+                                    1 if pcm16 else 0), lost.data_ptr(), max_age)
+            with _host.on_device(dev):
+                _lib.check(self._lib.ac_stream_inverse_typed(self._handle, ctypes.addressof(rows), _host.ptr(x),
+                                                             _lib.AC_PACKED | _lib.AC_CONCEAL, k, self._stream(stream)))
             return x
+        codes, sf = self.psy.unpack(data, index)
+        state = self._conceal
+        if state is None:   # a new stream, after reset(), or after a chunk that did not conceal: no source
+            state = (torch.zeros_like(codes[:, :1]), torch.zeros_like(sf[:, :1]),
+                     torch.full((B, C), 32, dtype=torch.int64, device=dev))
+        row_codes, row_sf, gap = state
+        # the carried row in front as frame -1; sources as DESIGN.md section 8f defines them
+        codes_ext, sf_ext = torch.cat((row_codes, codes), dim=1), torch.cat((row_sf, sf), dim=1)
+        f = torch.arange(k, dtype=torch.int64, device=dev).view(1, k, 1)
+        last = f.expand(B, k, C).masked_fill(lost != 0, -1).cummax(dim=1).values   # the last frame <= f of the chunk that arrived
+        inside = (last >= 0) & (f - last <= max_age)
+        carried_age = gap.view(B, 1, C) + f + 1
+        carried = ~inside & (gap.view(B, 1, C) <= 31) & (carried_age <= max_age)
+        muted = ~inside & ~carried
+        src = torch.where(inside, last + 1, torch.zeros_like(last))               # frame of codes_ext
+        age = torch.where(inside, f - last, carried_age).masked_fill(muted, 0).to(torch.uint8)
+        N, M = codes.shape[2], sf.shape[2]
+        got_codes = codes_ext.gather(1, src.unsqueeze(2).expand(B, k, N, C)).masked_fill(muted.unsqueeze(2), 0)
+        got_sf = sf_ext.gather(1, src.unsqueeze(2).expand(B, k, M, C)).masked_fill(muted.unsqueeze(2), 0)
+        self._inverse_chunk_into(self.psy.dequantize(got_codes, self.psy.conceal_fade(got_sf, age)), x, pcm16, stream)
+        # the state after the chunk, whatever max_age was
+        final = last[:, -1]                                                         # [B, C]: f*, or -1
+        has = final >= 0
+        at = final.clamp(min=0).view(B, 1, 1, C)
+        new_codes = torch.where(has.view(B, 1, 1, C), codes.gather(1, at.expand(B, 1, N, C)), row_codes)
+        new_sf = torch.where(has.view(B, 1, 1, C), sf.gather(1, at.expand(B, 1, M, C)), row_sf)
+        new_gap = torch.where(has, k - 1 - final, gap + k).clamp(max=32)
+        self._conceal = (new_codes, new_sf, new_gap)   # (after inverse_chunk, which leaves no source)
+        return x

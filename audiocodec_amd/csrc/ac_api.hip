@@ -989,6 +989,7 @@ int ac_stream_reset(ac_stream* s, void* stream) {
   AC_HIP_CHECK(hipMemsetAsync(s->d_tail, 0, nt, (hipStream_t)stream));
   if (s->d_prev64) AC_HIP_CHECK(hipMemsetAsync(s->d_prev64, 0, 2 * nb, (hipStream_t)stream));
   if (s->d_tail64) AC_HIP_CHECK(hipMemsetAsync(s->d_tail64, 0, 2 * nt, (hipStream_t)stream));
+  s->conceal_stale = true;   // (the concealment state, where there is one: the next concealing chunk reads every gap as 32)
   return AC_OK;
 }
 
@@ -1002,6 +1003,7 @@ int ac_stream_destroy(ac_stream* s) {
   (void)hipFree(s->d_prev64);
   (void)hipFree(s->d_tail64);
   (void)hipFree(s->d_tail64_tmp);
+  (void)hipFree(s->d_conceal);
   delete s;
   return AC_OK;
 }
@@ -1079,6 +1081,7 @@ int ac_stream_inverse(ac_stream* s, const float* X_chunk, float* x, int k, void*
     st = launch_inv_generic(p, X_chunk, x, s->d_tail, s->d_tail_tmp, s->B, k, k, s->C, hs);
   if (st) return st;
   std::swap(s->d_tail, s->d_tail_tmp);
+  s->conceal_stale = true;
   return AC_OK;
 }
 
@@ -1089,6 +1092,7 @@ int ac_stream_inverse(ac_stream* s, const float* X_chunk, float* x, int k, void*
 // at home when the replay starts: after chunk calls (ac_stream_forward / _encode / _inverse), call ac_stream_settle first.
 static int settle_state(ac_stream* s, hipStream_t hs) {
   DeviceGuard guard(s->device);
+  s->conceal_stale = true;   // (what follows -- ac_stream_run, or a replay the library never sees -- advances d_tail and conceals nothing)
   if (s->d_prev_block != s->d_prev_home) {
     AC_HIP_CHECK(hipMemcpyAsync(s->d_prev_home, s->d_prev_block, (size_t)s->B * s->N * s->C * sizeof(float), hipMemcpyDeviceToDevice, hs));
     std::swap(s->d_prev_block, s->d_prev_tmp);
@@ -1154,6 +1158,7 @@ int ac_stream_run(ac_stream* s, const ac_psy_plan* psy, int nchunks, int k, cons
       if (!st) {
         std::swap(s->d_prev_block, s->d_prev_tmp);
         std::swap(s->d_tail, s->d_tail_tmp);
+        s->conceal_stale = true;
       }
     }
     if (!st) st = ac_stream_inverse(s, X_chunks[nchunks - 1], xhat_chunks[nchunks - 1], k, stream);
@@ -1591,7 +1596,9 @@ static bool stream_encode_packed_fuses(const ac_stream* s, const ac_psy_plan* ps
 
 int ac_stream_packed_launches(const ac_stream* s, const ac_psy_plan* psy, int decode) {
   if (!stream_packed_args_match(s, psy)) return 0;
-  if (decode) return decode_packed_fuses(s->plan, psy, s->C) ? 1 : 3;   // ac_unpack, ac_dequantize, ac_stream_inverse
+  // ac_unpack, ac_dequantize, ac_stream_inverse (decode == 2, concealing: the fade between them is the caller's)
+  if (decode == 2) return decode_packed_fuses(s->plan, psy, s->C) && fast_inv_packed_conceal_stream_serves(s->plan, psy, s->C) ? 1 : 3;
+  if (decode) return decode_packed_fuses(s->plan, psy, s->C) ? 1 : 3;
   if (!psy->row_bits) return 0;
   // ac_stream_encode, ac_quantize_budget, ac_pack
   return stream_encode_packed_fuses(s, psy, false) ? 1 : ac_encode_launches(s->plan, psy, s->C) + 2;
@@ -1667,6 +1674,74 @@ static int stream_inverse_packed(ac_stream* s, const ac_stream_packed_in* in, vo
                               s->B, k, k, s->C, (hipStream_t)stream);
   if (st) return st;
   std::swap(s->d_tail, s->d_tail_tmp);
+  s->conceal_stale = true;
+  return AC_OK;
+}
+
+// the concealment state of a stream (AC_PACKED | AC_CONCEAL): allocated and zeroed -- the padding behind every carried row stays
+// zero from here on -- by the first concealing call, on that call's stream
+static size_t conceal_gap_bytes(const ac_stream* s) { return ((size_t)s->B * (size_t)s->C + 15) / 16 * 16; }
+static int stream_conceal_state(ac_stream* s, hipStream_t hs) {
+  if (s->d_conceal) return AC_OK;
+  const size_t n = 2 * (conceal_state_row_bytes(s->B, s->C) + conceal_gap_bytes(s));
+  hipError_t e = hipMalloc((void**)&s->d_conceal, n);
+  if (e == hipSuccess) e = hipMemsetAsync(s->d_conceal, 0, n, hs);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(s->d_conceal);
+    s->d_conceal = nullptr;
+    set_error("concealment state allocation failed: %s", hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? AC_ENOMEM : AC_EHIP;
+  }
+  s->conceal_cur = 0;
+  s->conceal_stale = true;
+  return AC_OK;
+}
+
+static int stream_inverse_packed_conceal(ac_stream* s, const ac_stream_packed_lost_in* in, void* x, int k, void* stream) {
+  AC_REQUIRE(s != nullptr, "stream is NULL");
+  AC_REQUIRE(k >= 0, "negative chunk length %d", k);
+  AC_REQUIRE(in != nullptr, "AC_PACKED | AC_CONCEAL without its ac_stream_packed_lost_in (X_chunk)");
+  const ac_stream_packed_lost_in li = *in;
+  const ac_stream_packed_in& pin = li.in;
+  const ac_psy_plan* psy = pin.psy;
+  const ac_mdct_plan* p = s->plan;
+  AC_REQUIRE(psy != nullptr, "ac_stream_packed_in: psy is NULL");
+  int st = check_plan_pair(p, psy);
+  if (st) return st;
+  AC_REQUIRE(pin.pcm16 == 0 || pin.pcm16 == 1, "ac_stream_packed_in: pcm16 must be 0 or 1 (got %d)", (int)pin.pcm16);
+  AC_REQUIRE(li.max_age >= 0 && li.max_age <= AC_CONCEAL_MAX_AGE, "ac_stream_packed_lost_in: max_age (%d) outside [0, %d]",
+             (int)li.max_age, AC_CONCEAL_MAX_AGE);
+  AC_REQUIRE(li.lost != nullptr, "ac_stream_packed_lost_in: lost is NULL");
+  if (k == 0) return AC_OK;
+  if (ac_stream_packed_launches(s, psy, 2) != 1) {
+    set_error("AC_PACKED | AC_CONCEAL: no kernel decodes a chunk of packed rows with lost rows concealed in one launch for "
+              "filters_n = %d, bark_bands_n = %d, %d channels here (ac_stream_packed_launches(s, psy, 2) != 1): compose it from "
+              "ac_unpack, the fade, ac_dequantize and ac_stream_inverse, and carry the last row that arrived yourself",
+              p->N, psy->M, s->C);
+    return AC_EUNSUPPORTED;
+  }
+  st = check_quant(psy, s->B, k, s->C);
+  if (st) return st;
+  AC_REQUIRE(pin.rows.nbytes >= 0, "negative nbytes (%lld)", (long long)pin.rows.nbytes);
+  AC_REQUIRE(pin.rows.index != nullptr && x != nullptr, "NULL tensor pointer");
+  AC_REQUIRE(pin.rows.data != nullptr || pin.rows.nbytes == 0, "data is NULL");
+  AC_REQUIRE_ALIGNED(pin.rows.data, pin.rows.index, x);
+  DeviceGuard guard(s->device);
+  hipStream_t hs = (hipStream_t)stream;
+  st = stream_conceal_state(s, hs);
+  if (st) return st;
+  const size_t nr = conceal_state_row_bytes(s->B, s->C), ng = conceal_gap_bytes(s);
+  uint8_t* rows[2] = {s->d_conceal, s->d_conceal + nr};
+  uint8_t* gaps[2] = {s->d_conceal + 2 * nr, s->d_conceal + 2 * nr + ng};
+  const int cur = s->conceal_cur;
+  st = launch_inv_fast_packed_conceal_stream(p, psy, pin.rows.data, pin.rows.nbytes, pin.rows.index, li.lost, li.max_age, x,
+                                             pin.pcm16 != 0, s->d_tail, s->d_tail_tmp, gaps[cur], rows[cur], gaps[cur ^ 1],
+                                             rows[cur ^ 1], s->conceal_stale, s->B, k, s->C, hs);
+  if (st) return st;
+  std::swap(s->d_tail, s->d_tail_tmp);
+  s->conceal_cur = cur ^ 1;
+  s->conceal_stale = false;
   return AC_OK;
 }
 
@@ -1721,6 +1796,8 @@ int ac_stream_encode_typed(ac_stream* s, const ac_psy_plan* psy, const void* x_c
 
 int ac_stream_inverse_typed(ac_stream* s, const void* X_chunk, void* x, int dtype, int k, void* stream) {
   if (dtype == AC_PACKED) return stream_inverse_packed(s, static_cast<const ac_stream_packed_in*>(X_chunk), x, k, stream);
+  if (dtype == (AC_PACKED | AC_CONCEAL))
+    return stream_inverse_packed_conceal(s, static_cast<const ac_stream_packed_lost_in*>(X_chunk), x, k, stream);
   AC_REQUIRE_DTYPE(dtype);
   if (dtype == AC_F32) return ac_stream_inverse(s, static_cast<const float*>(X_chunk), static_cast<float*>(x), k, stream);
   int st = stream_typed_check(s, dtype, k);
@@ -1740,6 +1817,7 @@ int ac_stream_inverse_typed(ac_stream* s, const void* X_chunk, void* x, int dtyp
   st = launch_inv_fast(s->plan, static_cast<const float*>(X_chunk), x, 2, s->d_tail, s->d_tail_tmp, s->B, k, k, s->C, (hipStream_t)stream);
   if (st) return st;
   std::swap(s->d_tail, s->d_tail_tmp);
+  s->conceal_stale = true;
   return AC_OK;
 }
 

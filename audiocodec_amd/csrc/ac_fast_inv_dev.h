@@ -1,5 +1,6 @@
 // Synthesis of the wave-level kernels for filters_n = 1024 / 2048 (ac_fast_dev.h): the body shared by k_inv_fast,
-// k_inv_fast_q (instantiated in ac_fast_inv.hip), k_inv_fast_p (ac_fast_inv_p.hip) and k_duplex_fast (ac_fast_fwd.hip), and
+// k_inv_fast_q (instantiated in ac_fast_inv.hip), k_inv_fast_p (ac_fast_inv_p.hip), its concealing forms k_inv_fast_pl
+// (ac_fast_inv_pl.hip) and k_inv_fast_pls (ac_fast_inv_pls.hip) and k_duplex_fast (ac_fast_fwd.hip), and
 // prep_inv_fast(), the host code that fills its arguments for these objects (InvArgs has internal linkage, so no function
 // can pass it between them).
 #pragma once
@@ -70,11 +71,12 @@ struct QuantRows {
 template <int R, int CMODE, int NW, int IOF = 0>
 __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const int bid, const int nblocks,
                                               const QuantRows* qr = nullptr, const PackedRows* pr = nullptr,
-                                              const ConcealRows* cl = nullptr) {
+                                              const ConcealRows* cl = nullptr, const ConcealState* cs = nullptr) {
   using G = Geo<R>;
   constexpr bool QUANT = IOF >= 3;
   constexpr bool PACKED = IOF >= 5;   // (IOF 5 / 6) the quantised spectra come as rows of the packed bitstream
   constexpr bool CONCEAL = IOF >= 7;  // (IOF 7 / 8) ... and a row that did not arrive is concealed (ConcealRows)
+  constexpr bool CSTREAM = IOF >= 9;  // (IOF 9 / 10) ... with the last row of the chunks before as a source (ConcealState)
   static_assert(!PACKED || R == 8, "packed rows: filters_n = 1024");
   constexpr int OIOF = PACKED ? (IOF - 5) % 2 : QUANT ? IOF - 3 : IOF;   // format of the PCM side
   constexpr int FH = G::FH;
@@ -119,7 +121,7 @@ __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const
   uint32_t* rec = reinterpret_cast<uint32_t*>(lds + NW * WAVE_LDS + G::TAB_LDS + (PACKED ? wave * P_REC_BYTES : 0));
   auto load_frame = [&](int n, const spec_t* r0, const spec_t* r1, hold_t (&dst)[R]) {
     if constexpr (PACKED) {
-      load_row_p<R>(*pr, rec, n - (n0 - 1), bw, has1, dst);
+      load_row_p<R, CSTREAM>(*pr, rec, n - (n0 - 1), bw, has1, dst, cs);
     } else if constexpr (QUANT) {
       const size_t mc = (size_t)qr->M * C;
       const int8_t* sf0 = qr->sf + row_off(pq.b0, a.Kp, n, mc, pq.c0);
@@ -173,8 +175,8 @@ __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const
   if constexpr (PACKED) {
     // slot 0 is frame n0-1, read only by a wave that transforms it itself
     if (valid)
-      parse_strip_p<CONCEAL>(*pr, pq.b0, pq.b1, pq.c0, pq.c1, a.Kp, C, n0 - 1, (left && !deferred) ? 0 : 1,
-                             min(n1, a.Kp) - (n0 - 1), has1, lane, buf, rec, cl);
+      parse_strip_p<CONCEAL, CSTREAM>(*pr, pq.b0, pq.b1, pq.c0, pq.c1, a.Kp, C, n0 - 1, (left && !deferred) ? 0 : 1,
+                                      min(n1, a.Kp) - (n0 - 1), has1, lane, buf, rec, cl, cs);
   }
   if (valid) {
     hold_t ahead[R];
@@ -254,6 +256,9 @@ __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const
         a.tail_out[ts0 + j] = carry[j2].x;
         if (has1) a.tail_out[ts1 + j] = carry[j2].y;
       }
+    }
+    if constexpr (CSTREAM) {   // ... and the concealment state with it
+      if (n1 == a.nblk) carry_state_p(*pr, *cl, *cs, pq.b0, pq.b1, pq.c0, pq.c1, a.Kp, C, has1, lane);
     }
   }
 

@@ -20,6 +20,12 @@
 // arrive is read from the last row of its clip and channel that did, at most max_age frames back, with every scale factor
 // lowered by AC_CONCEAL_FADE per frame of age; a row with no such source reads as a row that starts at nbytes (silence).
 // Only the row start and the sf byte of the band records change: load_row_p and extract_row_p see a row like any other.
+//
+// ... in a stream (parse_strip_p<true, true>, k_inv_fast_pls in ac_fast_inv_pls.hip): the launch is one chunk, and the last row
+// that arrived before it is carried in the stream's state (ConcealState) with its gap, the frames of the stream since it.  A
+// lane that looks at a frame before the chunk finds that row there, the row is read from the state buffer -- a second base
+// the row's loads select with a wave-uniform flag -- and the wave that owns a signal's last strip leaves the new state in the
+// other half of a double buffer (carry_state_p).
 #pragma once
 #include "ac_fast_dev.h"
 
@@ -38,6 +44,21 @@ struct ConcealRows {
   const uint8_t* lost;     // [B, Kp, C]: nonzero = the row did not arrive
   int max_age;             // 0 .. AC_CONCEAL_MAX_AGE (31: a lane of half a wave per frame looked back at)
 };
+
+// (streams) the concealment state of a chunked decode, double buffered: other strips of a signal still read what its last strip
+// replaces.  A carried row is the P_CARRY_WORDS words from the row's start -- the most a row of 64 bands and 1024 bins takes --
+// at a stride that keeps the two further words a code window may touch inside the buffer (they stay 0): plain dword loads.
+struct ConcealState {
+  const uint8_t* gap;      // [B, C]: frames since the last row that arrived, at the end of the previous chunk; 32 = none in reach
+  const uint8_t* row;      // [B, C] carried rows, P_CARRY_STRIDE bytes apart
+  uint8_t* gap_out;        // the state after this chunk
+  uint8_t* row_out;
+  int64_t row_bytes;       // B C P_CARRY_STRIDE
+  int stale;               // nonzero: every gap reads as 32 (a new stream, after a reset or a chunk that did not conceal)
+};
+constexpr int P_CARRY_WORDS = (5 * 64 + 8 * 64 + 16 * 1024) / 32;   // 538
+constexpr int P_CARRY_STRIDE = 2176;
+constexpr int P_NO_SOURCE = 32;               // a gap no max_age (<= 31) reaches
 
 constexpr int P_M = 64;                       // bands of a row = lanes of a wave
 constexpr int P_SLOTS = 4;                    // frames a strip reads: at most 3 output blocks and the frame before them
@@ -74,14 +95,20 @@ __device__ __forceinline__ uint32_t p_pos(uint32_t rec, uint32_t d) {
 }
 
 // The records of the rows of frames base + slot, slot in [slot_lo, slot_hi), of the wave's two signals.  buf: the wave's FFT
-// buffer (free before the frame loop); rec: the wave's record region.  CONCEAL: the rows are looked up through cl (above).
-template <bool CONCEAL = false>
+// buffer (free before the frame loop); rec: the wave's record region.  CONCEAL: the rows are looked up through cl (above);
+// STREAM: frame -1 - gap is the carried row of cs.
+template <bool CONCEAL = false, bool STREAM = false>
 __device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0, long long b1, int c0, int c1, int Kp, int C,
                                               int base, int slot_lo, int slot_hi, bool has1, int lane, char* buf,
-                                              uint32_t* rec, const ConcealRows* cl = nullptr) {
+                                              uint32_t* rec, const ConcealRows* cl = nullptr, const ConcealState* cs = nullptr) {
+  static_assert(CONCEAL || !STREAM, "the carried row is a source of concealment");
   uint32_t* st = reinterpret_cast<uint32_t*>(buf);   // [P_ROWS][P_HDR_WORDS]
   uint32_t* info = rec + P_ROWS * P_M;
   const int sig = lane >> 5, k = lane & 31;          // half a wave per row: slot t, signal sig
+  int gap = P_NO_SOURCE;                             // (STREAM) of the half wave's signal: one load, ahead of every slot's `lost`
+  if constexpr (STREAM) {
+    if ((sig == 0 || has1) && !cs->stale) gap = (int)cs->gap[(size_t)(sig ? b1 : b0) * (size_t)C + (size_t)(sig ? c1 : c0)];
+  }
 #pragma unroll
   for (int t = 0; t < P_SLOTS; ++t) {
     int age = 0;         // (CONCEAL) frames back to the row that is read in this one's place ...
@@ -94,8 +121,16 @@ __device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0
       const int c = sig ? c1 : c0;
       const int f = base + t;
       if (on && k < P_HDR_WORDS) own = pr.index[((size_t)b * (size_t)Kp + (size_t)f) * (size_t)C + (size_t)c];
-      const bool there = on && k <= min(cl->max_age, f) &&
-                         cl->lost[((size_t)b * (size_t)Kp + (size_t)(f - k)) * (size_t)C + (size_t)c] == 0;
+      bool there;
+      if constexpr (STREAM) {
+        // a frame before the chunk is there exactly where the carried row sits: gap frames before frame 0 (32: nowhere)
+        const bool look = on && k <= cl->max_age;
+        there = look && k > f && f - k == -1 - gap;
+        if (look && k <= f) there = cl->lost[((size_t)b * (size_t)Kp + (size_t)(f - k)) * (size_t)C + (size_t)c] == 0;
+      } else {
+        there = on && k <= min(cl->max_age, f) &&
+                cl->lost[((size_t)b * (size_t)Kp + (size_t)(f - k)) * (size_t)C + (size_t)c] == 0;
+      }
       const uint64_t m = __builtin_amdgcn_ballot_w64(there);
       const uint32_t mh = sig ? (uint32_t)(m >> 32) : (uint32_t)m;
       muted = mh == 0u;
@@ -106,20 +141,31 @@ __device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0
       const long long b = sig ? b1 : b0;
       const int c = sig ? c1 : c0;
       int64_t a;
+      bool carried = false;   // (STREAM) the source lies before the chunk: the carried row of (b, c)
+      if constexpr (STREAM) carried = !muted && age > base + t;
       if constexpr (CONCEAL) {
         a = own;
-        if (age != 0) a = pr.index[((size_t)b * (size_t)Kp + (size_t)(base + t - age)) * (size_t)C + (size_t)c];
+        if (age != 0 && !carried) a = pr.index[((size_t)b * (size_t)Kp + (size_t)(base + t - age)) * (size_t)C + (size_t)c];
         if (muted) a = pr.nbytes;
       } else {
         a = pr.index[((size_t)b * (size_t)Kp + (size_t)(base + t)) * (size_t)C + (size_t)c];
       }
       // a row start beyond the buffer reads nothing; clamping it keeps start + 4 k from overflowing
       a = a > pr.nbytes ? pr.nbytes : (a < -(1ll << 40) ? -(1ll << 40) : a);
-      st[r * P_HDR_WORDS + k] = p_load_word(pr.data, pr.nbytes, a + 4ll * k);
+      const uint8_t* src = pr.data;
+      int64_t bound = pr.nbytes;
+      if constexpr (STREAM) {
+        if (carried) {
+          a = ((int64_t)b * C + c) * P_CARRY_STRIDE;
+          src = cs->row;
+          bound = cs->row_bytes;
+        }
+      }
+      st[r * P_HDR_WORDS + k] = p_load_word(src, bound, a + 4ll * k);
       if (k == 0) {
         info[4 * r] = (uint32_t)(uint64_t)a;
         info[4 * r + 1] = (uint32_t)((uint64_t)a >> 32);
-        if constexpr (CONCEAL) info[4 * r + 3] = (uint32_t)age;
+        if constexpr (CONCEAL) info[4 * r + 3] = (uint32_t)age | (carried ? 0x100u : 0u);   // bit 8: read from the state buffer
       }
     }
   }
@@ -145,7 +191,7 @@ __device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0
     if (w == 31) sfb = 0x80u;
     else if (p_stores(w)) sfb = p_get_bits(sr, 5u * P_M + 8u * (ex >> 16), 8);
     if constexpr (CONCEAL) {   // every sf but -128 fades: max(s - AC_CONCEAL_FADE * age, -127)
-      const int fade = 4 * __builtin_amdgcn_readfirstlane((int)info[4 * r + 3]);
+      const int fade = 4 * (__builtin_amdgcn_readfirstlane((int)info[4 * r + 3]) & (STREAM ? 0xff : -1));
       if (sfb != 0x80u) sfb = (uint32_t)max((int)(int8_t)sfb - fade, -127) & 0xffu;
     }
     rec[r * P_M + lane] = ((cbase + (ex & 0xffffu)) << 13) | (sfb << 5) | w;
@@ -153,7 +199,12 @@ __device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0
       // plain loads where every word a window of this row can touch -- its ceil(bits / 32) words and two more -- is in data
       const int64_t a = (int64_t)((uint64_t)info[4 * r] | ((uint64_t)info[4 * r + 1] << 32));
       const int64_t nw = (int64_t)((cbase + (total & 0xffffu) + 31u) >> 5);
-      info[4 * r + 2] = (a >= 0 && (a & 3) == 0 && a + 4 * (nw + 2) <= pr.nbytes) ? 1u : 0u;
+      if constexpr (STREAM) {   // bit 1: the row is read from the state buffer
+        const uint32_t sel = (info[4 * r + 3] >> 8) & 1u;
+        info[4 * r + 2] = ((a >= 0 && (a & 3) == 0 && a + 4 * (nw + 2) <= (sel ? cs->row_bytes : pr.nbytes)) ? 1u : 0u) | (sel << 1);
+      } else {
+        info[4 * r + 2] = (a >= 0 && (a & 3) == 0 && a + 4 * (nw + 2) <= pr.nbytes) ? 1u : 0u;
+      }
     }
   }
   wave_sync();
@@ -171,16 +222,24 @@ __device__ __forceinline__ void load_bw_p(const PackedRows& pr, int lane, uint32
 }
 
 // the window loads of row r: only loads, LDS reads and address arithmetic
-template <int R>
+// (STREAM: bit 1 of the row's flag word selects the state buffer of cs as base and bound -- one choice per row and wave)
+template <int R, bool STREAM = false>
 __device__ __forceinline__ void load_sig_p(const PackedRows& pr, const uint32_t* rec, int r, const uint32_t (&bw)[R],
-                                           uint32_t (&lo)[R], uint32_t (&hi)[R]) {
+                                           uint32_t (&lo)[R], uint32_t (&hi)[R], const ConcealState* cs = nullptr) {
   const uint32_t* info = rec + P_ROWS * P_M;
   const uint32_t* rr = rec + r * P_M;
   const uint32_t a_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)info[4 * r]);
   const uint32_t a_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)info[4 * r + 1]);
   const int64_t a = (int64_t)((uint64_t)a_lo | ((uint64_t)a_hi << 32));
-  if (__builtin_amdgcn_readfirstlane((int)info[4 * r + 2])) {
-    const uint32_t* row = reinterpret_cast<const uint32_t*>(pr.data + a);
+  const int flag = __builtin_amdgcn_readfirstlane((int)info[4 * r + 2]);
+  const uint8_t* data = pr.data;
+  int64_t nbytes = pr.nbytes;
+  if constexpr (STREAM) {
+    data = (flag & 2) ? cs->row : pr.data;
+    nbytes = (flag & 2) ? cs->row_bytes : pr.nbytes;
+  }
+  if (STREAM ? (flag & 1) : flag) {
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(data + a);
 #pragma unroll
     for (int i = 0; i < R; ++i) {
       const uint32_t wi = p_pos(rr[bw[i] & 63u], bw[i] >> 12) >> 5;
@@ -191,17 +250,17 @@ __device__ __forceinline__ void load_sig_p(const PackedRows& pr, const uint32_t*
 #pragma unroll
     for (int i = 0; i < R; ++i) {
       const uint32_t wi = p_pos(rr[bw[i] & 63u], bw[i] >> 12) >> 5;
-      lo[i] = p_load_word(pr.data, pr.nbytes, a + 4ll * wi);
-      hi[i] = p_load_word(pr.data, pr.nbytes, a + 4ll * wi + 4);
+      lo[i] = p_load_word(data, nbytes, a + 4ll * wi);
+      hi[i] = p_load_word(data, nbytes, a + 4ll * wi + 4);
     }
   }
 }
 // issues the window loads of the frame in `slot`, one frame ahead as load_row_q
-template <int R>
+template <int R, bool STREAM = false>
 __device__ __forceinline__ void load_row_p(const PackedRows& pr, const uint32_t* rec, int slot, const uint32_t (&bw)[R],
-                                           bool has1, PGran (&g)[R]) {
+                                           bool has1, PGran (&g)[R], const ConcealState* cs = nullptr) {
   uint32_t lo[R], hi[R];
-  load_sig_p<R>(pr, rec, 2 * slot, bw, lo, hi);
+  load_sig_p<R, STREAM>(pr, rec, 2 * slot, bw, lo, hi, cs);
 #pragma unroll
   for (int i = 0; i < R; ++i) {
     g[i].lo0 = lo[i];
@@ -209,7 +268,7 @@ __device__ __forceinline__ void load_row_p(const PackedRows& pr, const uint32_t*
     g[i].lo1 = g[i].hi1 = 0u;
   }
   if (has1) {
-    load_sig_p<R>(pr, rec, 2 * slot + 1, bw, lo, hi);
+    load_sig_p<R, STREAM>(pr, rec, 2 * slot + 1, bw, lo, hi, cs);
 #pragma unroll
     for (int i = 0; i < R; ++i) {
       g[i].lo1 = lo[i];
@@ -244,6 +303,59 @@ __device__ __forceinline__ void extract_row_p(const uint32_t* rec, int slot, con
     if (has1) extract_sig_p(rr0 + P_M, bw[i], g[i].lo1, g[i].hi1, c1, f1);
     out[i].code = s4{(short)(c0 & 0xffffu), (short)(c1 & 0xffffu), (short)(c0 >> 16), (short)(c1 >> 16)};
     out[i].sfw = f0 | (f1 << 8);
+  }
+}
+
+// (streams) The concealment state a chunk of Kp frames leaves for the wave's two signals, written into the other half of the
+// double buffer by the wave that owns their last strip.  Lane k of a signal's half wave looks at frame Kp-1 - k, whatever
+// max_age is: the first one that arrived is the new carried row and k the new gap; a frame before the chunk is there where the
+// old carried row sits, which is then kept; none in 32 frames: gap 32, and the row is left unspecified.
+// the P_CARRY_WORDS words at src (4-byte aligned, all readable) to dst: every load of a lane in flight before its first store
+__device__ __forceinline__ void copy_carried_row(uint32_t* dst, const uint32_t* src, int lane) {
+  constexpr int PER = (P_CARRY_WORDS + 63) / 64;
+  uint32_t v[PER];
+#pragma unroll
+  for (int i = 0; i < PER; ++i) v[i] = (64 * i + lane < P_CARRY_WORDS) ? src[64 * i + lane] : 0u;
+#pragma unroll
+  for (int i = 0; i < PER; ++i)
+    if (64 * i + lane < P_CARRY_WORDS) dst[64 * i + lane] = v[i];
+}
+
+__device__ __forceinline__ void carry_state_p(const PackedRows& pr, const ConcealRows& cl, const ConcealState& cs, long long b0,
+                                              long long b1, int c0, int c1, int Kp, int C, bool has1, int lane) {
+  const int sig = lane >> 5, k = lane & 31;
+  const bool on = sig == 0 || has1;
+  const long long b = sig ? b1 : b0;
+  const int c = sig ? c1 : c0;
+  const int f = Kp - 1 - k;
+  const int gap = (on && !cs.stale) ? (int)cs.gap[(size_t)b * (size_t)C + (size_t)c] : P_NO_SOURCE;
+  const bool there = on && (f >= 0 ? cl.lost[((size_t)b * (size_t)Kp + (size_t)f) * (size_t)C + (size_t)c] == 0 : f == -1 - gap);
+  const uint64_t m = __builtin_amdgcn_ballot_w64(there);
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    if (s && !has1) break;
+    const uint32_t mh = s ? (uint32_t)(m >> 32) : (uint32_t)m;   // (wave-uniform: the branches below are scalar)
+    const long long bs = s ? b1 : b0;
+    const int csg = s ? c1 : c0;
+    const size_t sg = (size_t)bs * (size_t)C + (size_t)csg;
+    const int ngap = mh ? __builtin_ctz(mh) : P_NO_SOURCE;
+    if (lane == 0) cs.gap_out[sg] = (uint8_t)ngap;
+    if (mh == 0u) continue;
+    uint32_t* dst = reinterpret_cast<uint32_t*>(cs.row_out + sg * (size_t)P_CARRY_STRIDE);
+    const int fs = Kp - 1 - ngap;
+    if (fs >= 0) {
+      const int64_t own = pr.index[((size_t)bs * (size_t)Kp + (size_t)fs) * (size_t)C + (size_t)csg];
+      int64_t a = (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)own) |
+                            ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)own >> 32)) << 32));
+      a = a > pr.nbytes ? pr.nbytes : (a < -(1ll << 40) ? -(1ll << 40) : a);
+      if (a >= 0 && (a & 3) == 0 && a + 4ll * P_CARRY_WORDS <= pr.nbytes) {   // the usual row: plain loads
+        copy_carried_row(dst, reinterpret_cast<const uint32_t*>(pr.data + a), lane);
+      } else {
+        for (int w = lane; w < P_CARRY_WORDS; w += 64) dst[w] = p_load_word(pr.data, pr.nbytes, a + 4ll * w);
+      }
+    } else {
+      copy_carried_row(dst, reinterpret_cast<const uint32_t*>(cs.row + sg * (size_t)P_CARRY_STRIDE), lane);
+    }
   }
 }
 

@@ -192,6 +192,12 @@ struct ac_stream {
   double* d_prev64 = nullptr;      // [B, N, C]
   double* d_tail64 = nullptr;      // [B, C, N/2]
   double* d_tail64_tmp = nullptr;
+  // concealment across chunks (AC_PACKED | AC_CONCEAL), allocated by the first concealing call: one
+  // buffer holding the carried rows twice, then the gaps twice; half conceal_cur is current.  conceal_stale: the last call that
+  // advanced d_tail did not conceal (or the stream is new or was reset), so the next concealing call reads every gap as 32
+  uint8_t* d_conceal = nullptr;
+  int conceal_cur = 0;
+  bool conceal_stale = true;
 };
 
 // ---- kernel launchers (each returns an AC_* status) -----------------------------------------
@@ -321,6 +327,15 @@ int launch_inv_fast_packed(const ac_mdct_plan* p, const ac_psy_plan* psy, const 
 int launch_inv_fast_packed_conceal(const ac_mdct_plan* p, const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes,
                                    const int64_t* index, const uint8_t* lost, int max_age, void* x, bool pcm16, int B, int Kp,
                                    int C, hipStream_t s);
+// ... as one chunk of k frames of a stream (k_inv_fast_pls, ac_fast_inv_pls.hip): tails as launch_inv_fast_packed takes them,
+// and the concealment state -- gap [B,C] and carried rows [B,C] at conceal_state_row_bytes(1, 1) bytes each -- read from
+// gap_in / row_in (stale: every gap reads as 32, nothing is read) and written to gap_out / row_out, other buffers
+bool fast_inv_packed_conceal_stream_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);
+size_t conceal_state_row_bytes(int B, int C);
+int launch_inv_fast_packed_conceal_stream(const ac_mdct_plan* p, const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes,
+                                          const int64_t* index, const uint8_t* lost, int max_age, void* x, bool pcm16,
+                                          const float* tail_in, float* tail_out, const uint8_t* gap_in, const uint8_t* row_in,
+                                          uint8_t* gap_out, uint8_t* row_out, bool stale, int B, int k, int C, hipStream_t s);
 int launch_psy_fast(const ac_psy_plan* p, const float* X, const float* t_in, float* t_out, float* thr, float drown,
                     int B, int F, int C, hipStream_t s, int iof = 0);
 // streaming duplex: the analysis of a chunk of k_fwd blocks (psy: with the fused masking model) and the synthesis of a

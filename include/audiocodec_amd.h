@@ -52,7 +52,8 @@ extern "C" {
                           * ac_psy_plan_row_budget; packed rows in a stream: AC_PACKED, ac_stream_packed_in,
                           * ac_stream_packed_launches; 16-bit PCM into the quantising encodes: AC_IN_PCM16,
                           * ac_*_launches_pcm16; rows to a lower budget without decoding: ac_quantized_rows, AC_IN_PACKED,
-                          * ac_transrate_launches); additions only, so the number stays.
+                          * ac_transrate_launches; lost rows concealed in a stream: AC_CONCEAL,
+                          * ac_stream_packed_lost_in); additions only, so the number stays.
                           * 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
                           * with a 5-smooth half up to 8192, float32); masking model for general band layouts up to 4096 bins.
                           * 0.1.7: only the ac_* entry points are exported; ac_stream_settle (home buffers for the streaming state);
@@ -621,7 +622,7 @@ AC_API int ac_stream_inverse_typed(ac_stream* s, const void* X_chunk, void* x, i
  * ac_stream_packed_launches(s, psy, decode): library launches of a chunk on this stream.  decode = 0: 1 where
  *   ac_encode_packed_launches is 1 for the stream's channels and the kernel instance with streaming state passed its register
  *   gate (stereo with the f32 spreading product did not), else ac_encode_launches + 2.  decode != 0: 1 where
- *   ac_decode_packed_launches is 1, else 3.  AC_ENCODE_PACKED_NOFUSE=1 / AC_DECODE_PACKED_NOFUSE=1 apply as they do one-shot
+ *   ac_decode_packed_launches is 1, else 3 (decode = 2: of the concealing decode, below).  AC_ENCODE_PACKED_NOFUSE=1 / AC_DECODE_PACKED_NOFUSE=1 apply as they do one-shot
  *   (read per call).  0 for NULL or mismatched arguments, or (decode = 0) a plan without a row budget.
  * 16-bit PCM into the encoder: ac_stream_encode_typed(..., dtype = AC_PACKED | AC_IN_PCM16 (48), ...) takes x_chunk as int16
  *   [B,k*N,C], x = pcm / 32768: the rows, and the float32 state it leaves, are those of the AC_PACKED call on that float32
@@ -635,6 +636,29 @@ typedef struct ac_stream_packed_in {
   const ac_psy_plan* psy;   /* the band layout of the rows */
   int32_t pcm16;            /* 0: x is float32 [B,k*N,C]; 1: int16 */
 } ac_stream_packed_in;
+/* Lost rows concealed in a stream (extension; DESIGN.md section 8f, "Streams"): AC_CONCEAL is a flag beside AC_PACKED for
+ * ac_stream_inverse_typed and nothing else.
+ *   ac_stream_inverse_typed(s, X_chunk, x, AC_PACKED | AC_CONCEAL (144), k, stream): X_chunk addresses one
+ *     ac_stream_packed_lost_in.  lost uint8 [B,k,C] (nonzero: the row did not arrive), max_age in [0, AC_CONCEAL_MAX_AGE].  The
+ *     stream carries, per clip and channel, the last row that arrived (its first 2152 bytes, bytes outside data as 0) and the
+ *     gap g in [0, 32]: the frames since it at the end of the previous chunk, 32 = none within reach.  Row (b, f, c) is read
+ *     from index[b, f-a, c] for the smallest a in [0, min(max_age, f)] with lost[b, f-a, c] == 0; else from the carried row,
+ *     with age g + f + 1, where g <= 31 and that age <= max_age; else it is silence.  Scale factors fade as ac_conceal fades
+ *     them.  So the chunk calls of any split give the blocks ac_decode_quantized with an ac_conceal gives for the whole signal,
+ *     bit for bit.  Afterwards: the last row of the chunk that arrived is carried with g = min(32, k-1 - its frame); none
+ *     arrived: g = min(32, g + k).  AC_EINVAL for max_age outside its range, a NULL lost, an unaligned pointer or pcm16 not 0 /
+ *     1.  k == 0 is AC_OK and leaves the state.  The state is allocated by the first such call, zeroed on its stream, and freed
+ *     with the stream; ac_stream_reset resets it.  Every other call that advances the synthesis state (ac_stream_inverse,
+ *     ac_stream_inverse_typed without AC_CONCEAL, ac_stream_run) leaves no source: the next concealing call reads g = 32.
+ *   ONE launch where ac_stream_packed_launches(s, psy, 2) returns 1 (where decode = 1 does); AC_EUNSUPPORTED elsewhere, with all
+ *   state untouched, and the query returns 3: ac_unpack, ac_dequantize, ac_stream_inverse, with the fade and the carried row
+ *   kept by the caller. */
+enum { AC_CONCEAL = 128 };   /* ac_stream_inverse_typed, beside AC_PACKED: rows marked in lost are concealed */
+typedef struct ac_stream_packed_lost_in {
+  ac_stream_packed_in in;
+  const uint8_t* lost;      /* [B,k,C]: nonzero = the row did not arrive */
+  int32_t max_age;          /* 0 .. AC_CONCEAL_MAX_AGE */
+} ac_stream_packed_lost_in;
 AC_API int ac_stream_packed_launches(const ac_stream* s, const ac_psy_plan* psy, int decode);
 AC_API int ac_stream_packed_launches_pcm16(const ac_stream* s, const ac_psy_plan* psy);
 AC_API int ac_amplitude_to_db_typed(const void* a, void* out, size_t n, int norm, int dtype, void* stream);

@@ -16,10 +16,12 @@ the one launch on int16 (k_fwd_fast_qp16 / qps16), the conversion to(float32) / 
 caller did before), and the float32 one launch on a resident float32 tensor; compared byte for byte, then alternating
 (profiles/pack/pack_bench_pcm16.txt).
 python tools/pack_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7] [--round-steps 30]
-                           [--row-bits 1365] [--only-rows] [--stream] [--pcm16] [--transrate [--targets 1365 682]] [--conceal]
+                           [--row-bits 1365] [--only-rows] [--stream] [--pcm16] [--transrate [--targets 1365 682]] [--conceal] [--conceal-stream]
 --transrate: rows at 2730 bits transrated to each of --targets (transrate_rows(); profiles/pack/pack_bench_transrate.txt).
 --conceal: decode_packed with lost rows concealed -- none lost, and 1 % lost at random -- against decode_packed without `lost`
-(conceal_rows(); profiles/pack/pack_bench_conceal.txt)."""
+(conceal_rows(); profiles/pack/pack_bench_conceal.txt).
+--conceal-stream: the same chunk by chunk on a StreamingMDCT, the last good row carried across chunks, against
+decode_packed_chunk without `lost` (conceal_stream_rows(); profiles/pack/pack_bench_conceal_stream.txt)."""
 import argparse
 import ctypes
 import os
@@ -320,8 +322,79 @@ def conceal_rows(a):
         print("  (b) / (a) = %.3f   (c) / (a) = %.3f   (c) / (d) = %.3f" % (med[1] / med[0], med[2] / med[0], med[2] / med[3]))
 
 
+def conceal_stream_rows(a):
+    """Concealment of lost rows in a stream ("Streams") on the rows of encode_packed_rows_chunk at
+    --row-bits, per workload: (a) decode_packed_chunk without `lost`, the yardstick (k_inv_fast_p; the only form an older
+    commit has, so the same script times it there); (b) with `lost` all false; (c) with 1 % of the rows lost at random,
+    max_age 8 -- both the one launch of k_inv_fast_pls; (d) the composition of (c) (AC_DECODE_PACKED_NOFUSE=1, read per call).
+    Compared bit for bit first, then alternating, --rounds rounds of --round-steps passes over the workload's chunks, float32
+    and 16-bit PCM out.  Two workloads: one stereo clip in chunks of 256 blocks and --clips x --blocks as one chunk."""
+    import inspect
+    N, C = a.filters, a.channels
+    cbr = audiocodec_amd.AudioCodec(48000, N).with_row_budget(a.row_bits)
+    rb = (a.row_bits + 31) // 32 * 4
+    new = "lost" in inspect.signature(audiocodec_amd.codec.StreamingMDCT.decode_packed_chunk).parameters
+    for name, B, k, n in (("one clip, chunks of 256 blocks", 1, 256, 8), ("%d clips x %d blocks, one chunk" % (a.clips, a.blocks), a.clips, a.blocks, 1)):
+        g = torch.Generator("cuda").manual_seed(1)
+        enc, dec, comp = cbr.stream(B, C), cbr.stream(B, C), cbr.stream(B, C)
+        packed = []
+        for _ in range(n):
+            packed.append(enc.encode_packed_rows_chunk(torch.rand((B, k * N, C), device="cuda", generator=g) * 2 - 1)[0])
+        index = (torch.arange(B * k * C, dtype=torch.int64, device="cuda") * rb).view(B, k, C)
+        none = torch.zeros(index.shape, dtype=torch.uint8, device="cuda")
+        some = [(torch.rand(index.shape, device="cuda", generator=g) < 0.01).to(torch.uint8) for _ in range(n)]
+
+        def composition(pcm16):
+            os.environ["AC_DECODE_PACKED_NOFUSE"] = "1"   # (read per call)
+            try:
+                return [comp.decode_packed_chunk(d, index, pcm16=pcm16, lost=s, max_age=8) for d, s in zip(packed, some)]
+            finally:
+                del os.environ["AC_DECODE_PACKED_NOFUSE"]
+
+        launches = ""
+        if new:
+            v = torch.int16
+            for pcm16 in (False, True):
+                dec.reset()
+                plain = [dec.decode_packed_chunk(d, index, pcm16=pcm16) for d in packed]
+                dec.reset()
+                for d, w in zip(packed, plain):
+                    assert torch.equal(dec.decode_packed_chunk(d, index, pcm16=pcm16, lost=none).view(v), w.view(v)), "none lost != the plain chunk"
+                dec.reset()
+                comp.reset()
+                one = [dec.decode_packed_chunk(d, index, pcm16=pcm16, lost=s, max_age=8) for d, s in zip(packed, some)]
+                for o, t in zip(one, composition(pcm16)):
+                    assert o.dtype == t.dtype and torch.equal(o.view(v), t.view(v)), "the two forms differ"
+                del plain, one
+            launches = ("  launches: %d; none lost equals the plain chunk, the one launch and the composition agree bit for bit "
+                        "(float32 and 16-bit PCM)" % dec.packed_chunk_launches(decode=True, conceal=True))
+        print("conceal stream: %s  (B=%d k=%d N=%d C=%d, %d chunks per pass, %d bits per row, %.2f %% of the rows lost, max_age 8)  %s%s"
+              % (name, B, k, N, C, n, a.row_bits, 100.0 * float(torch.stack(some).float().mean()), torch.cuda.get_device_name(), launches))
+        for pcm16 in (False, True):
+            forms = [("(a) decode_packed_chunk", lambda: [dec.decode_packed_chunk(d, index, pcm16=pcm16) for d in packed])]
+            if new:
+                forms += [("(b) lost all false, one launch", lambda: [dec.decode_packed_chunk(d, index, pcm16=pcm16, lost=none) for d in packed]),
+                          ("(c) 1 % lost, one launch",
+                           lambda: [dec.decode_packed_chunk(d, index, pcm16=pcm16, lost=s, max_age=8) for d, s in zip(packed, some)]),
+                          ("(d) 1 % lost, composition", lambda: composition(pcm16))]
+            runs = dict((f, []) for f, _ in forms)
+            for _ in range(a.rounds):
+                for f, fn in forms:
+                    runs[f].append(timed(fn, a.round_steps, 1) / n * 1e3)
+            med = []
+            print("  %s out:" % ("16-bit PCM" if pcm16 else "float32"))
+            for f, _ in forms:
+                v = sorted(runs[f])
+                med.append(v[len(v) // 2])
+                print("    %-32s median %9.1f us per chunk  min %9.1f  max %9.1f  (%d alternating rounds of %d)"
+                      % (f, med[-1], v[0], v[-1], len(v), a.round_steps))
+            if new:
+                print("    (b) / (a) = %.3f   (c) / (a) = %.3f   (c) / (d) = %.3f" % (med[1] / med[0], med[2] / med[0], med[2] / med[3]))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--conceal-stream", action="store_true", help="only decode_packed_chunk with lost rows concealed, against without")
     ap.add_argument("--conceal", action="store_true", help="only decode_packed with lost rows concealed, against without")
     ap.add_argument("--transrate", action="store_true", help="only transrating: rows at --row-bits (default 2730 here) to --targets")
     ap.add_argument("--targets", type=int, nargs="+", default=[1365, 682], help="the target budgets of --transrate")
@@ -341,6 +414,8 @@ def main():
     B, K, N, C = a.clips, a.blocks, a.filters, a.channels
     if a.conceal:
         return conceal_rows(a)
+    if a.conceal_stream:
+        return conceal_stream_rows(a)
     if a.transrate:
         if a.row_bits == 1365:
             a.row_bits = 2730   # the source rows: 128 kbit/s
