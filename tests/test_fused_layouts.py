@@ -38,6 +38,7 @@ from test_stream_packed import _decode_chunks, _encode_chunks
 
 gpu = pytest.mark.gpu
 BY_ID = {l[0]: l for l in LAYOUTS}
+BY_ID["48000"] = ("48000", 48000, 0.6)                       # no case of this file: test_conceal_layouts.py takes _ref there
 SIGNALS = ("noise", "tonal")
 CHUNKS = (2, 1, 2)
 FORMS = [(spreading, pcm16) for spreading in (None, "f32") for pcm16 in (False, True)]
@@ -382,11 +383,17 @@ def test_chunks(layout, signal, C, monkeypatch):
 
 # ---- 5. decode: k_inv_fast_p ------------------------------------------------------------------------------------------------------
 def _hold_to_the_oracle(codec, off, data, index, pcm, what):
-    """float32 PCM of decode_packed against MDCTOracle(float64).inverse_transform(np_dequantize(the rows' codes)).  The bar is
-    the existing decode tests' for signals within full scale, one LSB of 16-bit PCM; the synthesis is linear, so for a block
-    whose reference peaks above 1 (the 3e12 sample of ``noise``) the bar scales with that peak.  Blocks under a frame with a NaN
-    band (a frame covers two blocks) are left out."""
+    """float32 PCM of decode_packed against MDCTOracle(float64).inverse_transform(np_dequantize(the rows' codes)): the rows as
+    psy.unpack reads them, held by _hold_codes_to_the_oracle."""
     codes, sf = (v.cpu().numpy() for v in codec.psy.unpack(data, index))
+    return _hold_codes_to_the_oracle(codes, sf, off, pcm, what)
+
+
+def _hold_codes_to_the_oracle(codes, sf, off, pcm, what):
+    """float32 PCM decoded from codes int16 [B, F, N0, C] and sf int8 [B, F, M0, C] (numpy) against
+    MDCTOracle(float64).inverse_transform(np_dequantize(codes, sf)).  The bar is the existing decode tests' for signals within
+    full scale, one LSB of 16-bit PCM; the synthesis is linear, so for a block whose reference peaks above 1 (the 3e12 sample of
+    ``noise``) the bar scales with that peak.  Blocks under a frame with a NaN band (a frame covers two blocks) are left out."""
     Xh = np_dequantize(codes, sf, off).astype(np.float64)
     bad = np.isnan(Xh).any(axis=2)                               # [B, F, C]
     ref = MDCTOracle(N0, "vorbis", np.float64).inverse_transform(np.where(np.isnan(Xh), 0.0, Xh))
