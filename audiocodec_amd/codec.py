@@ -969,7 +969,7 @@ class StreamingMDCT:
         ``self._conceal``.  Nothing here waits for the device."""
         B, k, C = index.shape
         dev = data.device
-        if self._lib.ac_stream_packed_launches(self._handle, psy, 2) in (1, 2):
+        if self._lib.ac_stream_packed_launches(self._handle, psy, 2) == 1:
             self._conceal = None   # (the state lives in the library from here on)
             rows = _lib.StreamPackedLostIn(
                 _lib.StreamPackedIn(_lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr()), psy.value,

@@ -114,7 +114,7 @@ static void launch_fwd_R(const FwdArgs& a, bool psy, int spread, int C, unsigned
     }
   }
   if constexpr (IOF == 2) {
-    // bfloat16 tensors: stereo and mono kernels (other channel counts are served by the LDS-FFT tier, see ac_api.hip)
+    // bfloat16 tensors: stereo and mono kernels (other channel counts are served by the LDS-FFT tier, see ac_api_quant.hip)
     if (psy) {
       const dim3 blk(AC_WAVES_PSY * 64);
       if (C == 2) hipLaunchKernelGGL((k_fwd_fast<R, 0, true, AC_WAVES_PSY, 2>), dim3(grid), blk, 0, s, a);
@@ -134,7 +134,7 @@ static void launch_fwd_R(const FwdArgs& a, bool psy, int spread, int C, unsigned
     else if (C == 2 && spread == 2) hipLaunchKernelGGL((k_fwd_fast<R, 0, true, AC_WAVES_PSY, IOF, 2>), dim3(grid), blk, 0, s, a);
     else if (C == 2) hipLaunchKernelGGL((k_fwd_fast<R, 0, true, AC_WAVES_PSY, IOF>), dim3(grid), blk, 0, s, a);
     else if (C == 1) {
-      // (R = 16: the caller runs transform and masking model as two launches, see encode_fused in ac_api.hip)
+      // (R = 16: the caller runs transform and masking model as two launches, see encode_fused in ac_api_encode.hip)
       if constexpr (R == 8) {
         if (spread == 1) hipLaunchKernelGGL((k_fwd_fast<R, 2, true, AC_WAVES_PSY, IOF, 1>), dim3(grid), blk, 0, s, a);
         else if (spread == 2) hipLaunchKernelGGL((k_fwd_fast<R, 2, true, AC_WAVES_PSY, IOF, 2>), dim3(grid), blk, 0, s, a);

@@ -342,7 +342,7 @@ __global__ __launch_bounds__(NW * 64, (wpe<R, CMODE, PSY, SPREAD>())) void k_fwd
 int prep_fwd_fast(const ac_mdct_plan* p, const ac_psy_plan* psy, const void* x, int iof, float* X, float* t,
                   float* thr, float drown, const float* prev_block, int B, int Kin, int F, int C, float* state_out,
                   float* noisy, float* dbn, uint64_t seed, FwdArgs& a, unsigned& grid) {
-  // combinations no kernel is instantiated for (ac_api.hip routes them elsewhere; refuse rather than launch nothing)
+  // combinations no kernel is instantiated for (ac_api_encode.hip routes them elsewhere; refuse rather than launch nothing)
   if ((iof == 2 && C > 2) || (psy && p->N == Geo<16>::FN && (C == 1 || (iof == 1 && C > 2)))) {
     set_error("internal: no wave-level analysis kernel for filters_n = %d, %d channels, io format %d%s", p->N, C, iof,
               psy ? ", fused masking model" : "");

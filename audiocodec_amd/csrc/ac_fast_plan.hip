@@ -174,9 +174,7 @@ int fast_mdct_plan_init(ac_mdct_plan* p) {
   }
   p->fold4 = fold4 ? 1 : 0;
   p->fast_bytes = t.size() * sizeof(float);
-  AC_HIP_CHECK(hipMalloc((void**)&p->d_fast, p->fast_bytes));
-  AC_HIP_CHECK(hipMemcpy(p->d_fast, t.data(), p->fast_bytes, hipMemcpyHostToDevice));
-  return AC_OK;
+  return p->tables.upload(t, &p->d_fast);
 }
 
 // The wave-level epilogue needs: N = 128 R (1024 or 2048), 64 Bark bands (lane = band), every band a contiguous bin
@@ -310,9 +308,7 @@ int fast_psy_plan_init(ac_psy_plan* p) {
     return AC_EUNSUPPORTED;
   }
   p->fast_bytes = w.size() * sizeof(uint32_t);
-  AC_HIP_CHECK(hipMalloc((void**)&p->d_fast, p->fast_bytes));
-  AC_HIP_CHECK(hipMemcpy(p->d_fast, w.data(), p->fast_bytes, hipMemcpyHostToDevice));
-  return AC_OK;
+  return p->tables.upload(w, reinterpret_cast<uint32_t**>(&p->d_fast));   // (words of mixed type behind a float pointer)
 }
 
 int grid_for(long long ntasks, int nw, unsigned* grid) {

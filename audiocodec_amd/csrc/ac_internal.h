@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <string>
+#include <vector>
 
 #include "../../include/audiocodec_amd.h"
 #include "../../include/audiocodec_amd_testing.h"
@@ -60,6 +61,27 @@ struct DeviceGuard {
 };
 
 extern int g_force_generic;
+
+// The device memory of a plan.  Every table goes up through upload(), which records what it allocates; release() frees all
+// of it, so a plan's destroy needs no list of its own.
+struct DeviceTables {
+  std::vector<void*> owned;
+  DeviceTables() = default;
+  DeviceTables(const DeviceTables&) = delete;   // (one owner: a copied plan would free its tables twice)
+  template <typename T>
+  int upload(const std::vector<T>& h, T** d) {
+    *d = nullptr;
+    const size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
+    AC_HIP_CHECK(hipMalloc((void**)d, bytes));
+    owned.push_back(*d);
+    if (!h.empty()) AC_HIP_CHECK(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    return AC_OK;
+  }
+  void release() {
+    for (void* d : owned) (void)hipFree(d);
+    owned.clear();
+  }
+};
 
 // ---- element-wise pieces shared by the stand-alone utilities (ac_generic.hip) and the fused encode epilogue (ac_fast_psy_dev.h):
 // one definition, so that fused and un-fused results agree bit for bit
@@ -117,7 +139,8 @@ struct RunsLayout {
 
 struct ac_mdct_plan {
   int N = 0, window = 0, device = 0;
-  int cus = 0;                 // compute units of the device (sizes the persistent launches)
+  ac::DeviceTables tables;     // owns every d_* below
+  int cus = 0;                // compute units of the device (sizes the persistent launches)
   int fast = 0;                // 1: wave-level FFT kernels available for this N
   int pre = AC_F64;            // arithmetic type the constants were computed in (the reference's precompute_dtype)
   int fold4 = 0;               // 1: the wave-level kernels run their FOLD4 form (fold blocks that are not rotations)
@@ -135,6 +158,7 @@ struct ac_mdct_plan {
 
 struct ac_psy_plan {
   int N = 0, M = 0, device = 0;
+  ac::DeviceTables tables;     // owns every d_* below
   double sample_rate = 0, alpha = 0;
   int fast = 0;                // 1: the fused wave-level epilogue supports this (N, M, table shape)
   int pre = AC_F64;            // arithmetic type the constants were computed in (the reference's precompute_dtype)

@@ -682,9 +682,7 @@ int mid_psy_plan_init(ac_psy_plan* p) {
   p->mid_off_band = L.off_band;
   p->mid_off_wbe = L.off_wbe;
   p->mid_off_wi = L.off_wi;
-  AC_HIP_CHECK(hipMalloc((void**)&p->d_mid, w.size() * sizeof(uint32_t)));
-  AC_HIP_CHECK(hipMemcpy(p->d_mid, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  return AC_OK;
+  return p->tables.upload(w, &p->d_mid);
 }
 
 
@@ -873,10 +871,9 @@ runs::RunsParams runs_params(const ac_psy_plan* p, float drown, bool idx_in_lds)
 int runs_psy_plan_init(ac_psy_plan* p) {
   std::vector<uint32_t> w;
   if (!build_runs(p->host, &w, &p->runs_lay)) return AC_EUNSUPPORTED;   // (not an error: the plan keeps the band walk)
-  AC_HIP_CHECK(hipMalloc((void**)&p->d_runs, w.size() * sizeof(uint32_t)));
-  AC_HIP_CHECK(hipMemcpy(p->d_runs, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  p->runs = 1;
-  return AC_OK;
+  const int st = p->tables.upload(w, &p->d_runs);
+  if (!st) p->runs = 1;
+  return st;
 }
 
 // t_out != null: tonality (from X); thr != null: threshold (from t_out when given, else from t_in)

@@ -335,7 +335,7 @@ static __global__ __launch_bounds__((NTC > kThreads ? NTC : kThreads), 2) void k
 // the fused encode (k_enc_wave_v): sizes with an instance whose frame region holds a slot of the model -- filters_n 108 ...
 // 4096 (the masking model's range ends there; below 108 a frame's LDS is smaller than the model's smallest slot)
 // (128, 256 and 512 have none: mono and stereo float32 tensors of those sizes run the several-frames-per-wave kernels under
-// every window -- wave_level() in ac_api.hip -- so this launch was never reached there)
+// every window -- wave_level() in ac_api_encode.hip -- so this launch was never reached there)
 static inline constexpr bool enc_instance(int N) { return N >= 108 && N <= 4096 && N != 128 && N != 256 && N != 512; }
 static bool enc_size(int N) { return enc_instance(N) && lds_wave_ct_size(N); }
 // ... and where the one launch measured faster than transform + masking kernel on an MI355X (ratio <= 0.98 over B = 256 stereo

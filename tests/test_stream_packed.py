@@ -469,7 +469,7 @@ def test_composition_elsewhere(N, M, C, R):
     assert _same(got, want), _where(got, want)
     # ... which is the one-shot call's 16-bit PCM wherever that runs the float32 synthesis' arithmetic.  With three channels at
     # filters_n = 1024 it does not: float32 tensors take the channel-pair kernels of the LDS-FFT tier, 16-bit PCM the wave-level
-    # strided ones (wave_level() in ac_api.hip), and the two round differently in a few samples.
+    # strided ones (wave_level() in ac_api_encode.hip), and the two round differently in a few samples.
     if C <= 2:
         ref16 = cbr.decode_packed(data, index, True)[:, :K0 * N]
         assert _same(got, ref16), _where(got, ref16)
