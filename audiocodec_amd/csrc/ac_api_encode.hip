@@ -58,7 +58,7 @@ static int mdct_forward(const ac_mdct_plan* p, const void* x, bool pcm16, float*
     if (lds_fft_serves_pcm16(p, C)) return launch_fwd_lds_pcm16(p, static_cast<const int16_t*>(x), X, B, K, C, s);
     return refuse_pcm16();
   }
-  return launch_fwd_generic(p, static_cast<const float*>(x), X, nullptr, B, K, K + 1, C, s);
+  return launch_fwd_typed(p, x, X, nullptr, AC_F32, B, K, K + 1, C, s);
 }
 
 int mdct_inverse(const ac_mdct_plan* p, const float* X, void* x, bool pcm16, int B, int Kp, int C, void* stream) {
@@ -75,7 +75,7 @@ int mdct_inverse(const ac_mdct_plan* p, const float* X, void* x, bool pcm16, int
     if (lds_fft_serves_pcm16(p, C)) return launch_inv_lds_pcm16(p, X, static_cast<int16_t*>(x), B, Kp, C, s);
     return refuse_pcm16();
   }
-  return launch_inv_generic(p, X, static_cast<float*>(x), nullptr, nullptr, B, Kp, Kp + 1, C, s);
+  return launch_inv_typed(p, X, x, nullptr, nullptr, AC_F32, B, Kp, Kp + 1, C, s);
 }
 
 // Whether AC_EMIT_CODES is one launch (k_fwd_fast_q); AC_ENCODE_QUANT_NOFUSE=1 sends every configuration down the two
@@ -125,7 +125,7 @@ int ac_tonality(const ac_psy_plan* p, const float* X, float* t, int B, int F, in
   hipStream_t s = (hipStream_t)stream;
   if (psy_fast_serves(p, C)) return launch_psy_fast(p, X, nullptr, t, nullptr, 0.f, B, F, C, s);
   if (psy_mid_serves(p, C)) return launch_psy_mid(p, X, nullptr, t, nullptr, 0.f, B, F, C, s);
-  return launch_tonality_generic(p, X, t, B, F, C, s);
+  return launch_tonality_typed(p, X, t, AC_F32, B, F, C, s);
 }
 
 int ac_mask_threshold(const ac_psy_plan* p, const float* X, const float* t, float drown, float* thr, int B, int F,
@@ -140,7 +140,7 @@ int ac_mask_threshold(const ac_psy_plan* p, const float* X, const float* t, floa
   hipStream_t s = (hipStream_t)stream;
   if (psy_fast_serves(p, C)) return launch_psy_fast(p, X, t, nullptr, thr, drown, B, F, C, s);
   if (psy_mid_serves(p, C)) return launch_psy_mid(p, X, t, nullptr, thr, drown, B, F, C, s);
-  return launch_threshold_generic(p, X, t, drown, thr, B, F, C, s);
+  return launch_threshold_typed(p, X, t, drown, thr, AC_F32, B, F, C, s);
 }
 
 int ac_tonality_backward(const ac_psy_plan* p, const float* X, const float* grad_t, float* grad_X, int accumulate, int B,
@@ -155,7 +155,7 @@ int ac_tonality_backward(const ac_psy_plan* p, const float* X, const float* grad
   if (p->fast && !g_force_generic)
     return launch_psy_bwd_fast(p, X, nullptr, 0.f, nullptr, grad_t, grad_X, nullptr, accumulate, B, F, C,
                                (hipStream_t)stream);
-  return launch_tonality_bwd_generic(p, X, grad_t, grad_X, accumulate, B, F, C, (hipStream_t)stream);
+  return launch_tonality_bwd_typed(p, X, grad_t, grad_X, accumulate, AC_F32, B, F, C, (hipStream_t)stream);
 }
 
 int ac_mask_threshold_backward(const ac_psy_plan* p, const float* X, const float* t, float drown, const float* grad_thr,
@@ -170,7 +170,7 @@ int ac_mask_threshold_backward(const ac_psy_plan* p, const float* X, const float
   DeviceGuard guard(p->device);
   if (p->fast && !g_force_generic)
     return launch_psy_bwd_fast(p, X, t, drown, grad_thr, nullptr, grad_X, grad_t, 0, B, F, C, (hipStream_t)stream);
-  return launch_threshold_bwd_generic(p, X, t, drown, grad_thr, grad_X, grad_t, B, F, C, (hipStream_t)stream);
+  return launch_threshold_bwd_typed(p, X, t, drown, grad_thr, grad_X, grad_t, AC_F32, B, F, C, (hipStream_t)stream);
 }
 
 static int encode_fused(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const void* x, bool pcm16, float* X, float* t,

@@ -48,7 +48,7 @@ extern "C" {
 
 int ac_amplitude_to_db(const float* a, float* out, size_t n, int norm, void* stream) {
   AC_REQUIRE(n == 0 || (a != nullptr && out != nullptr), "NULL tensor pointer");
-  return launch_db(a, out, n, norm, (hipStream_t)stream);
+  return launch_db_typed(a, out, n, norm, AC_F32, (hipStream_t)stream);
 }
 
 int ac_amplitude_to_db_backward(const float* a, const float* grad_out, float* grad_a, size_t n, int norm, void* stream) {
@@ -58,7 +58,7 @@ int ac_amplitude_to_db_backward(const float* a, const float* grad_out, float* gr
 
 int ac_add_noise(const float* X, const float* thr, float* out, size_t n, uint64_t seed, void* stream) {
   AC_REQUIRE(n == 0 || (thr != nullptr && out != nullptr), "NULL tensor pointer");   // X == NULL: zeros
-  return launch_add_noise(X, thr, out, n, seed, (hipStream_t)stream);
+  return launch_add_noise_typed(X, thr, out, n, seed, AC_F32, (hipStream_t)stream);
 }
 
 // ---- quantiser (ac_quant.hip) -----------------------------------------------
@@ -263,11 +263,9 @@ int ac_mdct_forward_typed(const ac_mdct_plan* p, const void* x, void* X, int dty
   AC_REQUIRE_ALIGNED(x, X);
   DeviceGuard guard(p->device);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == AC_F64) return launch_fwd_f64(p, static_cast<const double*>(x), static_cast<double*>(X), B, K, K + 1, C, s);
-  if (dtype == AC_F16) return launch_fwd_f16(p, static_cast<const f16_t*>(x), static_cast<f16_t*>(X), B, K, K + 1, C, s);
-  if (wave_level(p, C, 2, K) && C <= 2)   // bfloat16 on the wave-level kernels (stereo / mono)
+  if (dtype == AC_BF16 && wave_level(p, C, 2, K) && C <= 2)   // bfloat16 on the wave-level kernels (stereo / mono)
     return launch_fwd_fast(p, nullptr, x, 2, static_cast<float*>(X), nullptr, nullptr, 0.f, nullptr, B, K, K + 1, C, s);
-  return launch_fwd_bf16(p, static_cast<const bf16_t*>(x), static_cast<bf16_t*>(X), B, K, K + 1, C, s);
+  return launch_fwd_typed(p, x, X, nullptr, dtype, B, K, K + 1, C, s);
 }
 
 int ac_mdct_inverse_typed(const ac_mdct_plan* p, const void* X, void* x, int dtype, int B, int Kp, int C, void* stream) {
@@ -281,11 +279,9 @@ int ac_mdct_inverse_typed(const ac_mdct_plan* p, const void* X, void* x, int dty
   AC_REQUIRE_ALIGNED(x, X);
   DeviceGuard guard(p->device);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == AC_F64) return launch_inv_f64(p, static_cast<const double*>(X), static_cast<double*>(x), B, Kp, Kp + 1, C, s);
-  if (dtype == AC_F16) return launch_inv_f16(p, static_cast<const f16_t*>(X), static_cast<f16_t*>(x), B, Kp, Kp + 1, C, s);
-  if (wave_level(p, C, 2, Kp) && C <= 2)
+  if (dtype == AC_BF16 && wave_level(p, C, 2, Kp) && C <= 2)
     return launch_inv_fast(p, static_cast<const float*>(X), x, 2, nullptr, nullptr, B, Kp, Kp + 1, C, s);
-  return launch_inv_bf16(p, static_cast<const bf16_t*>(X), static_cast<bf16_t*>(x), B, Kp, Kp + 1, C, s);
+  return launch_inv_typed(p, X, x, nullptr, nullptr, dtype, B, Kp, Kp + 1, C, s);
 }
 
 int ac_tonality_typed(const ac_psy_plan* p, const void* X, void* t, int dtype, int B, int F, int C, void* stream) {
@@ -299,10 +295,9 @@ int ac_tonality_typed(const ac_psy_plan* p, const void* X, void* t, int dtype, i
   AC_REQUIRE_ALIGNED(X);
   DeviceGuard guard(p->device);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == AC_F64) return launch_tonality_f64(p, static_cast<const double*>(X), static_cast<double*>(t), B, F, C, s);
-  if (p->fast && !g_force_generic && C <= 2)
+  if (dtype == AC_BF16 && p->fast && !g_force_generic && C <= 2)
     return launch_psy_fast(p, static_cast<const float*>(X), nullptr, static_cast<float*>(t), nullptr, 0.f, B, F, C, s, 2);
-  return launch_tonality_bf16(p, static_cast<const bf16_t*>(X), static_cast<bf16_t*>(t), B, F, C, s);
+  return launch_tonality_typed(p, X, t, dtype, B, F, C, s);
 }
 
 int ac_mask_threshold_typed(const ac_psy_plan* p, const void* X, const void* t, double drown, void* thr, int dtype, int B,
@@ -319,14 +314,10 @@ int ac_mask_threshold_typed(const ac_psy_plan* p, const void* X, const void* t, 
   AC_REQUIRE_ALIGNED(X, thr);
   DeviceGuard guard(p->device);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == AC_F64)
-    return launch_threshold_f64(p, static_cast<const double*>(X), static_cast<const double*>(t), drown,
-                                static_cast<double*>(thr), B, F, C, s);
-  if (p->fast && !g_force_generic && C <= 2)
+  if (dtype == AC_BF16 && p->fast && !g_force_generic && C <= 2)
     return launch_psy_fast(p, static_cast<const float*>(X), static_cast<const float*>(t), nullptr, static_cast<float*>(thr),
                            (float)drown, B, F, C, s, 2);
-  return launch_threshold_bf16(p, static_cast<const bf16_t*>(X), static_cast<const bf16_t*>(t), (float)drown,
-                               static_cast<bf16_t*>(thr), B, F, C, s);
+  return launch_threshold_typed(p, X, t, drown, thr, dtype, B, F, C, s);
 }
 
 int ac_amplitude_to_db_typed(const void* a, void* out, size_t n, int norm, int dtype, void* stream) {
@@ -347,7 +338,7 @@ int ac_tonality_backward_typed(const ac_psy_plan* p, const void* X, const void* 
   if (B == 0 || C == 0 || F == 0) return AC_OK;
   AC_REQUIRE(X != nullptr && grad_t != nullptr && grad_X != nullptr, "NULL tensor pointer");
   DeviceGuard guard(p->device);
-  return launch_tonality_bwd_typed(p, X, grad_t, grad_X, dtype, B, F, C, (hipStream_t)stream);
+  return launch_tonality_bwd_typed(p, X, grad_t, grad_X, 0, dtype, B, F, C, (hipStream_t)stream);
 }
 
 int ac_mask_threshold_backward_typed(const ac_psy_plan* p, const void* X, const void* t, double drown, const void* grad_thr, void* grad_X,

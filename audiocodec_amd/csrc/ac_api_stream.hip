@@ -110,7 +110,7 @@ static int stream_analysis(ac_stream* s, const ac_psy_plan* psy, const float* x_
     if (st) return st;
     advance_prev(s);
   } else {
-    st = launch_fwd_generic(p, x_chunk, X, s->d_prev_block, s->B, k, k, s->C, hs);
+    st = launch_fwd_typed(p, x_chunk, X, s->d_prev_block, AC_F32, s->B, k, k, s->C, hs);
     if (st) return st;
     // new state = last block of the chunk, per clip: B rows of N*C floats, source pitch k*N*C floats
     const size_t row = (size_t)p->N * s->C * sizeof(float);
@@ -151,7 +151,7 @@ int ac_stream_inverse(ac_stream* s, const float* X_chunk, float* x, int k, void*
   if (wave_level(p, s->C, 0, k))
     st = launch_inv_fast(p, X_chunk, x, false, s->d_tail, s->d_tail_tmp, s->B, k, k, s->C, hs);
   else
-    st = launch_inv_generic(p, X_chunk, x, s->d_tail, s->d_tail_tmp, s->B, k, k, s->C, hs);
+    st = launch_inv_typed(p, X_chunk, x, s->d_tail, s->d_tail_tmp, AC_F32, s->B, k, k, s->C, hs);
   if (!st) advance_tail(s, false);
   return st;
 }
@@ -440,14 +440,13 @@ int ac_stream_encode_typed(ac_stream* s, const ac_psy_plan* psy, const void* x_c
     st = stream_state64(s, hs);
     if (st) return st;
     const double* xd = static_cast<const double*>(x_chunk);
-    st = launch_fwd_f64_stream(p, xd, static_cast<double*>(X), s->d_prev64, s->B, k, k, s->C, hs);
+    st = launch_fwd_typed(p, x_chunk, X, s->d_prev64, AC_F64, s->B, k, k, s->C, hs);
     if (st) return st;
     const size_t row = (size_t)p->N * s->C * sizeof(double);
     AC_HIP_CHECK(hipMemcpy2DAsync(s->d_prev64, row, xd + (size_t)(k - 1) * p->N * s->C, row * k, row, (size_t)s->B, hipMemcpyDeviceToDevice, hs));
     if (psy) {
-      st = launch_tonality_f64(psy, static_cast<const double*>(X), static_cast<double*>(t), s->B, k, s->C, hs);
-      if (!st) st = launch_threshold_f64(psy, static_cast<const double*>(X), static_cast<const double*>(t), drown, static_cast<double*>(thr),
-                                         s->B, k, s->C, hs);
+      st = launch_tonality_typed(psy, X, t, AC_F64, s->B, k, s->C, hs);
+      if (!st) st = launch_threshold_typed(psy, X, t, drown, thr, AC_F64, s->B, k, s->C, hs);
     }
     return st;
   }
@@ -475,8 +474,7 @@ int ac_stream_inverse_typed(ac_stream* s, const void* X_chunk, void* x, int dtyp
   DeviceGuard guard(s->device);
   if (dtype == AC_F64) {
     st = stream_state64(s, (hipStream_t)stream);
-    if (!st) st = launch_inv_f64_stream(s->plan, static_cast<const double*>(X_chunk), static_cast<double*>(x), s->d_tail64, s->d_tail64_tmp,
-                                        s->B, k, k, s->C, (hipStream_t)stream);
+    if (!st) st = launch_inv_typed(s->plan, X_chunk, x, s->d_tail64, s->d_tail64_tmp, AC_F64, s->B, k, k, s->C, (hipStream_t)stream);
     if (st) return st;
     std::swap(s->d_tail64, s->d_tail64_tmp);
     return AC_OK;

@@ -101,7 +101,7 @@ __device__ __forceinline__ v2f spread(v2f v, char* buf, const uint32_t* pimg_g, 
   return acc0 + acc1;
 }
 
-// d thr / d X and d thr / d t  (the chain of k_threshold_bwd_generic in ac_generic.hip, psychoacoustic.py:122-148 with
+// d thr / d X and d thr / d t  (the chain of k_threshold_bwd_generic in ac_psy_generic.hip, psychoacoustic.py:122-148 with
 // 169-210, 301-331), and d t / d X (psychoacoustic.py:102-120) when TONALITY
 template <int R, int CMODE, bool TONALITY, int NW>
 __global__ __launch_bounds__(NW * 64, 2) void k_psy_bwd_fast(PsyBwdArgs a) {

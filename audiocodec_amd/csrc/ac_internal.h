@@ -83,7 +83,7 @@ struct DeviceTables {
   }
 };
 
-// ---- element-wise pieces shared by the stand-alone utilities (ac_generic.hip) and the fused encode epilogue (ac_fast_psy_dev.h):
+// ---- element-wise pieces shared by the stand-alone utilities (ac_elementwise.hip) and the fused encode epilogue (ac_fast_psy_dev.h):
 // one definition, so that fused and un-fused results agree bit for bit
 // counter-based generator: a 64-bit mix (splitmix64) of (seed, pair index) -> Box-Muller, both outputs used:
 // elements 2p and 2p+1 of the flattened tensor take R cos(theta) and R sin(theta)
@@ -227,8 +227,30 @@ struct ac_stream {
 // ---- kernel launchers (each returns an AC_* status) -----------------------------------------
 namespace ac {
 
-// generic O(N^2) kernels: any even N, any C, any M
-int lds_fft_tier_of(const ac_mdct_plan* p, int C);   // ac_generic.hip: 2 / 1 / 0, see ac_mdct_plan_tier
+int check_grid(long long n);   // ac_mdct_generic.hip.  0: launch, 1: nothing to do, < 0: error (too many workgroups)
+// ---- the tiers below the wave-level kernels: any even N, any C, any M.  One function per kernel family; `dtype` (AC_*) is the
+// element type of the tensors behind the void pointers.  The C ABI checks it before it calls (AC_REQUIRE_DTYPE*).
+// Filter bank (ac_mdct_generic.hip), AC_F32 / AC_F64 / AC_BF16 / AC_F16: the LDS-FFT tier where it serves, else the O(N^2)
+// kernels.  The streaming state may be null: prev_block [B,N,C] of the tensors' type, block -1 of every signal; tail_in / tail_out
+// [B,C,N/2], float (double for AC_F64): the aliased half of the frame before frame 0 in, of the last one out
+int launch_fwd_typed(const ac_mdct_plan* p, const void* x, void* X, const void* prev_block, int dtype, int B, int Kin, int F, int C,
+                     hipStream_t s);
+int launch_inv_typed(const ac_mdct_plan* p, const void* X, void* x, const void* tail_in, void* tail_out, int dtype, int B, int Kp,
+                     int nblk, int C, hipStream_t s);
+int lds_fft_tier_of(const ac_mdct_plan* p, int C);   // ac_mdct_generic.hip: 2 / 1 / 0, see ac_mdct_plan_tier
+// Masking model and its backward (ac_psy_generic.hip), AC_F32 / AC_F64 / AC_BF16; float64: everything in double on the float64
+// tables, bfloat16: float32 arithmetic and tables
+int launch_tonality_typed(const ac_psy_plan* p, const void* X, void* t, int dtype, int B, int F, int C, hipStream_t s);
+int launch_threshold_typed(const ac_psy_plan* p, const void* X, const void* t, double drown, void* thr, int dtype, int B, int F,
+                           int C, hipStream_t s);
+int launch_tonality_bwd_typed(const ac_psy_plan* p, const void* X, const void* gt, void* gX, int accumulate, int dtype, int B, int F,
+                              int C, hipStream_t s);
+int launch_threshold_bwd_typed(const ac_psy_plan* p, const void* X, const void* t, double drown, const void* gthr, void* gX, void* gt,
+                               int dtype, int B, int F, int C, hipStream_t s);
+// Element-wise utilities (ac_elementwise.hip), AC_F32 / AC_F64 / AC_BF16; the backward of amplitude_to_dB is float32 only
+int launch_db_typed(const void* a, void* out, size_t n, int norm, int dtype, hipStream_t s);
+int launch_db_bwd(const float* a, const float* g, float* ga, size_t n, int norm, hipStream_t s);
+int launch_add_noise_typed(const void* X, const void* thr, void* out, size_t n, uint64_t seed, int dtype, hipStream_t s);
 // the 16-byte kernels of the LDS-FFT tier (ac_wave_v.h) on stereo rows (ac_wave_stereo.hip) ...
 int launch_fwd_wave_stereo(const ac_mdct_plan* p, const float* x, float* X, const float* prev_block, int B, int Kin, int F,
                            hipStream_t s);
@@ -263,13 +285,6 @@ int launch_fwd_wave_strided(const ac_mdct_plan* p, const float* x, float* X, con
                             int C, hipStream_t s);
 int launch_inv_wave_strided(const ac_mdct_plan* p, const float* X, float* x, const float* tail_in, float* tail_out, int B,
                             int Kp, int nblk, int C, hipStream_t s);
-int launch_fwd_generic(const ac_mdct_plan* p, const float* x, float* X, const float* prev_block, int B, int Kin,
-                       int F, int C, hipStream_t s);
-int launch_inv_generic(const ac_mdct_plan* p, const float* X, float* x, const float* tail_in, float* tail_out,
-                       int B, int Kp, int nblk, int C, hipStream_t s);
-int launch_tonality_generic(const ac_psy_plan* p, const float* X, float* t, int B, int F, int C, hipStream_t s);
-int launch_threshold_generic(const ac_psy_plan* p, const float* X, const float* t, float drown, float* thr, int B,
-                             int F, int C, hipStream_t s);
 
 // wave-level FFT kernels (ac_fast_*.hip; what they share among themselves: ac_fast.h)
 bool fast_mdct_supported(int N, const FoldCoef& c);
@@ -379,40 +394,10 @@ int launch_psy_mid(const ac_psy_plan* p, const float* X, const float* t_in, floa
 bool build_runs(const PsyTables& t, std::vector<uint32_t>* out, RunsLayout* lay);
 int runs_psy_plan_init(ac_psy_plan* p);
 
-int launch_tonality_bwd_generic(const ac_psy_plan* p, const float* X, const float* gt, float* gX, int accumulate, int B,
-                                int F, int C, hipStream_t s);
-int launch_threshold_bwd_generic(const ac_psy_plan* p, const float* X, const float* t, float drown, const float* gthr,
-                                 float* gX, float* gt, int B, int F, int C, hipStream_t s);
 // wave-level backward: tonality backward when g_thr is null, else threshold backward
 int launch_psy_bwd_fast(const ac_psy_plan* p, const float* X, const float* t, float drown, const float* g_thr,
                         const float* g_t, float* g_X, float* g_t_out, int accumulate, int B, int F, int C,
                         hipStream_t s);
-// compute_dtype variants (ac_generic.hip)
-int launch_fwd_f64(const ac_mdct_plan* p, const double* x, double* X, int B, int Kin, int F, int C, hipStream_t s);
-int launch_inv_f64(const ac_mdct_plan* p, const double* X, double* x, int B, int Kp, int nblk, int C, hipStream_t s);
-// ... with the streaming state (block -1 of every signal / the aliased half of the frame before frame 0 in, of the last one out)
-int launch_fwd_f64_stream(const ac_mdct_plan* p, const double* x, double* X, const double* prev_block, int B, int Kin, int F, int C,
-                          hipStream_t s);
-int launch_inv_f64_stream(const ac_mdct_plan* p, const double* X, double* x, const double* tail_in, double* tail_out, int B, int Kp,
-                          int nblk, int C, hipStream_t s);
-int launch_fwd_bf16(const ac_mdct_plan* p, const bf16_t* x, bf16_t* X, int B, int Kin, int F, int C, hipStream_t s);
-int launch_inv_bf16(const ac_mdct_plan* p, const bf16_t* X, bf16_t* x, int B, int Kp, int nblk, int C, hipStream_t s);
-int launch_fwd_f16(const ac_mdct_plan* p, const f16_t* x, f16_t* X, int B, int Kin, int F, int C, hipStream_t s);
-int launch_inv_f16(const ac_mdct_plan* p, const f16_t* X, f16_t* x, int B, int Kp, int nblk, int C, hipStream_t s);
-int launch_tonality_f64(const ac_psy_plan* p, const double* X, double* t, int B, int F, int C, hipStream_t s);
-int launch_tonality_bf16(const ac_psy_plan* p, const bf16_t* X, bf16_t* t, int B, int F, int C, hipStream_t s);
-int launch_threshold_f64(const ac_psy_plan* p, const double* X, const double* t, double drown, double* thr, int B, int F,
-                         int C, hipStream_t s);
-int launch_threshold_bf16(const ac_psy_plan* p, const bf16_t* X, const bf16_t* t, float drown, bf16_t* thr, int B, int F,
-                          int C, hipStream_t s);
-int launch_tonality_bwd_typed(const ac_psy_plan* p, const void* X, const void* gt, void* gX, int dtype, int B, int F, int C, hipStream_t s);
-int launch_threshold_bwd_typed(const ac_psy_plan* p, const void* X, const void* t, double drown, const void* gthr, void* gX, void* gt,
-                               int dtype, int B, int F, int C, hipStream_t s);
-int launch_db_typed(const void* a, void* out, size_t n, int norm, int dtype, hipStream_t s);
-int launch_add_noise_typed(const void* X, const void* thr, void* out, size_t n, uint64_t seed, int dtype, hipStream_t s);
-int launch_db(const float* a, float* out, size_t n, int norm, hipStream_t s);
-int launch_db_bwd(const float* a, const float* g, float* ga, size_t n, int norm, hipStream_t s);
-int launch_add_noise(const float* X, const float* thr, float* out, size_t n, uint64_t seed, hipStream_t s);
 // Launch geometry of the quantiser, pack and rate kernels: grid (B*F rows, channel groups), a block of whole waves.
 constexpr int kRowThreads = 256;   // the most threads of a block: the __launch_bounds__ of every kernel row_launch serves
 struct RowLaunch {

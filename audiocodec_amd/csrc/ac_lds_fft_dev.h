@@ -1,4 +1,4 @@
-// Device building blocks of the LDS-FFT tier, shared by its run-time forms (ac_generic.hip) and by the 16-byte kernels with the
+// Device building blocks of the LDS-FFT tier, shared by its run-time forms (ac_mdct_generic.hip) and by the 16-byte kernels with the
 // size and the plan known at compile time (ac_wave_v.h and the translation units that instantiate them): the complex pair
 // arithmetic, the Stockham passes and the DCT-IV around them, the LDS padding and the LDS sizes per frame.  gfx950 only.
 #pragma once

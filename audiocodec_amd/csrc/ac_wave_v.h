@@ -2,7 +2,7 @@
 // and the launch templates that pick an instance.  Each row layout instantiates them in a translation unit of its own
 // (ac_wave_stereo.hip, ac_wave_mono.hip, ac_wave_strided.hip); the team form (ac_wave_team.hip) and the fused encode
 // (ac_wave_enc.hip) build on the same pieces.  The host plan and geometry helpers declared here are defined once, with the
-// dispatch, in ac_generic.hip.  gfx950 only.
+// dispatch, in ac_mdct_generic.hip.  gfx950 only.
 #pragma once
 #include <initializer_list>
 #include <map>
@@ -23,7 +23,7 @@ namespace ac {
 // current frame and land while it runs.
 // The two rows a complex pair carries through the transform (LAY): 0 the channels of a stereo signal (one 16-byte access
 // per two samples); 1 two mono signals b, b + 1 (8 bytes each; the last pair of an odd batch is half empty); 2 the channels
-// c, c + 1 of three or more channels (8-byte accesses on the 4-byte grid; the last pair of an odd count is half empty).  bfloat16 tensors and filters_n % 4 == 2 run the 8-byte kernels (ac_generic.hip).
+// c, c + 1 of three or more channels (8-byte accesses on the 4-byte grid; the last pair of an odd count is half empty).  bfloat16 tensors and filters_n % 4 == 2 run the 8-byte kernels (k_fwd_wave / k_inv_wave, ac_mdct_generic.hip).
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 // instances of the 16-byte kernels that form the lane's LDS offsets per frame from opaque copies instead of holding them, hoisted,
 // across the frame loop: ~130 instead of ~200 registers; with every instance in that form, slower at most sizes (+2 ... +13 %, 18
@@ -535,7 +535,7 @@ int allow_lds(K kernel, size_t bytes) {
   AC_WAVE_CT(2048, 128, 8, 8, 8, 2)
 #endif
 
-// defined in ac_generic.hip, with the dispatch
+// defined in ac_mdct_generic.hip, with the dispatch
 bool lds_wave_ct_size(int N);   // a size of AC_WAVE_CT_SIZES
 bool wave_ct_off();             // AC_LDS_WAVE_NOCT: the compile-time instances off (A/B measurements)
 WavePlan lds_wave_plan(int N, bool groups = true);   // groups: frames dealt to more than one wave allowed (the 16-byte kernels)
@@ -543,7 +543,6 @@ bool lds_wave_vec_ok(const ac_mdct_plan* p, const WavePlan& wp, int C);   // the
 int wave_v_layout(int C, std::initializer_list<const void*> ptrs);        // LAY of RowPair for these tensors, -1: none
 void wave_v_geometry(int N, const WavePlan& wp, int* w, int* gpw, size_t* lds);
 int wave_strip(long long pairs, int per_sig, int gpw, int w, size_t lds, int cus, double extra);
-int check_grid(long long n);   // 0: launch, 1: nothing to do, < 0: error (too many workgroups)
 
 // sizes with instances on 16-bit PCM rows (stereo / mono): the frame lengths of the speech and music codecs this tier is for
 #define AC_WAVE_PCM_SIZES             \

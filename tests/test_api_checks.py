@@ -7,6 +7,9 @@ Every call here is refused before any launch, so a case costs a ctypes call.  Th
 NULL tensor, then a NULL ``data``, then a misaligned address, in that order and in the same words.  Texts and order are those
 the entry points had while each carried its own copy of these checks, so this file passes on a library from before they were
 shared and on one after.
+
+The same holds for the size refusals of the generic launchers at the end of the file: one launcher per kernel family serves every
+dtype, and which text a dtype gets ("float64 kernel", "generic kernel", "backward kernel") is what these cases pin.
 """
 
 import ctypes
@@ -147,3 +150,122 @@ def test_mono_at_2048_takes_two_launches():
     """filters_n = 2048: mono input is two launches (the fused kernel would spill registers), stereo one."""
     codec = audiocodec_amd.AudioCodec(48000, 2048)
     assert codec.encode_launches(1) == 2 and codec.encode_launches(2) == 1
+
+
+# ---- the size refusals of the generic launchers ---------------------------------------------------------------------------------
+# Each kernel below the LDS-FFT tier keeps its working set in at most LDS_BOUND bytes of LDS, in the arithmetic type (8 bytes for
+# float64 tensors, 4 for float32 and the 2-byte types): the O(N^2) analysis one frame of filters_n values, the synthesis two, the
+# generic threshold filter_bands_n + 2 bark_bands_n values, its backward 2 filter_bands_n + 10 bark_bands_n.  Every size below is
+# derived from that; a call is one clip, one block, one channel.
+LDS_BOUND = 64 * 1024
+PLAN_MAX_N, PLAN_MAX_M = 8192, 4096   # the largest filters_n / filter_bands_n and bark_bands_n a plan is made for
+M_SMALL = 8                            # a band count the suite runs elsewhere (test_psy_alpha.py)
+
+
+def _first_even_filters_n(bytes_per_filter):
+    """The first even filters_n whose working set of bytes_per_filter * filters_n bytes is above LDS_BOUND."""
+    n = LDS_BOUND // bytes_per_filter + 1
+    return n + (n & 1)
+
+
+def _smooth5(h):
+    for r in (2, 3, 5):
+        while h % r == 0:
+            h //= r
+    return h == 1
+
+
+def _device():
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _expect_einval(status, text):
+    got = _lib.load().ac_last_error().decode()
+    assert status == _lib.AC_EINVAL and got == text, (status, got, text)
+
+
+def _float64_inverse(n):
+    """Status of ac_mdct_inverse_typed on one float64 frame of n filters (ctypes: MDCTransformer.inverse_transform refuses
+    float64 above 4096 itself, with a text of its own)."""
+    mdct = audiocodec_amd.MDCTransformer(n, compute_dtype=torch.float64)
+    X = torch.zeros((1, 1, n, 1), dtype=torch.float64, device=_device())
+    x = torch.zeros((1, 2 * n, 1), dtype=torch.float64, device=_device())
+    st = mdct._lib.ac_mdct_inverse_typed(mdct._plan(_device()), ctypes.c_void_p(X.data_ptr()), ctypes.c_void_p(x.data_ptr()),
+                                         mdct._dtype_id, 1, 1, 1, None)
+    torch.cuda.synchronize()
+    return st
+
+
+@gpu
+def test_float64_synthesis_refuses_past_two_frames_of_lds():
+    """launch_inv_T<double>: 16 bytes per filter.  4098 is refused in the float64 kernel's words, 4096 is served."""
+    n = _first_even_filters_n(16)
+    assert n == 4098
+    _expect_einval(_float64_inverse(n), "filters_n = %d too large for the float64 kernel" % n)
+    assert _float64_inverse(n - 2) == _lib.AC_OK
+
+
+@gpu
+@pytest.mark.parametrize("what, bytes_per_filter", [("float64 analysis", 8), ("float32 analysis", 4), ("float32 synthesis", 8)])
+def test_plan_creation_refuses_first_what_these_launchers_would(what, bytes_per_filter):
+    """Not cases of the launchers: the first even filters_n past the bound of the float64 analysis (8194) and of the float32
+    synthesis (8194) and analysis (16386) -- halves not 5-smooth, so the O(N^2) kernels would be the ones reached -- are above the
+    8192 that ac_mdct_plan_create admits, and it refuses with its own text.  "filters_n = %d too large for the float64 / generic
+    kernel" cannot be reached through the C ABI for these three."""
+    n = _first_even_filters_n(bytes_per_filter)
+    assert n > PLAN_MAX_N and not _smooth5(n // 2)
+    out = ctypes.c_void_p()
+    st = _lib.load().ac_mdct_plan_create(n, _lib.window_id("vorbis"), torch.cuda.current_device(), ctypes.byref(out))
+    _expect_einval(st, "filters_n = %d not supported (max %d)" % (n, PLAN_MAX_N))
+    assert not out.value
+
+
+@gpu
+def test_float64_analysis_serves_the_largest_plan():
+    """launch_fwd_T<double>: 8 bytes per filter, so filters_n = 8192 fills the bound exactly and is served."""
+    assert 8 * PLAN_MAX_N == LDS_BOUND
+    mdct = audiocodec_amd.MDCTransformer(PLAN_MAX_N, compute_dtype=torch.float64)
+    X = mdct.transform(torch.zeros((1, PLAN_MAX_N, 1), dtype=torch.float64, device=_device()))
+    torch.cuda.synchronize()
+    assert tuple(X.shape) == (1, 2, PLAN_MAX_N, 1)
+
+
+def _threshold(n, dtype, backward):
+    """The generic threshold (or its backward) on one frame of n filters and M_SMALL bands through PsychoacousticModel."""
+    model = audiocodec_amd.PsychoacousticModel(48000, n, M_SMALL, compute_dtype=dtype)
+    X = torch.full((1, 1, n, 1), 0.5, dtype=dtype, device=_device())
+    t = torch.full((1, 1, 1, 1), 0.5, dtype=dtype, device=_device())
+    out = model._threshold_backward(X, t, 0.0, torch.ones_like(X)) if backward else model.global_masking_threshold(X, t)
+    torch.cuda.synchronize()
+    return out
+
+
+@gpu
+@pytest.mark.parametrize("dtype, backward, words, kernel", [
+    (torch.float64, False, lambda n, m: n + 2 * m, "float64"),
+    (torch.float64, True, lambda n, m: 2 * n + 10 * m, "backward"),
+    (torch.float32, True, lambda n, m: 2 * n + 10 * m, "backward"),
+], ids=["float64-forward", "float64-backward", "float32-backward"])
+def test_generic_threshold_refuses_past_its_lds(dtype, backward, words, kernel):
+    """launch_threshold_T<double> names the float64 kernel, launch_threshold_bwd_T the backward kernel in every dtype.  The
+    largest even filter_bands_n whose working set fits the bound at 8 bands is served, the next even one refused (ValueError is
+    what the package makes of AC_EINVAL)."""
+    size = 8 if dtype == torch.float64 else 4
+    n = max(n for n in range(2, PLAN_MAX_N + 1, 2) if words(n, M_SMALL) * size <= LDS_BOUND)
+    assert n + 2 <= PLAN_MAX_N and words(n + 2, M_SMALL) * size > LDS_BOUND
+    _threshold(n, dtype, backward)
+    with pytest.raises(ValueError) as e:
+        _threshold(n + 2, dtype, backward)
+    assert str(e.value) == "filter_bands_n = %d / bark_bands_n = %d too large for the %s kernel" % (n + 2, M_SMALL, kernel)
+
+
+@gpu
+def test_plan_creation_refuses_first_what_the_float32_arithmetic_threshold_would():
+    """Not a case of the launcher: float32 and bfloat16 tensors (float32 arithmetic) cross the bound at filter_bands_n +
+    2 bark_bands_n > 16384, and the largest plan, 8192 filters and 4096 bands, has exactly 16384.  One band more is refused by
+    ac_psy_plan_create with its own text; "... too large for the generic kernel" cannot be reached through the C ABI."""
+    assert (PLAN_MAX_N + 2 * PLAN_MAX_M) * 4 == LDS_BOUND
+    out = ctypes.c_void_p()
+    st = _lib.load().ac_psy_plan_create(PLAN_MAX_N, PLAN_MAX_M + 1, 48000.0, 0.6, torch.cuda.current_device(), ctypes.byref(out))
+    _expect_einval(st, "filter_bands_n = %d / bark_bands_n = %d not supported" % (PLAN_MAX_N, PLAN_MAX_M + 1))
+    assert not out.value

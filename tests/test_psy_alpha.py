@@ -309,7 +309,7 @@ def test_fused_encode_beside_1024_at_other_alpha(N, alpha, monkeypatch):
         _hold_encode(X, t, thr, 0.4, (48000, N, 64), alpha, TOL, "fused encode beside 1024")
 
 
-# ---- the generic kernels (ac_generic.hip:532-541) -----------------------------------------------------------------------------
+# ---- the generic kernels (ac_psy_generic.hip) ---------------------------------------------------------------------------------
 GENERIC = [(48000, 1024, 64, torch.float32), (48000, 30, 8, torch.float32), (48000, 1024, 128, torch.float32),
            (48000, 2048, 64, torch.float64), (48000, 960, 64, torch.bfloat16), (48000, 1024, 64, torch.bfloat16)]
 
@@ -321,10 +321,10 @@ def _generic_id(sr, N, M, dt, *rest):
 @pytest.mark.parametrize("alpha", ALPHAS)
 @pytest.mark.parametrize("case", range(len(GENERIC)), ids=[_generic_id(*c) for c in GENERIC])
 def test_generic_forward_at_other_alpha(case, alpha):
-    """k_threshold_generic (ac_generic.hip:532-541: m_pow(max(eps, P), alpha), 10^(-alpha O / 10), (fac A)^(1/alpha)) with
-    ac_set_force_generic(1), from each of its four launch sites: float32 (launch_threshold_generic, :1154) at 64 bands, at a
-    small layout (30 filters, 8 bands) and at 128 bands; float64 (launch_threshold_f64, :1406); bfloat16 tensors with float32
-    arithmetic (launch_threshold_bf16, :1419).  (The fourth site, :1189, is the backward's launch: below.)"""
+    """k_threshold_generic (ac_psy_generic.hip: m_pow(max(eps, P), alpha), 10^(-alpha O / 10), (fac A)^(1/alpha)) with
+    ac_set_force_generic(1), in each instance of its one launcher (launch_threshold_T): float32 at 64 bands, at a small layout
+    (30 filters, 8 bands) and at 128 bands; float64; bfloat16 tensors with float32 arithmetic.  (The backward has a launcher
+    of its own, launch_threshold_bwd_T: below.)"""
     sr, N, M, dt = GENERIC[case]
     p = audiocodec_amd.PsychoacousticModel(sr, filter_bands_n=N, bark_bands_n=M, alpha=alpha, compute_dtype=dt)
     X = torch.from_numpy(_spectrum(N + M, 2, 3, N, 3)).cuda().to(dt)
@@ -406,7 +406,7 @@ GENERIC_BWD = [(48000, 960, 64, 2, 3, 3, torch.float32), (48000, 120, 20, 2, 3, 
 @pytest.mark.parametrize("case", range(len(GENERIC_BWD)),
                          ids=[_generic_id(c[0], c[1], c[2], c[6], "B%dF%dC%d" % c[3:6]) for c in GENERIC_BWD])
 def test_generic_backward_at_other_alpha(case, alpha):
-    """k_threshold_bwd_generic (ac_generic.hip:641-701, launched at :1189 with (TC) alpha) in float32 -- at 960 filters, at
+    """k_threshold_bwd_generic (ac_psy_generic.hip, launched by launch_threshold_bwd_T with (TC) alpha) in float32 -- at 960 filters, at
     a small layout of 20 bands with seven channels, and at 128 bands -- in float64 and on bfloat16 tensors: the scheme of
     test_fast_backward_at_other_alpha, drown 1 once per dtype at alpha 0.8."""
     sr, N, M, B, F, C, dt = GENERIC_BWD[case]

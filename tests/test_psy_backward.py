@@ -1,5 +1,5 @@
 """GPU (MI355X): the adjoint kernels of the masking model -- k_psy_bwd_fast (ac_fast_psy_bwd.hip: float32, filter_bands_n 1024 /
-2048, 64 bands) and k_tonality_bwd_generic / k_threshold_bwd_generic (ac_generic.hip: every other plan and dtype) --
+2048, 64 bands) and k_tonality_bwd_generic / k_threshold_bwd_generic (ac_psy_generic.hip: every other plan and dtype) --
 against torch.autograd on the float64 restatement (tests/psy_torch_reference.py), evaluated at the very inputs the kernels
 saw, on every path the kernels take: the channel modes and row widths of the fast kernel with a half-filled last pair,
 partial and chip-filling grids, more than 64 bands, the spreading matrix from global memory, the accumulate form of the C
