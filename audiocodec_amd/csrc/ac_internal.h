@@ -125,7 +125,7 @@ __device__ __forceinline__ short to_pcm16(float v) {
 typedef __bf16 bf16_t;   // storage type of the AC_BF16 tensors (device code converts with v_cvt_pk_bf16_f32)
 typedef _Float16 f16_t;  // storage type of the AC_F16 tensors (filter bank only)
 
-// layout of the run-structured masking-model image and of its per-frame LDS slot (build_runs in ac_psy_mid.hip; the fields
+// layout of the run-structured masking-model image and of its per-frame LDS slot (build_runs in ac_psy_mid_plan.hip; the fields
 // are those of runs::RunsParams, ac_psy_runs_dev.h)
 struct RunsLayout {
   int words = 0;
@@ -183,7 +183,7 @@ struct ac_psy_plan {
   int mid = 0;
   uint32_t* d_mid = nullptr;
   int mid_words = 0;
-  int mid_wi_w = 0, mid_off_S = 0, mid_off_band = 0, mid_off_wbe = 0, mid_off_wi = 0;   // layout of the image (build_mid)
+  int mid_wi_w = 0, mid_off_S = 0, mid_off_band = 0, mid_off_wbe = 0, mid_off_wi = 0;   // layout of the image (build_mid, ac_psy_mid_plan.hip)
   // ... in its run-structured form (ac_psy_runs_dev.h): the form every kernel of that tier runs when the plan's tables have
   // the structure (runs = 1; the band walk above stays for tables that do not)
   int runs = 0;
@@ -384,15 +384,17 @@ int launch_duplex_fast(const ac_mdct_plan* p, const ac_psy_plan* psy, const floa
                        float drown, const float* prev_block, float* state_out, int k_fwd, const float* X_inv, float* x_inv,
                        const float* tail_in, float* tail_out, int k_inv, int B, int C, hipStream_t s);
 
-// wave-level masking model for general band layouts (ac_psy_mid.hip); mono / stereo float32
+// wave-level masking model for general band layouts; float32, any channel count.  The plan's side (ac_psy_mid_plan.hip) ...
 bool mid_psy_supported(const ac_psy_plan* p);
 int mid_psy_plan_init(ac_psy_plan* p);
-int launch_psy_mid(const ac_psy_plan* p, const float* X, const float* t_in, float* t_out, float* thr, float drown, int B,
-                   int F, int C, hipStream_t s);
 // the run-structured image of a model's tables, built on the host (no device needed): false when the tables lack the
 // structure (ac_psy_runs_dev.h); runs_psy_plan_init uploads it
 bool build_runs(const PsyTables& t, std::vector<uint32_t>* out, RunsLayout* lay);
 int runs_psy_plan_init(ac_psy_plan* p);
+// ... and the launch (ac_psy_mid.hip): the run-structured form where the plan has its image, else the band walk.
+// t_out != null: tonality (from X); thr != null: threshold (from t_out when given, else from t_in)
+int launch_psy_mid(const ac_psy_plan* p, const float* X, const float* t_in, float* t_out, float* thr, float drown, int B,
+                   int F, int C, hipStream_t s);
 
 // wave-level backward: tonality backward when g_thr is null, else threshold backward
 int launch_psy_bwd_fast(const ac_psy_plan* p, const float* X, const float* t, float drown, const float* g_thr,

@@ -1,5 +1,5 @@
 // Device code of the wave-level masking model for general band layouts, shared by the stand-alone kernel (k_psy_mid,
-// ac_psy_mid.hip) and the fused encode of the several-frames-per-wave MDCT kernels (k_fwd_multi, ac_fast_multi.hip): ONE
+// ac_psy_mid.hip; its image: build_mid, ac_psy_mid_plan.hip) and the fused encode of the several-frames-per-wave MDCT kernels (k_fwd_multi, ac_fast_multi.hip): ONE
 // definition of the per-frame arithmetic, so that the fused and the un-fused encode agree bit for bit.  gfx950 only.
 //
 // One frame (both signals of a pair) per call, all 64 lanes: the frame's granules xq[i] = (X[2q], X[2q+1]) x (s0, s1),
@@ -291,7 +291,9 @@ __device__ __forceinline__ void threshold_frames(const v4f (&xq)[FB][R], const v
 
 }  // namespace mid
 
-// the launch-time parameters of a plan's image (ac_psy_mid.hip)
+// the launch-time parameters of a plan's image (ac_psy_mid_plan.hip), and the dynamic LDS of a workgroup of nw waves that
+// take fb frames at a time: the image's lds_words and the waves' buffers
 mid::MidParams mid_params(const ac_psy_plan* p, float drown);
+size_t mid_lds_bytes(int N, int lds_words, int nw, int fb);
 
 }  // namespace ac

@@ -1,10 +1,10 @@
 // Device code of the wave-level masking model for general band layouts in its run-structured form (round 4): the model
 // of ac_psy_mid_dev.h with the structure every Bark mapping of the reference has (psychoacoustic.py:257-299) taken out of
-// the frame loop at plan time.  Shared by the stand-alone kernel (k_psy_runs, ac_psy_mid.hip), the fused encode of the
+// the frame loop at plan time.  Shared by the stand-alone kernels (k_psy_runs, ac_psy_mid.hip; k_psy_runs_c, ac_psy_runs_team_dev.h), the fused encode of the
 // several-frames-per-wave MDCT kernels (k_fwd_multi, ac_fast_multi.hip) and the fused encode of the LDS-FFT tier (k_enc_wave_v,
 // ac_wave_enc.hip): ONE definition of the per-frame arithmetic, so the fused and the un-fused encode agree bit for bit.
 //
-// What the structure is (checked by build_runs on the host; a plan that does not have it keeps the band walk):
+// What the structure is (checked by build_runs, ac_psy_mid_plan.hip, on the host; a plan that does not have it keeps the band walk):
 //   * W (bins -> bands, :301-315): the bins of band j are one contiguous run f0 .. f1; the interior bins f0+1 .. f1-1 carry
 //     weight exactly 1, only the two edge bins a fraction.  So P_j = w0 I[f0] + w1 I[f1] + (sum of the interior), and the
 //     interior is covered by a host-built list of aligned partial sums over 4, 16 (and 64) bins plus single bins: at most
@@ -535,7 +535,7 @@ __device__ __forceinline__ void threshold_frames(const v2f (&t)[FB], const RunsP
 
 }  // namespace runs
 
-// the launch-time parameters of a plan's run-structured image (ac_psy_mid.hip); runs_supported: the plan has one
+// the launch-time parameters of a plan's run-structured image (ac_psy_mid_plan.hip); runs_supported: the plan has one
 bool runs_supported(const ac_psy_plan* p);
 // idx_in_lds: the kernel reads the per-bin entry offsets from the LDS image (else it holds them in registers)
 runs::RunsParams runs_params(const ac_psy_plan* p, float drown, bool idx_in_lds);

@@ -625,7 +625,7 @@ def test_fused_encode_of_a_frame_on_four_waves_at_2048_workgroups(N, C, B, monke
 @pytest.mark.parametrize("N", [300, 480, 512, 600, 640, 960, 1024, 1280, 1536, 2048])
 @pytest.mark.parametrize("C", [3, 4, 5, 6, 7, 8])
 def test_masking_model_of_more_than_two_channels_through_whole_rows(N, C, monkeypatch):
-    """k_psy_runs_c (ac_psy_mid.hip): the waves that take the channel pairs of one frame move the [filter_bands_n, C] row and
+    """k_psy_runs_c (ac_psy_runs_team_dev.h): the waves that take the channel pairs of one frame move the [filter_bands_n, C] row and
     the threshold row in whole 16-byte pieces and pick their pairs out of a row image in LDS (psychoacoustic.py:102-148 takes
     any channels_n) -- against the strided channel pairs (AC_PSY_NOTEAM=1): tonality and thresholds bit for bit, twice (no run
     may differ from another), with a given tonality and with the kernel's own, odd channel counts (a pair either side of a
@@ -1029,12 +1029,34 @@ def _run_child(code, env, tmp_path, name, *args):
     return np.load(f)
 
 
+def _rows_vs_float64_kernels(p64, X, t, thr, drown, what):
+    """t and thr of a float32 masking kernel on X against the float64 kernels (k_*_generic<double>) on X cast up: the tonality
+    from X, the threshold from X and the very tonality the float32 kernel computed or was given.  TOL / tonality_err."""
+    X64 = dev(X).double() if isinstance(X, np.ndarray) else X.double()
+    t64 = dev(t).double() if isinstance(t, np.ndarray) else t.double()
+    thr64 = dev(thr).double() if isinstance(thr, np.ndarray) else thr.double()
+    et = tonality_err(t64, p64.tonality(X64))
+    ref = p64.global_masking_threshold(X64, t64, drown)
+    er = float(((thr64 - ref).abs() / ref).max())
+    print("%s: tonality %.2e of its bar, thr rel %.2e (bar %.0e)" % (what, et, er, TOL))
+    assert et <= 1.0 and er <= TOL, (what, et, er)
+
+
+# the sizes at which a frame fills its 2 / 4 granule registers per lane (no granule past the frame): waves take 4 / 2 rows at a time
+FULL_ROW_SIZES = (256, 512)
+
+
 def test_masking_model_band_walk_at_every_granule_count(tmp_path):
     """k_psy_mid, the band walk the run-structured model replaced where a plan has a run image: AC_NO_RUNS=1 (read once per
     process) puts it back on every plan.  One instance per granule-register count (filters_n 120 ... 3840), row layout
     (stereo, three channels, mono with an odd batch) and set of outputs (tonality, threshold from a given tonality, both in
-    the un-fused encode()); the child returns what it computed and each is held to the oracle here."""
-    sizes, chans = (120, 240, 480, 960, 1920, 3840), (2, 3, 1)
+    the un-fused encode()); the child returns what it computed and each is held to the oracle here.
+
+    256 and 512 (a rectangular window: the encode of mono and stereo stays un-fused there) are the row loader's edges on
+    frames that fill their registers: three clips of five frames are 15 / 30 / 10 tasks for stereo / three channels / mono,
+    never a multiple of the 4 or 2 rows a wave takes at a time -- the last group of some wave has rows past the end -- with
+    the half-empty last pair of three channels and of three mono clips.  Those two sizes are held to the float64 kernels too."""
+    sizes, chans = (120, 240, 480, 960, 1920, 3840) + FULL_ROW_SIZES, (2, 3, 1)
     code = ("import sys, numpy as np, torch, audiocodec_amd\n"
             "out = {}\n"
             "for N in %r:\n"
@@ -1042,20 +1064,21 @@ def test_masking_model_band_walk_at_every_granule_count(tmp_path):
             "        g = torch.Generator(device='cuda').manual_seed(N + C)\n"
             "        x = torch.empty(3, 4 * N, C, device='cuda').uniform_(-1, 1, generator=g)\n"
             "        x *= torch.empty(3, 1, C, device='cuda').uniform_(1e-3, 1, generator=g)\n"
-            "        codec = audiocodec_amd.AudioCodec(48000, N)\n"
+            "        codec = audiocodec_amd.AudioCodec(48000, N, window_type='rect' if N in %r else 'vorbis')\n"
             "        assert codec.psy.tier() == 1 and codec.encode_launches(C) >= 2\n"
             "        X, t, thr = codec.encode(x, 0.2)\n"
             "        ts = codec.psy.tonality(X)\n"
             "        thrs = codec.psy.global_masking_threshold(X, ts, 0.2)\n"
             "        for k, v in (('x', x), ('X', X), ('t', t), ('thr', thr), ('ts', ts), ('thrs', thrs)):\n"
             "            out['%%s_%%d_%%d' %% (k, N, C)] = v.cpu().numpy()\n"
-            "np.savez(sys.argv[1], **out)\n" % (sizes, chans))
+            "np.savez(sys.argv[1], **out)\n" % (sizes, chans, FULL_ROW_SIZES))
     got = _run_child(code, {"AC_NO_RUNS": "1", "AC_LDS_WAVE_NOFUSE": "1"}, tmp_path, "walk.npz")
     for N in sizes:
         o = PsychoOracle(48000, N, 64, compute_dtype=np.float64)
-        om = MDCTOracle(N, "vorbis", np.float64)
+        om = MDCTOracle(N, "rect" if N in FULL_ROW_SIZES else "vorbis", np.float64)
         for C in chans:
             x, X, t, thr, ts, thrs = (got["%s_%d_%d" % (k, N, C)] for k in ("x", "X", "t", "thr", "ts", "thrs"))
+            assert X.shape == (3, 5, N, C)
             Xo = om.transform(x.astype(np.float64))
             assert rel_peak(X, Xo) <= TOL and rel_l2(X, Xo) <= TOL, (N, C)
             X64 = X.astype(np.float64)
@@ -1063,6 +1086,34 @@ def test_masking_model_band_walk_at_every_granule_count(tmp_path):
             assert tonality_err(t, t64) <= 1.0 and tonality_err(ts, t64) <= 1.0, (N, C)
             assert rel_elem(thr, o.global_masking_threshold(X64, t64, 0.2)) <= TOL, (N, C)
             assert rel_elem(thrs, o.global_masking_threshold(X64, ts.astype(np.float64), 0.2)) <= TOL, (N, C)
+            if N in FULL_ROW_SIZES:
+                p64 = audiocodec_amd.PsychoacousticModel(48000, filter_bands_n=N, compute_dtype=torch.float64)
+                _rows_vs_float64_kernels(p64, X, t, thr, 0.2, "band walk %d x %d, both outputs" % (N, C))
+                _rows_vs_float64_kernels(p64, X, ts, thrs, 0.2, "band walk %d x %d, tonality, then threshold" % (N, C))
+
+
+@pytest.mark.parametrize("N", FULL_ROW_SIZES)
+@pytest.mark.parametrize("C", [1, 2, 3])
+def test_masking_model_run_form_rows_past_the_end(N, C, monkeypatch):
+    """k_psy_runs at the row loader's edges, the shapes test_masking_model_band_walk_at_every_granule_count gives the band
+    walk: filters_n 256 / 512 (4 / 2 rows per wave at a time, frames that fill their registers), three clips of five frames
+    -- rows past the end in the last group of some wave, the half-empty last pair of three mono clips and of three channels
+    (strided pairs: AC_PSY_NOTEAM=1).  Tonality and threshold in one launch (a rectangular window keeps the encode of mono and
+    stereo un-fused at these sizes) and the threshold from a given tonality, against the float64 kernels at TOL / tonality_err."""
+    monkeypatch.setenv("AC_PSY_NOTEAM", "1")
+    B, K, drown = 3, 4, 0.2
+    codec = audiocodec_amd.AudioCodec(48000, N, window_type="rect")
+    assert codec.psy.tier() == 1 and not codec.psy.is_fast() and codec.encode_launches(C) == 2
+    g = torch.Generator(device="cuda").manual_seed(N + C)
+    x = torch.empty(B, K * N, C, device="cuda").uniform_(-1, 1, generator=g)
+    x *= torch.empty(B, 1, C, device="cuda").uniform_(1e-3, 1, generator=g)
+    X, t, thr = codec.encode(x, drown)
+    assert X.shape == (B, K + 1, N, C) and torch.equal(X, codec.mdct.transform(x))
+    p64 = audiocodec_amd.PsychoacousticModel(48000, filter_bands_n=N, compute_dtype=torch.float64)
+    _rows_vs_float64_kernels(p64, X, t, thr, drown, "run form %d x %d, both outputs" % (N, C))
+    ts = codec.psy.tonality(X)
+    thrs = codec.psy.global_masking_threshold(X, ts, drown)
+    _rows_vs_float64_kernels(p64, X, ts, thrs, drown, "run form %d x %d, tonality, then threshold" % (N, C))
 
 
 def test_wave_level_kernels_on_more_than_two_float32_channels(tmp_path):

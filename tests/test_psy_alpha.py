@@ -29,10 +29,10 @@ Worst values measured on the MI355X over this module, at alpha 0.3 / 0.8 / 1.0 (
 That the module bites (scratch builds of the library, this module run against each): with 1 / alpha of the wave-level
 filler (ac_fast_psy_dev.h:317) fixed at 1 / 0.6 -- bit for bit the product at alpha 0.6, so no older test can tell -- 43 of
 the 109 cases fail: all of test_wave_level_model, test_wave_level_encode_stream_and_duplex and test_fast_backward, and the
-1024 cases of test_two_models; with alpha and 1 / alpha swapped in runs_params (ac_psy_mid.hip:866) 28 fail, every case
+1024 cases of test_two_models; with alpha and 1 / alpha swapped in runs_params (ac_psy_mid_plan.hip) 28 fail, every case
 at alpha 0.3 and 0.8 of test_run_structured_model and test_fused_encode_beside_1024, the 960 cases of test_two_models and
 the three-channel cases at 1024 / 2048, and none at 1.0, where the swap is the identity; with the same swap in mid_params
-(:665) test_band_walk fails and nothing else.
+(same file) test_band_walk fails and nothing else.
 """
 
 import functools
@@ -207,7 +207,7 @@ def test_wave_level_encode_stream_and_duplex_at_other_alpha(N, C, alpha):
             _hold_encode(Xd, td, thrd, drown, model, alpha, bar, "duplex " + spreading)
 
 
-# ---- the run-structured model (ac_psy_runs_dev.h, parameters: runs_params, ac_psy_mid.hip:866) ---------------------------
+# ---- the run-structured model (ac_psy_runs_dev.h, parameters: runs_params, ac_psy_mid_plan.hip) ---------------------------
 RUNS = [(48000, 120, 64), (44100, 256, 48), (48000, 512, 64), (48000, 960, 64), (48000, 1920, 64), (48000, 4096, 64)]
 
 
@@ -216,7 +216,7 @@ RUNS = [(48000, 120, 64), (44100, 256, 48), (48000, 512, 64), (48000, 960, 64), 
 def test_run_structured_model_at_other_alpha(sr, N, M, alpha, monkeypatch):
     """k_psy_runs / k_psy_runs_c: the run-structured model, which evaluates T in the log domain,
     exp2(inv_alpha max(log2 acc - alpha O log2(10) / 10, log2 eps)) -- other arithmetic than every other path, with the
-    parameters of runs_params (ac_psy_mid.hip:866).  The form the build compiles is band_tail16 (ac_psy_runs_dev.h:422-453);
+    parameters of runs_params (ac_psy_mid_plan.hip).  The form the build compiles is band_tail16 (ac_psy_runs_dev.h:422-453);
     band_tail4 (:320-338) is compiled only under -DAC_SPREAD_4X4X4, which no build of the library sets, so no test reaches
     it.  One size per granule-register class (1 / 2 / 4 / 8 / 16 / 32 registers per lane: 120, 256 at 44.1 kHz with 48
     bands, 512, 960, 1920, 4096): mono and stereo, and three and six channels once as strided pairs (AC_PSY_NOTEAM=1) and,
@@ -239,9 +239,9 @@ def test_run_structured_model_at_other_alpha(sr, N, M, alpha, monkeypatch):
     monkeypatch.delenv("AC_PSY_TEAM_ALWAYS", raising=False)
 
 
-# ---- the band walk (ac_psy_mid_dev.h:237-248, parameters: mid_params, ac_psy_mid.hip:665) -------------------------------
+# ---- the band walk (ac_psy_mid_dev.h:237-248, parameters: mid_params, ac_psy_mid_plan.hip) -------------------------------
 def test_band_walk_at_other_alpha(tmp_path):
-    """k_psy_mid (ac_psy_mid_dev.h:237-248 with the parameters of mid_params, ac_psy_mid.hip:665), reached only with
+    """k_psy_mid (ac_psy_mid_dev.h:237-248 with the parameters of mid_params, ac_psy_mid_plan.hip), reached only with
     AC_NO_RUNS=1 (read once per process): one fresh child with AC_NO_RUNS=1 and AC_LDS_WAVE_NOFUSE=1 runs filter_bands_n 120 /
     480 / 1920 in stereo, three channels and mono (an odd batch) at the three alphas -- the un-fused encode() (tonality and
     threshold in one pass) and the stand-alone calls; what it computed comes back in an .npz file and is held to the
