@@ -20,6 +20,8 @@ AC_PACKED = 16   # spectrum-side format of ac_stream_encode_typed / ac_stream_in
 AC_IN_PCM16 = 32   # x is int16 PCM: flag of ac_encode_fused_ex beside AC_EMIT_CODES / AC_EMIT_PACKED, and of
                    # ac_stream_encode_typed's dtype beside AC_PACKED
 AC_IN_PACKED = 64  # x is one ac_packed_rows: flag of ac_encode_fused_ex beside AC_EMIT_PACKED alone (transrating)
+AC_EMIT_REDUNDANT = 256   # beside AC_IN_PACKED | AC_EMIT_PACKED: out0 is one ac_protected_out (protected slots)
+AC_CONCEAL_REDUNDANT = 256   # in ac_conceal's max_age: the struct is an ac_conceal_redundant (lost rows recovered)
 AC_CONCEAL = 128   # beside AC_PACKED in ac_stream_inverse_typed's dtype: X_chunk is one ac_stream_packed_lost_in
 AC_PACK_ROWS_MAX_BITS = 16384 # the largest row budget AC_EMIT_PACKED serves in one launch (the header's macro)
 AC_CONCEAL_FADE = 4       # scale-factor units a concealed row loses per frame of age (the header's macro)
@@ -123,6 +125,7 @@ PROTOTYPES = {
     "ac_encode_packed_launches_pcm16": (c_int, [c_void_p, c_void_p, c_int]),
     "ac_stream_packed_launches_pcm16": (c_int, [c_void_p, c_void_p]),
     "ac_transrate_launches": (c_int, [c_void_p, c_int]),
+    "ac_protect_launches": (c_int, [c_void_p, c_int, c_int]),
     "ac_pack_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ac_pack_index": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ac_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
@@ -144,6 +147,17 @@ class PackedRows(ctypes.Structure):
 class Conceal(ctypes.Structure):
     """``ac_conceal``: what ``ac_decode_quantized`` takes for ``scratch`` when ``sf`` is NULL (lost rows concealed)."""
     _fields_ = [("lost", c_void_p), ("max_age", ctypes.c_int32)]
+
+
+class ConcealRedundant(ctypes.Structure):
+    """``ac_conceal_redundant``: ``ac_conceal`` with ``AC_CONCEAL_REDUNDANT`` in ``max_age``, then where the copies lie."""
+    _fields_ = [("lost", c_void_p), ("max_age", ctypes.c_int32), ("redundant_at", ctypes.c_int64)]
+
+
+class ProtectedOut(ctypes.Structure):
+    """``ac_protected_out``: what ``ac_encode_fused_ex`` takes for ``out0`` under ``AC_EMIT_REDUNDANT``."""
+    _fields_ = [("data", c_void_p), ("row_bytes", ctypes.c_int64), ("fits", c_void_p), ("red_bits", ctypes.c_int32),
+                ("red_fits", c_void_p), ("offset", c_void_p), ("red_offset", c_void_p)]
 
 
 class PackedOut(ctypes.Structure):

@@ -53,6 +53,7 @@ class AudioCodec:
         self.filters_n = int(filters_n)
         self.compute_dtype = self.mdct.compute_dtype
         self.row_bits = None      # the row budget of a codec made by with_row_budget() / with_bitrate()
+        self._red_codecs = {}     # protect_packed_rows' composition: with_row_budget(red_bits), kept per red_bits
         self._lib = _lib.load()
 
     def with_row_budget(self, row_bits, min_offset=0):
@@ -65,6 +66,7 @@ class AudioCodec:
         new = copy.copy(self)
         new.psy = self.psy.with_row_budget(row_bits, min_offset)
         new.row_bits = int(row_bits)
+        new._red_codecs = {}      # its own: a dict shared with the copy would hold the copy in a reference cycle
         return new
 
     def with_bitrate(self, bits_per_second, min_offset=0):
@@ -459,6 +461,101 @@ class AudioCodec:
                                          _host.stream_ptr(dev)))
         return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
 
+    # ---- protected rows: a redundant copy of the frame before in every slot (extension) ---
+    def _check_red_bits(self, red_bits, what):
+        if self.row_bits is None:
+            raise ValueError("%s needs a codec with a row budget: make one with with_bitrate() or with_row_budget()" % what)
+        if isinstance(red_bits, bool) or not isinstance(red_bits, (int, np.integer)):
+            raise TypeError("red_bits must be an int, got %s" % type(red_bits).__name__)
+        if red_bits < 5 * self.psy.bark_bands_n:
+            raise ValueError("red_bits (%d) below 5 * bark_bands_n = %d, the length of a row that stores no band"
+                             % (red_bits, 5 * self.psy.bark_bands_n))
+        return int(red_bits)
+
+    def _redundant_codec(self, red_bits):
+        """``with_row_budget(red_bits)``, kept: its plan is created once (creating one waits for the device).  The kept codec
+        holds no reference back to this one, so both are freed -- and their plans destroyed -- when the last reference goes,
+        never later by the garbage collector (a plan destroyed in the middle of another call's graph capture ends it)."""
+        if red_bits not in self._red_codecs:
+            self._red_codecs[red_bits] = self.with_row_budget(red_bits)
+        return self._red_codecs[red_bits]
+
+    def protected_slot_bytes(self, red_bits):
+        """Bytes of a slot of :meth:`protect_packed_rows`: :attr:`row_bytes` + ceil(red_bits / 32) * 4."""
+        red_bits = self._check_red_bits(red_bits, "protected_slot_bytes")
+        return self.row_bytes + (red_bits + 31) // 32 * 4
+
+    def protect_packed_rows_launches(self, channels_n=2, device=None, *, red_bits):
+        """Library launches :meth:`protect_packed_rows` takes for rows of ``channels_n`` channels (``ac_protect_launches``):
+        1 = one kernel reads each row once and packs it at both budgets (where :meth:`transrate_packed_rows_launches` is 1
+        and ``red_bits`` is at most ``_lib.AC_PACK_ROWS_MAX_BITS``), else those of the two :meth:`transrate_packed_rows`
+        calls of the composition (everywhere while ``AC_PROTECT_NOFUSE=1`` is set: read per call).  0 on a codec without
+        a row budget."""
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.row_bits is None:
+            return 0
+        return int(self._lib.ac_protect_launches(self.psy._plan(dev), int(channels_n), self._check_red_bits(red_bits, "")))
+
+    def protect_packed_rows(self, data, index, red_bits, return_offset=False):
+        """On a codec made by :meth:`with_bitrate` / :meth:`with_row_budget`: :meth:`transrate_packed_rows` into slots that
+        also carry a copy of the frame before at the budget ``red_bits`` (in-band redundancy).  data
+        uint8 [nbytes], index int64 [B, F, C] (any row starts) -> (data' uint8 [B*F*C*slot_bytes], index' int64 [B, F, C],
+        fits bool [B, F, C], red_fits bool [B, F, C]), then offset and red_offset int16 [B, F, C] with
+        ``return_offset=True``; ``slot_bytes`` = :meth:`protected_slot_bytes` and ``index'[b, f, c]`` = the slot's start.
+
+        The first :attr:`row_bytes` bytes of slot (b, f, c) are the slot :meth:`transrate_packed_rows` writes for the row,
+        with its ``fits`` and ``offset``.  The rest is, for f >= 1, the slot ``with_row_budget(red_bits)`` writes for the
+        *input* row (b, f-1, c) -- the marked row where even offset 254 does not fit, ``red_fits`` False -- and zero bytes
+        for f = 0, ``red_fits`` True, ``red_offset`` 0.  ``index'`` points at the primary rows, so every reader of packed
+        rows reads ``(data', index')`` as it is; ``decode_packed(..., lost=, redundant_at=row_bytes)`` recovers a lost row
+        from the next slot.  One launch where :meth:`protect_packed_rows_launches` is 1, else the composition: the same
+        bytes.  Never synchronises with the device, only enqueues on the current stream, and can be captured in a graph."""
+        _host.require_float32(self.compute_dtype, "protect_packed_rows")
+        red_bits = self._check_red_bits(red_bits, "protect_packed_rows")
+        data = self.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
+        index = self.psy._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
+        B, F, C = index.shape
+        dev, rb = data.device, self.row_bytes
+        sb = self.protected_slot_bytes(red_bits)
+        rows = B * F * C
+        index_out = (torch.arange(rows, dtype=torch.int64, device=dev) * sb).view(B, F, C)
+        if rows == 0:
+            flags = tuple(torch.empty((B, F, C), dtype=torch.bool, device=dev) for _ in range(2))
+            offs = tuple(torch.empty((B, F, C), dtype=torch.int16, device=dev) for _ in range(2)) if return_offset else ()
+            return (torch.empty((0,), dtype=torch.uint8, device=dev), index_out) + flags + offs
+        psy = self.psy._plan(dev)
+        if self._lib.ac_protect_launches(psy, C, red_bits) == 1:
+            out_data = torch.empty((rows * sb,), dtype=torch.uint8, device=dev)
+            fits = torch.empty((B, F, C), dtype=torch.bool, device=dev)
+            red_fits = torch.empty((B, F, C), dtype=torch.bool, device=dev)
+            offset = torch.empty((B, F, C), dtype=torch.int16, device=dev) if return_offset else None
+            red_offset = torch.empty((B, F, C), dtype=torch.int16, device=dev) if return_offset else None
+            src = _lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr())
+            dst = _lib.ProtectedOut(out_data.data_ptr(), rb, fits.data_ptr(), red_bits, red_fits.data_ptr(),
+                                    offset.data_ptr() if return_offset else None,
+                                    red_offset.data_ptr() if return_offset else None)
+            with _host.on_device(dev):
+                _lib.check(self._lib.ac_encode_fused_ex(
+                    self.mdct._plan(dev), psy, ctypes.addressof(src), None, None, None, 0.0,
+                    _lib.AC_IN_PACKED | _lib.AC_EMIT_PACKED | _lib.AC_EMIT_REDUNDANT, ctypes.addressof(dst), None, 0, B, F - 1,
+                    C, _host.stream_ptr(dev)))
+            out = (out_data, index_out, fits, red_fits)
+            return out + (offset, red_offset) if return_offset else out
+        # the composition: the rows transrated at both budgets, then copied into the two parts of every slot
+        prim = self.transrate_packed_rows(data, index, True)
+        red = self._redundant_codec(red_bits).transrate_packed_rows(data, index, True)
+        slots = torch.zeros((B, F, C, sb), dtype=torch.uint8, device=dev)
+        slots[..., :rb] = prim[0].view(B, F, C, rb)
+        slots[:, 1:, :, rb:] = red[0].view(B, F, C, sb - rb)[:, :-1]
+        red_fits = torch.ones((B, F, C), dtype=torch.bool, device=dev)
+        red_fits[:, 1:] = red[2][:, :-1]
+        out = (slots.view(-1), index_out, prim[2], red_fits)
+        if return_offset:
+            red_offset = torch.zeros((B, F, C), dtype=torch.int16, device=dev)
+            red_offset[:, 1:] = red[3][:, :-1]
+            out += (prim[3], red_offset)
+        return out
+
     # ---- rate control per clip (extension; DESIGN.md section 8d) ------------------------------------------------
     def clip_bits_for_bitrate(self, bits_per_second, frames_n, channels_n):
         """The clip budget of a per-channel bitrate: frames_n * channels_n rows of :meth:`row_bits_for_bitrate` bits each,
@@ -495,7 +592,7 @@ class AudioCodec:
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         return int(self._lib.ac_decode_packed_launches(self.mdct._plan(dev), self.psy._plan(dev), int(channels_n)))
 
-    def decode_packed(self, data, index, pcm16=False, *, lost=None, max_age=8):
+    def decode_packed(self, data, index, pcm16=False, *, lost=None, max_age=8, redundant_at=None):
         """data uint8 [nbytes], index int64 [B, K', C] -> x [B, (K'+1)*N, C] (``torch.int16`` with ``pcm16=True``);
         bit-equal to ``decode_quantized(*psy.unpack(data, index), pcm16)``, that is to ``decode_quantized`` on the codes
         that were packed.  One launch that reads the bitstream in the synthesis -- no codes or scale factors are
@@ -509,10 +606,20 @@ class AudioCodec:
         without such a source is silence, so ``max_age=0`` is zero-filling.  Sources are looked for in this call's
         ``index`` only.  Bit-equal to :meth:`PsychoacousticModel.conceal_plan`, ``unpack`` at its row starts,
         :meth:`PsychoacousticModel.conceal_fade` and :meth:`decode_quantized`, which is what runs where
-        :meth:`decode_packed_launches` is not 1; one launch where it is.  Only enqueues on the current stream."""
+        :meth:`decode_packed_launches` is not 1; one launch where it is.  Only enqueues on the current stream.
+
+        ``redundant_at`` (with ``lost``; an int in [1, 2^31)) recovers before it conceals: a lost row
+        whose successor arrived is read from ``index[b, f+1, c] + redundant_at`` with no fade -- on the slots of
+        :meth:`protect_packed_rows` with ``redundant_at=row_bytes``, the low-bitrate copy the next slot carries.  The decoder
+        reads whatever lies there; a recovered row is no source of concealment.  The same composition with
+        ``conceal_plan(..., redundant_at=)``, and still one launch where :meth:`decode_packed_launches` is 1."""
         _host.require_float32(self.compute_dtype, "decode_packed")
+        if redundant_at is not None:
+            if lost is None:
+                raise ValueError("redundant_at without lost: a row is recovered only where lost marks it")
+            redundant_at = self.psy._check_redundant_at(redundant_at)
         if lost is not None:
-            return self._decode_packed_concealed(data, index, pcm16, lost, max_age)
+            return self._decode_packed_concealed(data, index, pcm16, lost, max_age, redundant_at)
         if (isinstance(data, torch.Tensor) and isinstance(index, torch.Tensor) and data.is_cuda and index.dim() == 3
                 and index.shape[1] >= 1 and self.decode_packed_launches(index.shape[2], data.device) == 1):
             data = self.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
@@ -530,7 +637,7 @@ class AudioCodec:
         codes, sf = self.psy.unpack(data, index)
         return self.decode_quantized(codes, sf, pcm16)
 
-    def _decode_packed_concealed(self, data, index, pcm16, lost, max_age):
+    def _decode_packed_concealed(self, data, index, pcm16, lost, max_age, redundant_at=None):
         """:meth:`decode_packed` with ``lost`` given: the concealing kernel where packed rows are decoded in one launch, the
         composition elsewhere."""
         max_age = self.psy._check_max_age(max_age)
@@ -542,14 +649,17 @@ class AudioCodec:
         if B >= 1 and Kp >= 1 and C >= 1 and self.decode_packed_launches(C, dev) == 1:
             x = torch.empty((B, (Kp + 1) * self.filters_n, C), dtype=torch.int16 if pcm16 else torch.float32, device=dev)
             rows = _lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr())
-            conceal = _lib.Conceal(lost.data_ptr(), max_age)
+            if redundant_at is None:
+                conceal = _lib.Conceal(lost.data_ptr(), max_age)
+            else:
+                conceal = _lib.ConcealRedundant(lost.data_ptr(), max_age | _lib.AC_CONCEAL_REDUNDANT, redundant_at)
             with _host.on_device(dev):
                 _lib.check(self._lib.ac_decode_quantized(
                     self.mdct._plan(dev), self.psy._plan(dev), ctypes.addressof(rows), None,
                     None if pcm16 else _host.ptr(x), _host.ptr(x) if pcm16 else None, ctypes.addressof(conceal), B, Kp, C,
                     _host.stream_ptr(dev)))
             return x
-        src_index, age = self.psy.conceal_plan(index, lost, data.numel(), max_age)
+        src_index, age = self.psy.conceal_plan(index, lost, data.numel(), max_age, redundant_at)
         codes, sf = self.psy.unpack(data, src_index)
         return self.decode_quantized(codes, self.psy.conceal_fade(sf, age), pcm16)
 

@@ -94,6 +94,11 @@ static bool transrate_fuses(const ac_psy_plan* psy) {
   if (env_is_1("AC_TRANSRATE_NOFUSE")) return false;
   return !g_force_generic && transrate_serves(psy);
 }
+// whether packed rows are protected in one launch (k_protect_p); AC_PROTECT_NOFUSE=1: as above
+static bool protect_fuses(const ac_psy_plan* psy, int red_bits) {
+  if (env_is_1("AC_PROTECT_NOFUSE")) return false;
+  return transrate_fuses(psy) && protect_serves(psy, red_bits);
+}
 
 }  // namespace ac
 
@@ -335,11 +340,62 @@ static int transrate_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* ps
                           (long long)B * (K + 1) * C, (hipStream_t)stream);
 }
 
+int ac_protect_launches(const ac_psy_plan* psy, int C, int red_bits) {
+  if (!psy || C < 1 || !psy->row_bits || red_bits < 5 * psy->M) return 0;
+  if (protect_fuses(psy, red_bits)) return 1;
+  // the composition: a transrate at each budget (the copies into the slots are the caller's)
+  const bool one = transrate_fuses(psy);
+  return (one ? 1 : 3) + (one && red_bits <= kPackRowsMaxBits ? 1 : 3);
+}
+
+// ac_encode_fused_ex with AC_IN_PACKED | AC_EMIT_PACKED | AC_EMIT_REDUNDANT: rows [B,K+1,C] of `in` to the protected slots of
+// `out`
+static int protect_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const ac_packed_rows* in, const float* X,
+                               const float* t, const float* thr, const ac_protected_out* out, const void* out1, int B, int K,
+                               int C, void* stream) {
+  int st = check_plan_pair(mdct, psy);
+  if (!st) st = check_dims(B, K, C);
+  if (!st) st = check_quant(psy, B, K + 1, C);
+  if (st) return st;
+  AC_REQUIRE(psy->row_bits != 0, "AC_EMIT_REDUNDANT needs a plan with a row budget (ac_psy_plan_with_row_budget)");
+  AC_REQUIRE(X == nullptr && t == nullptr && thr == nullptr && out1 == nullptr,
+             "AC_EMIT_REDUNDANT writes no X, t or thr and takes no out1: they must be NULL");
+  AC_REQUIRE(in != nullptr, "AC_EMIT_REDUNDANT without its ac_packed_rows (x)");
+  AC_REQUIRE(out != nullptr, "AC_EMIT_REDUNDANT without its ac_protected_out (out0)");
+  const ac_packed_rows rows = *in;
+  const ac_protected_out po = *out;
+  AC_REQUIRE(po.row_bytes == plan_row_bytes(psy), "row_bytes (%lld) is not the plan's ceil(%d / 32) * 4 = %lld",
+             (long long)po.row_bytes, psy->row_bits, (long long)plan_row_bytes(psy));
+  AC_REQUIRE(po.red_bits >= 5 * psy->M, "red_bits (%d) below 5 * bark_bands_n = %d, the length of a row that stores no band",
+             (int)po.red_bits, 5 * psy->M);
+  AC_REQUIRE(rows.nbytes >= 0, "negative nbytes (%lld)", (long long)rows.nbytes);
+  if (B == 0 || C == 0) return AC_OK;
+  if (!protect_fuses(psy, po.red_bits)) {
+    set_error("AC_EMIT_REDUNDANT: no kernel protects packed rows in one launch for filters_n = %d, bark_bands_n = %d, row budget "
+              "%d, redundant budget %d here (ac_protect_launches() != 1): use the composition -- the AC_IN_PACKED | AC_EMIT_PACKED "
+              "call at each budget, then copies into the two parts of every slot of zero-filled data", psy->N, psy->M,
+              psy->row_bits, (int)po.red_bits);
+    return AC_EUNSUPPORTED;
+  }
+  st = check_packed_rows(rows, true, po.data != nullptr && po.fits != nullptr && po.red_fits != nullptr);
+  if (st) return st;
+  AC_REQUIRE_ALIGNED(po.data, po.offset, po.red_offset);
+  DeviceGuard guard(psy->device);
+  return launch_protect(psy, rows.data, rows.nbytes, rows.index, po.data, po.row_bytes, po.red_bits, po.fits, po.red_fits, po.offset,
+                        po.red_offset, B, K + 1, C, (hipStream_t)stream);
+}
+
 int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
                        float drown, int flags, void* noisy_v, void* db_norm_v, uint64_t seed, int B, int K, int C,
                        void* stream) {
-  AC_REQUIRE((flags & ~(AC_EMIT_NOISY | AC_EMIT_DB_NORM | AC_EMIT_CODES | AC_EMIT_PACKED | AC_IN_PCM16 | AC_IN_PACKED)) == 0,
-             "unknown flags %#x", flags);
+  AC_REQUIRE((flags & ~(AC_EMIT_NOISY | AC_EMIT_DB_NORM | AC_EMIT_CODES | AC_EMIT_PACKED | AC_IN_PCM16 | AC_IN_PACKED |
+                        AC_EMIT_REDUNDANT)) == 0, "unknown flags %#x", flags);
+  if (flags & AC_EMIT_REDUNDANT) {
+    AC_REQUIRE(flags == (AC_IN_PACKED | AC_EMIT_PACKED | AC_EMIT_REDUNDANT),
+               "AC_EMIT_REDUNDANT goes with AC_IN_PACKED | AC_EMIT_PACKED alone (got %#x): packed rows are protected", flags);
+    return protect_packed_rows(mdct, psy, reinterpret_cast<const ac_packed_rows*>(x), X, t, thr,
+                               static_cast<const ac_protected_out*>(noisy_v), db_norm_v, B, K, C, stream);
+  }
   if (flags & AC_IN_PACKED) {
     AC_REQUIRE(flags == (AC_IN_PACKED | AC_EMIT_PACKED),
                "AC_IN_PACKED goes with AC_EMIT_PACKED alone (got %#x): packed rows are transrated to packed rows", flags);

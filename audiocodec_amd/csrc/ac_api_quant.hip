@@ -170,14 +170,25 @@ int ac_decode_quantized(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const 
     // scratch addresses one ac_conceal: rows that did not arrive are concealed
     const uint8_t* lost = nullptr;
     int max_age = 0;
+    int64_t redundant_at = 0;   // nonzero: a lost row whose successor arrived is recovered
     if (scratch != nullptr) {
       const ac_conceal cl = *reinterpret_cast<const ac_conceal*>(scratch);
-      AC_REQUIRE(cl.max_age >= 0 && cl.max_age <= AC_CONCEAL_MAX_AGE, "max_age (%d) outside [0, %d]", (int)cl.max_age,
-                 AC_CONCEAL_MAX_AGE);
-      lost = cl.lost;
       max_age = cl.max_age;
+      // AC_CONCEAL_REDUNDANT in a max_age that is not negative: scratch addresses the longer ac_conceal_redundant
+      if (max_age >= 0 && (max_age & AC_CONCEAL_REDUNDANT)) {
+        redundant_at = reinterpret_cast<const ac_conceal_redundant*>(scratch)->redundant_at;
+        max_age &= ~AC_CONCEAL_REDUNDANT;
+        AC_REQUIRE(redundant_at >= 1 && redundant_at <= 2147483647ll, "redundant_at (%lld) outside [1, 2^31)",
+                   (long long)redundant_at);
+        AC_REQUIRE(cl.lost != nullptr, "AC_CONCEAL_REDUNDANT without lost");
+      }
+      AC_REQUIRE(max_age >= 0 && max_age <= AC_CONCEAL_MAX_AGE, "max_age (%d) outside [0, %d]", max_age, AC_CONCEAL_MAX_AGE);
+      lost = cl.lost;
     }
     DeviceGuard guard(mdct->device);
+    if (Kp >= 1 && lost != nullptr && redundant_at != 0)
+      return launch_inv_fast_packed_recover(mdct, psy, rows.data, rows.nbytes, rows.index, lost, max_age, redundant_at, out,
+                                            pcm16 != nullptr, B, Kp, C, (hipStream_t)stream);
     if (Kp >= 1 && lost != nullptr)
       return launch_inv_fast_packed_conceal(mdct, psy, rows.data, rows.nbytes, rows.index, lost, max_age, out, pcm16 != nullptr,
                                             B, Kp, C, (hipStream_t)stream);

@@ -26,6 +26,11 @@
 // lane that looks at a frame before the chunk finds that row there, the row is read from the state buffer -- a second base
 // the row's loads select with a wave-uniform flag -- and the wave that owns a signal's last strip leaves the new state in the
 // other half of a double buffer (carry_state_p).
+//
+// Recovery from the redundant copy (parse_strip_p<true, false, true>, k_inv_fast_plr in ac_fast_inv_plr.hip; DESIGN.md section
+// 8g): a lost row whose successor arrived is read from index[b, f+1, c] + redundant_at -- the copy the successor's slot
+// carries -- with age 0, ahead of every rule above.  Beside the look-back the row's half wave loads lost[b, f+1, c] and, with
+// it, index[b, f+1, c]: frame f + 1 is usually outside the strip and only an address, as the source of a concealed row is.
 #pragma once
 #include "ac_fast_dev.h"
 
@@ -55,6 +60,9 @@ struct ConcealState {
   uint8_t* row_out;
   int64_t row_bytes;       // B C P_CARRY_STRIDE
   int stale;               // nonzero: every gap reads as 32 (a new stream, after a reset or a chunk that did not conceal)
+};
+struct RedundRows {
+  int64_t at;              // redundant_at: bytes from a row's start to the copy of the frame before it, in [1, 2^31)
 };
 constexpr int P_CARRY_WORDS = (5 * 64 + 8 * 64 + 16 * 1024) / 32;   // 538
 constexpr int P_CARRY_STRIDE = 2176;
@@ -96,12 +104,15 @@ __device__ __forceinline__ uint32_t p_pos(uint32_t rec, uint32_t d) {
 
 // The records of the rows of frames base + slot, slot in [slot_lo, slot_hi), of the wave's two signals.  buf: the wave's FFT
 // buffer (free before the frame loop); rec: the wave's record region.  CONCEAL: the rows are looked up through cl (above);
-// STREAM: frame -1 - gap is the carried row of cs.
-template <bool CONCEAL = false, bool STREAM = false>
+// STREAM: frame -1 - gap is the carried row of cs.  REDUND: a lost row whose successor arrived is read from the successor's
+// copy of it (rd).
+template <bool CONCEAL = false, bool STREAM = false, bool REDUND = false>
 __device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0, long long b1, int c0, int c1, int Kp, int C,
                                               int base, int slot_lo, int slot_hi, bool has1, int lane, char* buf,
-                                              uint32_t* rec, const ConcealRows* cl = nullptr, const ConcealState* cs = nullptr) {
+                                              uint32_t* rec, const ConcealRows* cl = nullptr, const ConcealState* cs = nullptr,
+                                              const RedundRows* rd = nullptr) {
   static_assert(CONCEAL || !STREAM, "the carried row is a source of concealment");
+  static_assert(!REDUND || (CONCEAL && !STREAM), "recovery: the one-shot concealing form only");
   uint32_t* st = reinterpret_cast<uint32_t*>(buf);   // [P_ROWS][P_HDR_WORDS]
   uint32_t* info = rec + P_ROWS * P_M;
   const int sig = lane >> 5, k = lane & 31;          // half a wave per row: slot t, signal sig
@@ -114,6 +125,8 @@ __device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0
     int age = 0;         // (CONCEAL) frames back to the row that is read in this one's place ...
     bool muted = false;  // ... or there is none
     int64_t own = 0;     // (CONCEAL) the row's own start, loaded beside `lost`: the start of every row that arrived
+    bool recover = false;  // (REDUND) the row is lost and its successor arrived ...
+    int64_t nxt = 0;       // ... at this start
     if constexpr (CONCEAL) {
       // lane k of the row's half wave looks at frame f - k: the first one that arrived is the source
       const bool on = t >= slot_lo && t < slot_hi && (sig == 0 || has1);
@@ -121,6 +134,14 @@ __device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0
       const int c = sig ? c1 : c0;
       const int f = base + t;
       if (on && k < P_HDR_WORDS) own = pr.index[((size_t)b * (size_t)Kp + (size_t)f) * (size_t)C + (size_t)c];
+      bool succ = false;   // (REDUND) frame f + 1 of the signal exists and arrived: one byte, the same in the half wave's lanes
+      if constexpr (REDUND) {
+        if (on && f + 1 < Kp) {
+          const size_t e = ((size_t)b * (size_t)Kp + (size_t)(f + 1)) * (size_t)C + (size_t)c;
+          succ = cl->lost[e] == 0;
+          if (k < P_HDR_WORDS) nxt = pr.index[e];
+        }
+      }
       bool there;
       if constexpr (STREAM) {
         // a frame before the chunk is there exactly where the carried row sits: gap frames before frame 0 (32: nowhere)
@@ -135,6 +156,13 @@ __device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0
       const uint32_t mh = sig ? (uint32_t)(m >> 32) : (uint32_t)m;
       muted = mh == 0u;
       age = muted ? 0 : __builtin_ctz(mh);
+      if constexpr (REDUND) {   // lane 0 of the half wave looked at the row itself: bit 0 clear = lost
+        recover = succ && (mh & 1u) == 0u;
+        if (recover) {
+          age = 0;
+          muted = false;
+        }
+      }
     }
     if (t >= slot_lo && t < slot_hi && (sig == 0 || has1) && k < P_HDR_WORDS) {
       const int r = 2 * t + sig;
@@ -147,6 +175,9 @@ __device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0
         a = own;
         if (age != 0 && !carried) a = pr.index[((size_t)b * (size_t)Kp + (size_t)(base + t - age)) * (size_t)C + (size_t)c];
         if (muted) a = pr.nbytes;
+        if constexpr (REDUND) {
+          if (recover) a = (int64_t)((uint64_t)nxt + (uint64_t)rd->at);   // (wraps as the int64 sum of the definition does)
+        }
       } else {
         a = pr.index[((size_t)b * (size_t)Kp + (size_t)(base + t)) * (size_t)C + (size_t)c];
       }

@@ -366,6 +366,11 @@ int launch_inv_fast_packed(const ac_mdct_plan* p, const ac_psy_plan* psy, const 
 int launch_inv_fast_packed_conceal(const ac_mdct_plan* p, const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes,
                                    const int64_t* index, const uint8_t* lost, int max_age, void* x, bool pcm16, int B, int Kp,
                                    int C, hipStream_t s);
+// ... and a lost row whose successor arrived read from index[b,f+1,c] + redundant_at, the redundant copy of a protected slot
+// (k_inv_fast_plr, ac_fast_inv_plr.hip), where fast_inv_packed_serves(); redundant_at in [1, 2^31)
+int launch_inv_fast_packed_recover(const ac_mdct_plan* p, const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes,
+                                   const int64_t* index, const uint8_t* lost, int max_age, int64_t redundant_at, void* x,
+                                   bool pcm16, int B, int Kp, int C, hipStream_t s);
 // ... as one chunk of k frames of a stream (k_inv_fast_pls, ac_fast_inv_pls.hip): tails as launch_inv_fast_packed takes them,
 // and the concealment state -- gap [B,C] and carried rows [B,C] at conceal_state_row_bytes(1, 1) bytes each -- read from
 // gap_in / row_in (stale: every gap reads as 32, nothing is read) and written to gap_out / row_out, other buffers
@@ -450,6 +455,13 @@ int launch_requantize_budget(const ac_psy_plan* p, const int16_t* codes_in, cons
 bool transrate_serves(const ac_psy_plan* psy);
 int launch_transrate(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes, const int64_t* index, uint8_t* out,
                      int64_t row_bytes, uint8_t* fits, int16_t* offset, long long rows, hipStream_t s);
+// ... and to protected slots (k_protect_p, ac_protect.hip): slot r of out [rows (row_bytes + red_bytes)]
+// holds launch_transrate's slot of row r, then -- for f >= 1 -- its slot of row r - C at the budget red_bits (zeros at f = 0);
+// fits, red_fits [rows], offset, red_offset [rows] (or NULL).  Where transrate_serves() and red_bits in [5 M, kPackRowsMaxBits]
+bool protect_serves(const ac_psy_plan* psy, int red_bits);
+int launch_protect(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes, const int64_t* index, uint8_t* out,
+                   int64_t row_bytes, int red_bits, uint8_t* fits, uint8_t* red_fits, int16_t* offset, int16_t* red_offset, int B,
+                   int F, int C, hipStream_t s);
 // rate control per clip (ac_clip_rate.hip): one budget for the F*C rows of a clip (clip_budget [B] int64,
 // or the scalar budget where it is NULL); row_bits, clip_offset and clip_bits may be NULL; scratch of
 // clip_budget_scratch_bytes(p, B, F*C) bytes

@@ -1,0 +1,51 @@
+// Instance and launch of k_protect_p (ac_protect_dev.h): packed rows to protected slots -- the row at
+// the plan's budget, and behind it the row of the frame before at the redundant budget -- in one launch.  An object of its
+// own: k_transrate_p and the kernels whose device functions it borrows keep their registers and their text.
+#include "ac_protect_dev.h"
+
+namespace ac {
+
+// where k_transrate_p serves the plan's budget, and a wave can stage the redundant part too; any channel count
+bool protect_serves(const ac_psy_plan* psy, int red_bits) {
+  return transrate_serves(psy) && red_bits >= 5 * P_M && red_bits <= kPackRowsMaxBits;
+}
+
+int launch_protect(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes, const int64_t* index, uint8_t* out,
+                   int64_t row_bytes, int red_bits, uint8_t* fits, uint8_t* red_fits, int16_t* offset, int16_t* red_offset, int B,
+                   int F, int C, hipStream_t s) {
+  const long long rows = (long long)B * F * C;
+  if (rows <= 0) return AC_OK;
+  if (!protect_serves(psy, red_bits) || row_bytes != plan_row_bytes(psy)) {
+    set_error("internal: no protecting kernel for filters_n = %d, %d bands, row budget %d, redundant budget %d", psy->N, psy->M,
+              psy->row_bits, red_bits);
+    return AC_EUNSUPPORTED;
+  }
+  const long long groups = (rows + T_WAVES - 1) / T_WAVES;
+  if (groups > 2147483647ll) {
+    set_error("problem too large for one launch (%lld rows)", rows);
+    return AC_EINVAL;
+  }
+  ProtectArgs a;
+  a.in.data = data;
+  a.in.nbytes = nbytes;
+  a.in.index = index;
+  a.in.band32 = reinterpret_cast<const uint32_t*>(psy->d_qband);
+  a.in.off = psy->d_qoff;
+  a.data = out;
+  a.fits = fits;
+  a.red_fits = red_fits;
+  a.offset = offset;
+  a.red_offset = red_offset;
+  a.rows = rows;
+  a.F = F;
+  a.C = C;
+  a.row_bits = psy->row_bits;
+  a.red_bits = red_bits;
+  a.row_bytes = (int)row_bytes;
+  a.red_bytes = (red_bits + 31) / 32 * 4;
+  hipLaunchKernelGGL(k_protect_p, dim3((unsigned)groups), dim3(T_WAVES * 64), 0, s, a);
+  AC_HIP_CHECK(hipGetLastError());
+  return AC_OK;
+}
+
+}  // namespace ac

@@ -4,6 +4,18 @@
 #include "ac_transrate_dev.h"
 
 namespace ac {
+namespace {
+
+// grid: ceil(rows / T_WAVES) workgroups of T_WAVES waves
+__global__ __launch_bounds__(T_WAVES * 64) void k_transrate_p(TransArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[T_WAVES * T_WAVE_WORDS];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const long long r = (long long)blockIdx.x * T_WAVES + wave;
+  if (r >= a.rows) return;   // (no workgroup barrier anywhere: the waves of a workgroup share nothing)
+  transrate_row(a, r, lane, lds + wave * T_WAVE_WORDS);
+}
+
+}  // namespace
 
 // float32 plans with 1024 bins in 64 bands and a budget whose slot a wave can stage; any channel count (rows are independent)
 bool transrate_serves(const ac_psy_plan* psy) {

@@ -1,5 +1,5 @@
-// Packed rows to packed rows at a lower budget in one launch (k_transrate_p, instantiated in ac_transrate.hip; DESIGN.md
-// section 8e): filters_n = 1024 with bark_bands_n = 64, so a row has as many bands as a wave has lanes.  One wave owns one
+// Packed rows to packed rows at a lower budget in one launch (k_transrate_p, defined in ac_transrate.hip on transrate_row below;
+// DESIGN.md section 8e): filters_n = 1024 with bark_bands_n = 64, so a row has as many bands as a wave has lanes.  One wave owns one
 // row and lane j holds band j; rows are independent, so no wave waits for another and a tail wave simply exits.
 //
 // Per row, on the pieces of the two fused kernels that read and write packed rows:
@@ -182,15 +182,6 @@ __device__ __forceinline__ void transrate_row(const TransArgs& a, long long r, i
     a.out.fits[r] = fits ? 1 : 0;
     if (a.offset) a.offset[r] = (int16_t)lo;
   }
-}
-
-// grid: ceil(rows / T_WAVES) workgroups of T_WAVES waves
-__global__ __launch_bounds__(T_WAVES * 64) void k_transrate_p(TransArgs a) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[T_WAVES * T_WAVE_WORDS];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const long long r = (long long)blockIdx.x * T_WAVES + wave;
-  if (r >= a.rows) return;   // (no workgroup barrier anywhere: the waves of a workgroup share nothing)
-  transrate_row(a, r, lane, lds + wave * T_WAVE_WORDS);
 }
 
 }  // namespace

@@ -601,15 +601,29 @@ class PsychoacousticModel:
         lost = self._check_quant_tensor(lost, "lost", lost.dtype, index.shape, index.device, ndim=3)
         return lost.view(torch.uint8)
 
-    def conceal_plan(self, index, lost, nbytes, max_age=8):
+    @staticmethod
+    def _check_redundant_at(redundant_at):
+        if isinstance(redundant_at, bool) or not isinstance(redundant_at, (int, np.integer)):
+            raise TypeError("redundant_at must be an int, got %s" % type(redundant_at).__name__)
+        if not 1 <= int(redundant_at) < 2 ** 31:
+            raise ValueError("redundant_at (%d) outside [1, 2^31)" % redundant_at)
+        return int(redundant_at)
+
+    def conceal_plan(self, index, lost, nbytes, max_age=8, redundant_at=None):
         """Where each row of a stream with lost rows is read from: index int64 [B, F, C], lost uint8 / bool [B, F, C]
         (nonzero: the row did not arrive) -> (src_index int64 [B, F, C], age uint8 [B, F, C]).
 
         ``age`` is the smallest a in [0, min(max_age, f)] with ``lost[b, f-a, c] == 0`` and ``src_index`` is
         ``index[b, f-a, c]``: the last row of the same clip and channel that arrived.  Where there is none -- a run of
         lost rows longer than ``max_age``, or lost rows before the first good one -- the row is muted: ``src_index`` is
-        ``nbytes``, a row :meth:`unpack` reads as silence, and ``age`` 0.  Torch ops on the current stream."""
+        ``nbytes``, a row :meth:`unpack` reads as silence, and ``age`` 0.  Torch ops on the current stream.
+
+        ``redundant_at`` (an int in [1, 2^31)): ahead of that rule, a lost row whose successor
+        arrived -- ``f + 1 < F`` and ``lost[b, f+1, c] == 0`` -- is recovered: ``src_index`` is
+        ``index[b, f+1, c] + redundant_at``, the copy the successor's slot carries, and ``age`` 0."""
         max_age = self._check_max_age(max_age)
+        if redundant_at is not None:
+            redundant_at = self._check_redundant_at(redundant_at)
         index = self._check_quant_tensor(index, "index", torch.int64, ndim=3)
         lost = self._check_lost(lost, index)
         B, F, C = index.shape
@@ -620,6 +634,10 @@ class PsychoacousticModel:
         found = (last >= 0) & (f - last <= max_age)
         src_index = index.gather(1, last.clamp(min=0)).masked_fill(~found, int(nbytes))
         age = (f - last).masked_fill(~found, 0).to(torch.uint8)
+        if redundant_at is not None and F >= 2:
+            recovered = (lost[:, :-1] != 0) & (lost[:, 1:] == 0)
+            src_index[:, :-1] = torch.where(recovered, index[:, 1:] + redundant_at, src_index[:, :-1])
+            age[:, :-1].masked_fill_(recovered, 0)
         return src_index, age
 
     def conceal_fade(self, sf, age):

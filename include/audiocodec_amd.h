@@ -53,7 +53,9 @@ extern "C" {
                           * ac_stream_packed_launches; 16-bit PCM into the quantising encodes: AC_IN_PCM16,
                           * ac_*_launches_pcm16; rows to a lower budget without decoding: ac_quantized_rows, AC_IN_PACKED,
                           * ac_transrate_launches; lost rows concealed in a stream: AC_CONCEAL,
-                          * ac_stream_packed_lost_in); additions only, so the number stays.
+                          * ac_stream_packed_lost_in; protected rows and the decode that recovers from them:
+                          * AC_EMIT_REDUNDANT, ac_protected_out, ac_protect_launches, AC_CONCEAL_REDUNDANT,
+                          * ac_conceal_redundant); additions only, so the number stays.
                           * 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
                           * with a 5-smooth half up to 8192, float32); masking model for general band layouts up to 4096 bins.
                           * 0.1.7: only the ac_* entry points are exported; ac_stream_settle (home buffers for the streaming state);
@@ -270,9 +272,20 @@ AC_API int ac_encode_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
  *     ac_quantize_budget call.  Any other combination with the bit, or a plan without a row budget, is AC_EINVAL; a refused
  *     call writes nothing.  Served where ac_transrate_launches returns 1; AC_EUNSUPPORTED elsewhere (run the composition).
  *     The input and output buffers must not overlap.
+ *   AC_EMIT_REDUNDANT  protecting, valid only as AC_IN_PACKED | AC_EMIT_PACKED | AC_EMIT_REDUNDANT: the
+ *     transrating call above into slots that also carry a low-bitrate copy of the frame before.  x and the plans as under
+ *     AC_IN_PACKED; out0 addresses one ac_protected_out; out1, X, t and thr must be NULL.  With red_bytes =
+ *     ceil(red_bits / 32) * 4 and slot_bytes = row_bytes + red_bytes, slot r = (b (K+1) + f) C + c takes bytes
+ *     [r slot_bytes, (r + 1) slot_bytes) of data: first the row_bytes bytes the AC_IN_PACKED call writes for row (b,f,c) at
+ *     the plan's budget, with fits[r] and offset[r]; then, for f >= 1, the red_bytes bytes that call writes for the INPUT row
+ *     (b,f-1,c) at a budget of red_bits, with red_fits[r] and red_offset[r]; for f = 0, zero bytes, red_fits[r] = 1 and
+ *     red_offset[r] = 0.  Every byte of data is written.  The struct's row_bytes must be the plan's and red_bits at least
+ *     5 * bark_bands_n, else AC_EINVAL, as is any other combination with the bit; a refused call writes nothing.  Served
+ *     where ac_protect_launches returns 1; AC_EUNSUPPORTED elsewhere (run the composition).
  * out0 / out1: float* noisy, float* db_norm under AC_EMIT_NOISY / AC_EMIT_DB_NORM; int16_t* codes, int8_t* sf under
  * AC_EMIT_CODES; ac_packed_out*, NULL under AC_EMIT_PACKED (NULL or int16_t* offset with AC_IN_PACKED). */
-enum { AC_EMIT_NOISY = 1, AC_EMIT_DB_NORM = 2, AC_EMIT_CODES = 4, AC_EMIT_PACKED = 8, AC_IN_PCM16 = 32, AC_IN_PACKED = 64 };
+enum { AC_EMIT_NOISY = 1, AC_EMIT_DB_NORM = 2, AC_EMIT_CODES = 4, AC_EMIT_PACKED = 8, AC_IN_PCM16 = 32, AC_IN_PACKED = 64,
+       AC_EMIT_REDUNDANT = 256 };
 /* The largest row budget the one launch of AC_EMIT_PACKED serves: a wave stages both rows of its frame pair in the 4 KB of
  * its LDS buffer that the masking model has left, 2 KB = 16384 bits each. */
 #define AC_PACK_ROWS_MAX_BITS 16384
@@ -281,6 +294,15 @@ typedef struct ac_packed_out {
   int64_t row_bytes; /* ceil(row_bits / 32) * 4 of the plan's budget */
   uint8_t* fits;     /* [B,K+1,C] 1 = the row's codes are in its slot, 0 = the marked row (device) */
 } ac_packed_out;
+typedef struct ac_protected_out {
+  uint8_t* data;       /* [B (K+1) C (row_bytes + red_bytes)] the protected slots (device) */
+  int64_t row_bytes;   /* ceil(row_bits / 32) * 4 of the plan's budget: the primary part of a slot */
+  uint8_t* fits;       /* [B,K+1,C] of the primary part, as ac_packed_out's (device) */
+  int32_t red_bits;    /* the redundant budget, >= 5 * bark_bands_n; red_bytes = ceil(red_bits / 32) * 4 */
+  uint8_t* red_fits;   /* [B,K+1,C] of the redundant part of the slot; 1 at f = 0 (device) */
+  int16_t* offset;     /* [B,K+1,C] offsets of the primary search (device), or NULL */
+  int16_t* red_offset; /* [B,K+1,C] offsets of the redundant search, by the slot that holds the copy; 0 at f = 0; or NULL */
+} ac_protected_out;
 AC_API int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
                        float drown, int flags, void* out0, void* out1, uint64_t seed, int B, int K, int C,
                        void* stream);
@@ -306,6 +328,12 @@ AC_API int ac_encode_packed_launches_pcm16(const ac_mdct_plan* mdct, const ac_ps
  * of the composition above (also everywhere while AC_TRANSRATE_NOFUSE=1 is set in the environment: read per call).  0 for a
  * NULL plan, C < 1, or a plan without a row budget.  The bytes do not depend on it. */
 AC_API int ac_transrate_launches(const ac_psy_plan* psy, int C);
+/* Library launches of protecting rows of C channels with a redundant budget of red_bits: 1 = ac_encode_fused_ex with
+ * AC_IN_PACKED | AC_EMIT_PACKED | AC_EMIT_REDUNDANT serves it (where ac_transrate_launches returns 1 and red_bits is at most
+ * AC_PACK_ROWS_MAX_BITS), else the launches of the composition's two transrating calls, each 1 or 3 (also everywhere while
+ * AC_PROTECT_NOFUSE=1 is set in the environment: read per call).  0 for a NULL plan, C < 1, a plan without a row budget or
+ * red_bits below 5 * bark_bands_n.  The bytes do not depend on it. */
+AC_API int ac_protect_launches(const ac_psy_plan* psy, int C, int red_bits);
 
 /* 16-bit PCM at the boundary (extension; the reference takes float PCM in [-1, 1] only, mdctransformer.py:104):
  * x = pcm / 32768 on the way in; on the way out pcm = 0 if x is NaN else clamp(rint(fp32(32768 x)), -32768, 32767), rint
@@ -347,6 +375,12 @@ AC_API int ac_encode_fused_pcm16(const ac_mdct_plan* mdct, const ac_psy_plan* ps
  *   than max_age, or lost rows before the first one of a clip and channel that arrived -- the row reads as a row that
  *   starts at nbytes: silence.  Sources are looked for in this call's index only.  Still one launch; served where
  *   ac_decode_packed_launches returns 1 and AC_EUNSUPPORTED elsewhere.  Streams (ac_stream_inverse_typed) do not conceal.
+ *   Recovery: a max_age that is not negative and has AC_CONCEAL_REDUNDANT set marks the struct as the
+ *   longer ac_conceal_redundant, whose first two members are ac_conceal's; max_age is the rest of the field.  Ahead of the
+ *   rule above, a row with lost[b,f,c] != 0, f + 1 < Kp and lost[b,f+1,c] == 0 is read from index[b,f+1,c] + redundant_at
+ *   -- the redundant part of a protected slot where redundant_at is its row_bytes -- with age 0, as ac_unpack reads any
+ *   row start; it is no source of concealment itself.  redundant_at outside [1, 2^31), lost == NULL or a max_age outside
+ *   [0, AC_CONCEAL_MAX_AGE] is AC_EINVAL.  One launch, served as the form above.  Without the bit the call is the one above.
  * ac_decode_packed_launches: 1 where that form is served (float32 plans on the wave-level kernels, filters_n = 1024,
  *   bark_bands_n = 64, mono / stereo), else 1 + ac_decode_quantized_launches: ac_unpack, then ac_decode_quantized (also
  *   everywhere while AC_DECODE_PACKED_NOFUSE=1 is set in the environment: read per call).  0 for NULL or mismatched plans. */
@@ -361,6 +395,12 @@ typedef struct ac_conceal {
   const uint8_t* lost;  /* [B,Kp,C] nonzero = the row did not arrive (device); NULL: none is lost */
   int32_t max_age;      /* frames a row may be repeated over, 0 .. AC_CONCEAL_MAX_AGE; 0 = zero-filling */
 } ac_conceal;
+enum { AC_CONCEAL_REDUNDANT = 256 };   /* in ac_conceal's max_age: the struct is an ac_conceal_redundant */
+typedef struct ac_conceal_redundant {
+  const uint8_t* lost;  /* as ac_conceal's; not NULL */
+  int32_t max_age;      /* (0 .. AC_CONCEAL_MAX_AGE) | AC_CONCEAL_REDUNDANT */
+  int64_t redundant_at; /* bytes from a row's start to the copy of the frame before it, in [1, 2^31) */
+} ac_conceal_redundant;
 AC_API int ac_quantize(const ac_psy_plan* psy, const float* X, const float* thr, int16_t* codes, int8_t* sf, int B, int F,
                        int C, void* stream);
 AC_API int ac_dequantize(const ac_psy_plan* psy, const int16_t* codes, const int8_t* sf, float* X, int B, int F, int C,

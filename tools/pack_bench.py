@@ -16,12 +16,14 @@ the one launch on int16 (k_fwd_fast_qp16 / qps16), the conversion to(float32) / 
 caller did before), and the float32 one launch on a resident float32 tensor; compared byte for byte, then alternating
 (profiles/pack/pack_bench_pcm16.txt).
 python tools/pack_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7] [--round-steps 30]
-                           [--row-bits 1365] [--only-rows] [--stream] [--pcm16] [--transrate [--targets 1365 682]] [--conceal] [--conceal-stream]
+                           [--row-bits 1365] [--only-rows] [--stream] [--pcm16] [--transrate [--targets 1365 682]] [--conceal] [--conceal-stream] [--protect]
 --transrate: rows at 2730 bits transrated to each of --targets (transrate_rows(); profiles/pack/pack_bench_transrate.txt).
 --conceal: decode_packed with lost rows concealed -- none lost, and 1 % lost at random -- against decode_packed without `lost`
 (conceal_rows(); profiles/pack/pack_bench_conceal.txt).
 --conceal-stream: the same chunk by chunk on a StreamingMDCT, the last good row carried across chunks, against
-decode_packed_chunk without `lost` (conceal_stream_rows(); profiles/pack/pack_bench_conceal_stream.txt)."""
+decode_packed_chunk without `lost` (conceal_stream_rows(); profiles/pack/pack_bench_conceal_stream.txt).
+--protect [--red-bits 341]: protect_packed_rows against its composition and transrate_packed_rows alone, then decode_packed with
+redundant_at against without (protect_rows(); profiles/pack/pack_bench_protect.txt)."""
 import argparse
 import ctypes
 import os
@@ -272,6 +274,81 @@ def transrate_rows(a):
               "directly %.4f" % (R2, a.row_bits, err[0], err[1]))
 
 
+def protect_rows(a):
+    """Protected rows and the recovering decode: rows of encode_packed_rows at 2730 bits, R = 1365 and
+    R2 = --red-bits (341).  Protect: (a) protect_packed_rows in its one launch (k_protect_p); (b) its composition
+    (AC_PROTECT_NOFUSE=1, read per call); (c) transrate_packed_rows alone at R, the floor.  Recover, on the protected slots,
+    against decode_packed(lost=) without redundant_at (k_inv_fast_pl) on the same `lost`: nothing lost, 1 % lost (most lost
+    rows are recovered), and the composition (AC_DECODE_PACKED_NOFUSE=1).  Compared byte for byte first, then alternating,
+    --rounds rounds of --round-steps."""
+    B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    base = audiocodec_amd.AudioCodec(48000, N)
+    src, dst, R2 = base.with_row_budget(2730), base.with_row_budget(1365), a.red_bits
+    x = (torch.rand((B, K * N, C), device="cuda", generator=torch.Generator("cuda").manual_seed(0)) * 2 - 1)
+    data, index, _ = src.encode_packed_rows(x)
+    del x
+    print("protect: B=%d K=%d N=%d C=%d  rows=%d at 2730 bits (%.1f MB) -> R 1365, R2 %d, slot_bytes %d (%.1f MB)  launches=%d  %s"
+          % (B, K, N, C, index.numel(), data.numel() / 1e6, R2, dst.protected_slot_bytes(R2),
+             index.numel() * dst.protected_slot_bytes(R2) / 1e6, dst.protect_packed_rows_launches(C, red_bits=R2),
+             torch.cuda.get_device_name()))
+
+    def nofuse(name, fn):
+        os.environ[name] = "1"   # (read per call)
+        try:
+            return fn()
+        finally:
+            del os.environ[name]
+
+    def report(forms, ratios):
+        runs = dict((n, []) for n, _ in forms)
+        for _ in range(a.rounds):
+            for n, fn in forms:
+                runs[n].append(timed(fn, a.round_steps, 1))
+        med = []
+        for n, _ in forms:
+            v = sorted(runs[n])
+            med.append(v[len(v) // 2])
+            print("  %-44s median %.3f ms  min %.3f  max %.3f  (%d alternating rounds of %d)" % (n, med[-1], v[0], v[-1], len(v), a.round_steps))
+        print("  " + "   ".join("%s = %.3f" % (t, med[i] / med[j]) for t, i, j in ratios))
+
+    one = dst.protect_packed_rows(data, index, R2, True)
+    two = nofuse("AC_PROTECT_NOFUSE", lambda: dst.protect_packed_rows(data, index, R2, True))
+    assert all(torch.equal(g, r) for g, r in zip(one, two)), "the two forms of protect differ"
+    print("the one launch and the composition agree byte for byte; %d primary and %d redundant parts do not fit; mean offset %.2f, "
+          "mean redundant offset %.2f" % (int((~one[2]).sum()), int((~one[3]).sum()), float(one[4].float().mean()), float(one[5].float().mean())))
+    slots, sidx = one[0], one[1]
+    del one, two
+    report([("(a) protect_packed_rows, %d launch" % dst.protect_packed_rows_launches(C, red_bits=R2),
+             lambda: dst.protect_packed_rows(data, index, R2)),
+            ("(b) protect_packed_rows, composition", lambda: nofuse("AC_PROTECT_NOFUSE", lambda: dst.protect_packed_rows(data, index, R2))),
+            ("(c) transrate_packed_rows alone at R", lambda: dst.transrate_packed_rows(data, index))],
+           [("(a) / (b)", 0, 1), ("(a) / (c)", 0, 2)])
+    del data, index
+    o = dst.row_bytes
+    none = torch.zeros(sidx.shape, dtype=torch.uint8, device="cuda")
+    some = (torch.rand(sidx.shape, device="cuda", generator=torch.Generator("cuda").manual_seed(1)) < 0.01).to(torch.uint8)
+    rec = int(((some[:, :-1] != 0) & (some[:, 1:] == 0)).sum())
+    print("recover: %d rows lost (%.2f %%), %d of them recovered  max_age 8  redundant_at %d" % (int(some.sum()), 100.0 * float(some.float().mean()), rec, o))
+    v = torch.int16
+    for pcm16 in (False, True):
+        plain = dst.decode_packed(slots, sidx, pcm16)
+        assert torch.equal(dst.decode_packed(slots, sidx, pcm16, lost=none, redundant_at=o).view(v), plain.view(v)), "none lost != the plain decode"
+        got = dst.decode_packed(slots, sidx, pcm16, lost=some, max_age=8, redundant_at=o)
+        ref = nofuse("AC_DECODE_PACKED_NOFUSE", lambda: dst.decode_packed(slots, sidx, pcm16, lost=some, max_age=8, redundant_at=o))
+        assert got.dtype == ref.dtype and torch.equal(got.view(v), ref.view(v)), "the two forms of the recovering decode differ"
+        del plain, got, ref
+    print("none lost equals the plain decode; the one launch and the composition agree bit for bit (float32 and 16-bit PCM)")
+    for pcm16 in (False, True):
+        print("%s out:" % ("16-bit PCM" if pcm16 else "float32"))
+        report([("(a) lost all false, k_inv_fast_pl", lambda: dst.decode_packed(slots, sidx, pcm16, lost=none)),
+                ("(b) lost all false, redundant_at", lambda: dst.decode_packed(slots, sidx, pcm16, lost=none, redundant_at=o)),
+                ("(c) 1 % lost, k_inv_fast_pl", lambda: dst.decode_packed(slots, sidx, pcm16, lost=some)),
+                ("(d) 1 % lost, redundant_at", lambda: dst.decode_packed(slots, sidx, pcm16, lost=some, redundant_at=o)),
+                ("(e) 1 % lost, redundant_at, composition",
+                 lambda: nofuse("AC_DECODE_PACKED_NOFUSE", lambda: dst.decode_packed(slots, sidx, pcm16, lost=some, redundant_at=o)))],
+               [("(b) / (a)", 1, 0), ("(d) / (c)", 3, 2), ("(d) / (e)", 3, 4)])
+
+
 def conceal_rows(a):
     """Concealment of lost rows on the rows of encode_packed_rows at --row-bits: (a) decode_packed
     without `lost`, the yardstick; (b) with `lost` all false; (c) with 1 % of the rows lost at random, max_age 8 -- both the
@@ -395,6 +472,8 @@ def conceal_stream_rows(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--conceal-stream", action="store_true", help="only decode_packed_chunk with lost rows concealed, against without")
+    ap.add_argument("--protect", action="store_true", help="only protect_packed_rows and the recovering decode (2730 -> 1365 with --red-bits)")
+    ap.add_argument("--red-bits", type=int, default=341, help="the redundant budget of --protect (16 kbit/s)")
     ap.add_argument("--conceal", action="store_true", help="only decode_packed with lost rows concealed, against without")
     ap.add_argument("--transrate", action="store_true", help="only transrating: rows at --row-bits (default 2730 here) to --targets")
     ap.add_argument("--targets", type=int, nargs="+", default=[1365, 682], help="the target budgets of --transrate")
@@ -412,6 +491,8 @@ def main():
     ap.add_argument("--round-steps", type=int, default=30)
     a = ap.parse_args()
     B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    if a.protect:
+        return protect_rows(a)
     if a.conceal:
         return conceal_rows(a)
     if a.conceal_stream:
