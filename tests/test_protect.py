@@ -5,7 +5,8 @@ redundant_at=)`` (``ac_conceal_redundant``, k_inv_fast_plr).
 Every comparison is bit for bit.  Protect: the one launch, the composition -- ``transrate_packed_rows`` at both budgets and
 torch copies, everywhere while ``AC_PROTECT_NOFUSE=1`` is set -- and ``protect_reference.np_protect``.  Recover: the kernel,
 the composition -- ``conceal_plan(redundant_at=)``, ``unpack``, ``conceal_fade``, ``decode_quantized``, everywhere while
-``AC_DECODE_PACKED_NOFUSE=1`` is set -- and ``decode_quantized`` of the rows numpy plans and fades.
+``AC_DECODE_PACKED_NOFUSE=1`` is set -- and ``decode_quantized`` of the rows numpy plans and fades.  The 341-bit copies recovered
+from here store at most one band; test_protect_layouts.py recovers from copies that carry content, at other layouts and budgets.
 """
 
 import ctypes
