@@ -21,6 +21,7 @@ AC_IN_PCM16 = 32   # x is int16 PCM: flag of ac_encode_fused_ex beside AC_EMIT_C
                    # ac_stream_encode_typed's dtype beside AC_PACKED
 AC_IN_PACKED = 64  # x is one ac_packed_rows: flag of ac_encode_fused_ex beside AC_EMIT_PACKED alone (transrating)
 AC_EMIT_REDUNDANT = 256   # beside AC_IN_PACKED | AC_EMIT_PACKED: out0 is one ac_protected_out (protected slots)
+AC_EMIT_CARRY = 512   # beside the three flags of protecting: the rows are a chunk of a stream, out1 is one ac_protect_carry
 AC_CONCEAL_REDUNDANT = 256   # in ac_conceal's max_age: the struct is an ac_conceal_redundant (lost rows recovered)
 AC_CONCEAL = 128   # beside AC_PACKED in ac_stream_inverse_typed's dtype: X_chunk is one ac_stream_packed_lost_in
 AC_PACK_ROWS_MAX_BITS = 16384 # the largest row budget AC_EMIT_PACKED serves in one launch (the header's macro)
@@ -126,6 +127,7 @@ PROTOTYPES = {
     "ac_stream_packed_launches_pcm16": (c_int, [c_void_p, c_void_p]),
     "ac_transrate_launches": (c_int, [c_void_p, c_int]),
     "ac_protect_launches": (c_int, [c_void_p, c_int, c_int]),
+    "ac_protect_chunk_launches": (c_int, [c_void_p, c_int, c_int]),
     "ac_pack_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ac_pack_index": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ac_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
@@ -170,6 +172,12 @@ class QuantizedRows(ctypes.Structure):
     _fields_ = [("codes", c_void_p), ("sf", c_void_p)]
 
 
+class ProtectCarry(ctypes.Structure):
+    """``ac_protect_carry``: what ``ac_encode_fused_ex`` takes for ``out1`` under ``AC_EMIT_CARRY``."""
+    _fields_ = [("row_in", c_void_p), ("fits_in", c_void_p), ("offset_in", c_void_p), ("row_out", c_void_p), ("fits_out", c_void_p),
+                ("offset_out", c_void_p)]
+
+
 class StreamPackedIn(ctypes.Structure):
     """``ac_stream_packed_in``: what ``ac_stream_inverse_typed`` takes for ``X_chunk`` under ``AC_PACKED``."""
     _fields_ = [("rows", PackedRows), ("psy", c_void_p), ("pcm16", ctypes.c_int32)]
@@ -178,6 +186,12 @@ class StreamPackedIn(ctypes.Structure):
 class StreamPackedLostIn(ctypes.Structure):
     """``ac_stream_packed_lost_in``: what ``ac_stream_inverse_typed`` takes for ``X_chunk`` under ``AC_PACKED | AC_CONCEAL``."""
     _fields_ = [("inner", StreamPackedIn), ("lost", c_void_p), ("max_age", ctypes.c_int32)]
+
+
+class StreamPackedRecoverIn(ctypes.Structure):
+    """``ac_stream_packed_recover_in``: ``ac_stream_packed_lost_in`` with ``AC_CONCEAL_REDUNDANT`` in ``max_age``, then where
+    the copies lie -- a recovering chunk, one frame behind its rows."""
+    _fields_ = [("inner", StreamPackedIn), ("lost", c_void_p), ("max_age", ctypes.c_int32), ("redundant_at", ctypes.c_int64)]
 
 
 _lock = threading.Lock()

@@ -556,6 +556,13 @@ class AudioCodec:
             out += (prim[3], red_offset)
         return out
 
+    def protect_stream(self, batches_n, channels_n, red_bits, device=None):
+        """On a codec with a row budget: a :class:`ProtectStream` for ``batches_n`` clips of ``channels_n`` channels --
+        :meth:`protect_packed_rows` chunk by chunk, the copy of a chunk's last row carried into the next chunk's first
+        slots ("Streams")."""
+        _host.require_float32(self.compute_dtype, "protect_stream")
+        return ProtectStream(self, batches_n, channels_n, self._check_red_bits(red_bits, "protect_stream"), device)
+
     # ---- rate control per clip (extension; DESIGN.md section 8d) ------------------------------------------------
     def clip_bits_for_bitrate(self, bits_per_second, frames_n, channels_n):
         """The clip budget of a per-channel bitrate: frames_n * channels_n rows of :meth:`row_bits_for_bitrate` bits each,
@@ -686,6 +693,113 @@ class AudioCodec:
             _lib.check(fn(self.mdct._plan(X.device), _host.ptr(X), _host.ptr(x), B, Kp, C, _host.stream_ptr(X.device)))
 
 
+class ProtectStream:
+    """:meth:`AudioCodec.protect_packed_rows` chunk by chunk (``AudioCodec.protect_stream``; DESIGN.md section 8g, "Streams").
+
+    :meth:`protect_chunk` returns what ``protect_packed_rows`` returns for the chunk's ``k`` frames, in the same layout, but
+    the redundant part, ``red_fits`` and ``red_offset`` of frame 0 are the copy at ``red_bits`` of the previous chunk's last
+    *input* row -- on a fresh or reset stream the values of f = 0 -- and the copy of the chunk's last input row is kept for
+    the next chunk.  So for any split the chunks' slots, flags and offsets, put together along frames, are those of the
+    one-shot call on all rows, byte for byte.  The carry lives on the device, double buffered; the calls only enqueue, on
+    ``stream`` or the current stream, and calls on one object are ordered by the caller."""
+
+    def __init__(self, codec, batches_n, channels_n, red_bits, device=None):
+        if codec.row_bits is None:
+            raise ValueError("protect_stream needs a codec with a row budget (with_bitrate() / with_row_budget())")
+        self.codec, self.red_bits = codec, red_bits
+        self.B, self.C = int(batches_n), int(channels_n)
+        if self.B < 1 or self.C < 1:
+            raise ValueError("batches_n (%d) and channels_n (%d) must be positive" % (self.B, self.C))
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._red_bytes = (red_bits + 31) // 32 * 4
+        # two halves of (row, fits, offset); _cur is the half the last chunk wrote, None on a fresh stream
+        self._carry = [(torch.zeros((self.B, self.C, self._red_bytes), dtype=torch.uint8, device=self.device),
+                        torch.ones((self.B, self.C), dtype=torch.bool, device=self.device),
+                        torch.zeros((self.B, self.C), dtype=torch.int16, device=self.device)) for _ in range(2)]
+        self._cur = None
+
+    def reset(self):
+        """The next chunk's frame 0 takes the values of f = 0 again.  No device work."""
+        self._cur = None
+
+    def launches(self):
+        """Library launches of :meth:`protect_chunk` (``ac_protect_chunk_launches``): 1 where
+        ``protect_packed_rows_launches`` is 1, else those of the composition's two transrating calls (everywhere while
+        ``AC_PROTECT_NOFUSE=1`` is set: read per call)."""
+        return int(self.codec._lib.ac_protect_chunk_launches(self.codec.psy._plan(self.device), self.C, self.red_bits))
+
+    def protect_chunk(self, data, index, return_offset=False, stream=None):
+        """data uint8 [nbytes], index int64 [B, k, C] -> (data', index', fits, red_fits) and, with ``return_offset``, offset
+        and red_offset: ``protect_packed_rows``' outputs for the chunk (``index'`` the chunk's own arithmetic index), frame 0
+        taking the carried copy.  ``k = 0`` changes nothing."""
+        codec = self.codec
+        with (torch.cuda.stream(stream) if stream is not None else _host._NO_SWITCH):
+            data = codec.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
+            if data.device != self.device:
+                raise ValueError("data lives on %s but the stream's carry lives on %s" % (data.device, self.device))
+            index = codec.psy._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
+            B, k, C = index.shape
+            if (B, C) != (self.B, self.C):
+                raise ValueError("index must be [%d, k, %d], got %s" % (self.B, self.C, tuple(index.shape)))
+            dev, rb, red_bits = self.device, codec.row_bytes, self.red_bits
+            sb = codec.protected_slot_bytes(red_bits)
+            rows = B * k * C
+            index_out = (torch.arange(rows, dtype=torch.int64, device=dev) * sb).view(B, k, C)
+            if k == 0:
+                flags = tuple(torch.empty((B, k, C), dtype=torch.bool, device=dev) for _ in range(2))
+                offs = tuple(torch.empty((B, k, C), dtype=torch.int16, device=dev) for _ in range(2)) if return_offset else ()
+                return (torch.empty((0,), dtype=torch.uint8, device=dev), index_out) + flags + offs
+            src_half = None if self._cur is None else self._carry[self._cur]
+            nxt = 0 if self._cur is None else self._cur ^ 1
+            dst_half = self._carry[nxt]
+            psy = codec.psy._plan(dev)
+            if codec._lib.ac_protect_chunk_launches(psy, C, red_bits) == 1:
+                out_data = torch.empty((rows * sb,), dtype=torch.uint8, device=dev)
+                fits = torch.empty((B, k, C), dtype=torch.bool, device=dev)
+                red_fits = torch.empty((B, k, C), dtype=torch.bool, device=dev)
+                offset = torch.empty((B, k, C), dtype=torch.int16, device=dev) if return_offset else None
+                red_offset = torch.empty((B, k, C), dtype=torch.int16, device=dev) if return_offset else None
+                src = _lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr())
+                dst = _lib.ProtectedOut(out_data.data_ptr(), rb, fits.data_ptr(), red_bits, red_fits.data_ptr(),
+                                        offset.data_ptr() if return_offset else None,
+                                        red_offset.data_ptr() if return_offset else None)
+                carry = _lib.ProtectCarry(*((None, None, None) if src_half is None else [t.data_ptr() for t in src_half]),
+                                          *[t.data_ptr() for t in dst_half])
+                with _host.on_device(dev):
+                    _lib.check(codec._lib.ac_encode_fused_ex(
+                        codec.mdct._plan(dev), psy, ctypes.addressof(src), None, None, None, 0.0,
+                        _lib.AC_IN_PACKED | _lib.AC_EMIT_PACKED | _lib.AC_EMIT_REDUNDANT | _lib.AC_EMIT_CARRY,
+                        ctypes.addressof(dst), ctypes.addressof(carry), 0, B, k - 1, C,
+                        _host.stream_ptr(dev) if stream is None else ctypes.c_void_p(stream.cuda_stream)))
+                self._cur = nxt
+                out = (out_data, index_out, fits, red_fits)
+                return out + (offset, red_offset) if return_offset else out
+            # the composition: the rows transrated at both budgets, copied into the slots; frame 0 from the carry, the copy of
+            # the last row into the carry's other half
+            prim = codec.transrate_packed_rows(data, index, True)
+            red = codec._redundant_codec(red_bits).transrate_packed_rows(data, index, True)
+            red_rows = red[0].view(B, k, C, sb - rb)
+            slots = torch.zeros((B, k, C, sb), dtype=torch.uint8, device=dev)
+            slots[..., :rb] = prim[0].view(B, k, C, rb)
+            slots[:, 1:, :, rb:] = red_rows[:, :-1]
+            red_fits = torch.ones((B, k, C), dtype=torch.bool, device=dev)
+            red_fits[:, 1:] = red[2][:, :-1]
+            red_offset = torch.zeros((B, k, C), dtype=torch.int16, device=dev)
+            red_offset[:, 1:] = red[3][:, :-1]
+            if src_half is not None:
+                slots[:, 0, :, rb:] = src_half[0]
+                red_fits[:, 0] = src_half[1]
+                red_offset[:, 0] = src_half[2]
+            dst_half[0].copy_(red_rows[:, -1])
+            dst_half[1].copy_(red[2][:, -1])
+            dst_half[2].copy_(red[3][:, -1])
+            self._cur = nxt
+            out = (slots.view(-1), index_out, prim[2], red_fits)
+            return out + (prim[3], red_offset) if return_offset else out
+
+
 class StreamingMDCT:
     """Chunked analysis / synthesis with device-resident overlap state (BASELINE config 5).
 
@@ -728,6 +842,9 @@ class StreamingMDCT:
         self._handle = handle
         self._graphs = {}       # run(..., graph=True): captured calls by input buffers and arguments
         self._conceal = None    # decode_packed_chunk(lost=...) where it is composed: (carried codes, sf, gap), None = no source
+        # decode_packed_chunk(redundant_at=...) synthesises one frame behind its rows ("Streams"):
+        # _delayed from the first such chunk, _advanced from the first other call that moved the synthesis, until reset()
+        self._delayed = self._advanced = False
 
     def close(self):
         self._graphs = {}       # (the graphs hold launches that address the stream's state)
@@ -743,6 +860,7 @@ class StreamingMDCT:
 
     def reset(self):
         self._conceal = None
+        self._delayed = self._advanced = False
         with _host.on_device(self.device):
             _lib.check(self._lib.ac_stream_reset(self._handle, _host.stream_ptr(self.device)))
 
@@ -824,9 +942,16 @@ class StreamingMDCT:
         go (one stereo clip in chunks of 256 blocks: 7.9 us per chunk against 11.9).  A replay reads the CURRENT contents
         of the same input buffers and overwrites the output tensors of the first call, which are returned again."""
         _host.require_float32(self.mdct.compute_dtype, "StreamingMDCT.run (use the chunk calls for bfloat16 / float64 streams)")
+        self._not_delayed("run")
         self._conceal = None    # (the synthesis state moves on without a source for concealment)
         if graph:
-            return self._run_graph(x, blocks_per_chunk, masking, synthesis, drown)
+            out = self._run_graph(x, blocks_per_chunk, masking, synthesis, drown)
+        else:
+            out = self._run(x, blocks_per_chunk, masking, synthesis, drown)
+        self._advanced = self._advanced or bool(synthesis)   # (only once the library call has gone through)
+        return out
+
+    def _run(self, x, blocks_per_chunk, masking, synthesis, drown):
         k, N = int(blocks_per_chunk), self.mdct.filters_n
         if masking and self.psy is None:
             raise ValueError("this stream was created without a masking model (psy=...)")
@@ -925,8 +1050,21 @@ class StreamingMDCT:
         hit[0].replay()
         return hit[1]
 
+    def _not_delayed(self, what):
+        if self._delayed:
+            raise ValueError("%s on a stream that decodes recovering chunks (decode_packed_chunk(..., redundant_at=)), which "
+                             "run one frame behind their rows: flush_packed() or reset() first" % what)
+
     def inverse_chunk(self, X_chunk, out=None, stream=None):
         """X_chunk [B, k, N, C] -> x [B, k*N, C]."""
+        self._not_delayed("inverse_chunk")
+        x = self._inverse_chunk(X_chunk, out, stream)
+        if x.shape[1]:
+            self._advanced = True
+        return x
+
+    def _inverse_chunk(self, X_chunk, out, stream):
+        """:meth:`inverse_chunk` without the check of the stream's mode: also the last step of the composed recovering chunk."""
         X = self._check_chunk(X_chunk, "X_chunk", 4)
         B, k, N, C = X.shape
         if (B, C, N) != (self.B, self.C, self.mdct.filters_n):
@@ -958,7 +1096,7 @@ class StreamingMDCT:
             return None
         return (self.psy.row_budget[0] + 31) // 32 * 4
 
-    def packed_chunk_launches(self, decode=False, *, conceal=False, pcm16=False):
+    def packed_chunk_launches(self, decode=False, *, conceal=False, recover=False, pcm16=False):
         """Library launches of :meth:`encode_packed_rows_chunk` (``decode=True``: of :meth:`decode_packed_chunk`) on this
         stream (``ac_stream_packed_launches``): 1 = one launch that carries the overlap state -- filters_n = 1024, 64 bands,
         mono / stereo, a budget of at most ``_lib.AC_PACK_ROWS_MAX_BITS``, and for the encode a kernel instance that passed
@@ -967,12 +1105,15 @@ class StreamingMDCT:
         stream without a row budget.  ``pcm16=True``: of the encode on a ``torch.int16`` chunk
         (``ac_stream_packed_launches_pcm16``; its instances passed the gate with ``spreading="bf16x2_mfma"`` only).
         ``decode=True, conceal=True``: of :meth:`decode_packed_chunk` with ``lost`` given -- 1 wherever the plain decode is
-        1, else the 3 library launches of its composition."""
+        1, else the 3 library launches of its composition.  ``recover=True`` beside them: of the recovering chunk
+        (``redundant_at`` given; ``ac_stream_packed_launches(s, psy, 3)``), 1 and 3 in the same places."""
         self._packed_ready("packed_chunk_launches", False)
+        if recover and not conceal:
+            raise ValueError("recover=True is a form of the concealing decode: pass decode=True, conceal=True")
         if conceal:
             if not decode:
                 raise ValueError("conceal=True is a form of the decode: pass decode=True")
-            return int(self._lib.ac_stream_packed_launches(self._handle, self.psy._plan(self.device), 2))
+            return int(self._lib.ac_stream_packed_launches(self._handle, self.psy._plan(self.device), 3 if recover else 2))
         if pcm16 and not decode:
             return int(self._lib.ac_stream_packed_launches_pcm16(self._handle, self.psy._plan(self.device)))
         return int(self._lib.ac_stream_packed_launches(self._handle, self.psy._plan(self.device), 1 if decode else 0))
@@ -1018,7 +1159,7 @@ class StreamingMDCT:
             data, fits = _pack_rows_of_spectra(self.psy, X, thr, index, rb)
             return data, index, fits
 
-    def decode_packed_chunk(self, data, index, pcm16=False, out=None, stream=None, *, lost=None, max_age=8):
+    def decode_packed_chunk(self, data, index, pcm16=False, out=None, stream=None, *, lost=None, max_age=8, redundant_at=None):
         """data uint8 [nbytes], index int64 [B, k, C] -> x [B, k*N, C] (``torch.int16`` with ``pcm16=True``): the next k
         blocks of the signal, bit-equal to ``inverse_chunk(psy.dequantize(*psy.unpack(data, index)))`` -- with ``pcm16``
         through the store of ``AudioCodec.decode``: ``0 if NaN else clamp(rint(fp32(32768 * x)), -32768, 32767)``.
@@ -1032,9 +1173,27 @@ class StreamingMDCT:
         one-shot call on the whole signal, bit for bit; each row takes the ``max_age`` of its own call.  The carried row
         is the stream's state: :meth:`reset`, and every chunk that is decoded or inverted without ``lost``, leave no
         source behind.  One launch where ``packed_chunk_launches(decode=True, conceal=True)`` is 1, else the
-        composition with the same state kept in tensors."""
+        composition with the same state kept in tensors.
+
+        ``redundant_at`` (with ``lost``; an int in [1, 2^31), DESIGN.md section 8g, "Streams") recovers before it conceals,
+        as ``AudioCodec.decode_packed(..., redundant_at=)`` does, and for that the stream is *delayed*: the k blocks
+        returned are the frames of ``D, row 0, ..., row k-2``, where ``D`` is the deferred last row of the chunk before (on
+        a new or reset stream: a lost row with no source before it), and the chunk's last row waits for the next call.
+        So the successor of every frame is in the chunk in hand: a lost frame whose successor arrived is read from
+        ``index[b, successor, c] + redundant_at`` with no fade, every other frame as under ``lost`` alone.  However
+        ``index [B, K', C]`` is split into chunks, the outputs are blocks ``[0, K')`` of the one-shot call on
+        ``cat(index[:, :1], index)`` and ``cat(ones, lost)`` -- one lost frame in front -- bit for bit, and
+        :meth:`flush_packed` returns block ``K'``.  A stream is delayed from its first such chunk until :meth:`reset`: in
+        between :meth:`inverse_chunk`, :meth:`run` and this call without ``redundant_at`` raise ``ValueError`` and leave
+        the state alone, as does a recovering chunk on a stream whose synthesis one of those has advanced since it was
+        made or reset.  One launch where ``packed_chunk_launches(decode=True, conceal=True, recover=True)`` is 1, else
+        the composition."""
         self._packed_ready("decode_packed_chunk", False)
         N = self.mdct.filters_n
+        if redundant_at is not None:
+            if lost is None:
+                raise ValueError("redundant_at without lost: a row is recovered only where lost marks it")
+            redundant_at = self.psy._check_redundant_at(redundant_at)
         with self._on(stream):
             if lost is not None:
                 max_age = self.psy._check_max_age(max_age)
@@ -1052,23 +1211,34 @@ class StreamingMDCT:
                 return x
             dev = data.device
             psy = self.psy._plan(dev)
-            if lost is not None:
-                return self._decode_packed_chunk_concealed(data, index, lost, max_age, pcm16, x, psy, stream)
-            self._conceal = None   # (a chunk that does not conceal leaves no source; the library marks its own state)
-            if self._lib.ac_stream_packed_launches(self._handle, psy, 1) == 1:
-                rows = _lib.StreamPackedIn(_lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr()), psy.value,
-                                           1 if pcm16 else 0)
-                with _host.on_device(dev):
-                    _lib.check(self._lib.ac_stream_inverse_typed(self._handle, ctypes.addressof(rows), _host.ptr(x),
-                                                                 _lib.AC_PACKED, k, self._stream(stream)))
+            if redundant_at is not None:
+                if self._advanced:
+                    raise ValueError("redundant_at on a stream whose synthesis has advanced without it since it was made or "
+                                     "reset: a recovering chunk runs one frame behind its rows -- reset() first")
+                self._decode_packed_chunk_recovered(data, index, lost, max_age, redundant_at, pcm16, x, psy, stream)
+                self._delayed = True   # (the mode changes only once the chunk has gone through)
                 return x
-            return self._inverse_chunk_into(self.psy.dequantize(*self.psy.unpack(data, index)), x, pcm16, stream)
+            self._not_delayed("decode_packed_chunk without redundant_at")
+            if lost is not None:
+                self._decode_packed_chunk_concealed(data, index, lost, max_age, pcm16, x, psy, stream)
+            else:
+                self._conceal = None   # (a chunk that does not conceal leaves no source; the library marks its own state)
+                if self._lib.ac_stream_packed_launches(self._handle, psy, 1) == 1:
+                    rows = _lib.StreamPackedIn(_lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr()), psy.value,
+                                               1 if pcm16 else 0)
+                    with _host.on_device(dev):
+                        _lib.check(self._lib.ac_stream_inverse_typed(self._handle, ctypes.addressof(rows), _host.ptr(x),
+                                                                     _lib.AC_PACKED, k, self._stream(stream)))
+                else:
+                    self._inverse_chunk_into(self.psy.dequantize(*self.psy.unpack(data, index)), x, pcm16, stream)
+            self._advanced = True
+            return x
 
     def _inverse_chunk_into(self, X, x, pcm16, stream):
         """:meth:`inverse_chunk` of X into x, through the 16-bit PCM store where x is int16."""
         if not pcm16:
-            return self.inverse_chunk(X, out=x, stream=stream)
-        p = torch.nan_to_num(self.inverse_chunk(X, stream=stream) * 32768.0, nan=0.0)   # the float32 product
+            return self._inverse_chunk(X, x, stream)
+        p = torch.nan_to_num(self._inverse_chunk(X, None, stream) * 32768.0, nan=0.0)   # the float32 product
         x.copy_(p.round_().clamp_(-32768.0, 32767.0).to(torch.int16))                   # round: half to even
         return x
 
@@ -1116,4 +1286,71 @@ class StreamingMDCT:
         new_sf = torch.where(has.view(B, 1, 1, C), sf.gather(1, at.expand(B, 1, M, C)), row_sf)
         new_gap = torch.where(has, k - 1 - final, gap + k).clamp(max=32)
         self._conceal = (new_codes, new_sf, new_gap)   # (after inverse_chunk, which leaves no source)
+        return x
+
+    def _decode_packed_chunk_recovered(self, data, index, lost, max_age, redundant_at, pcm16, x, psy, stream):
+        """:meth:`decode_packed_chunk` with ``redundant_at`` given (checked; under the stream the work runs on): the one
+        launch where the library has it, else the composition on the same state as the concealing one keeps
+        (``self._conceal``) -- the deferred row is the carried row where the gap is 0.  Nothing here waits for the device."""
+        B, k, C = index.shape
+        dev = data.device
+        if self._lib.ac_stream_packed_launches(self._handle, psy, 3) == 1:
+            self._conceal = None   # (the state lives in the library from here on)
+            rows = _lib.StreamPackedRecoverIn(
+                _lib.StreamPackedIn(_lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr()), psy.value,
+                                    1 if pcm16 else 0), lost.data_ptr(), max_age | _lib.AC_CONCEAL_REDUNDANT, redundant_at)
+            with _host.on_device(dev):
+                _lib.check(self._lib.ac_stream_inverse_typed(self._handle, ctypes.addressof(rows), _host.ptr(x),
+                                                             _lib.AC_PACKED | _lib.AC_CONCEAL, k, self._stream(stream)))
+            return x
+        # the chunk's rows and, behind them, the copies their slots carry: the copy in row j's slot is of frame j - 1
+        codes, sf = self.psy.unpack(data, torch.cat((index, index + redundant_at), dim=1))
+        codes, red_codes, sf, red_sf = codes[:, :k], codes[:, k:], sf[:, :k], sf[:, k:]
+        state = self._conceal
+        if state is None:   # a new stream or after reset(): the deferred row did not arrive and has no source
+            state = (torch.zeros_like(codes[:, :1]), torch.zeros_like(sf[:, :1]),
+                     torch.full((B, C), 32, dtype=torch.int64, device=dev))
+        row_codes, row_sf, gap = state
+        # frames j = 0 .. k of the delayed chunk: j = 0 is D, which arrived where the gap is 0, j = f + 1 is row f; the carried
+        # row in front of the chunk's rows is frame 0 where it is D and the row gap frames before it otherwise
+        codes_ext, sf_ext = torch.cat((row_codes, codes), dim=1), torch.cat((row_sf, sf), dim=1)
+        arrived = torch.cat(((gap == 0).view(B, 1, C), lost == 0), dim=1)              # [B, k+1, C]
+        j = torch.arange(k, dtype=torch.int64, device=dev).view(1, k, 1)
+        last = j.expand(B, k, C).masked_fill(~arrived[:, :k], -1).cummax(dim=1).values   # the last frame <= j that arrived
+        recovered = ~arrived[:, :k] & arrived[:, 1:]
+        inside = (last >= 0) & (j - last <= max_age)
+        carried_age = gap.view(B, 1, C) + j
+        carried = ~inside & (gap.view(B, 1, C) <= 31) & (carried_age <= max_age)
+        muted = ~inside & ~carried & ~recovered
+        src = torch.where(inside, last, torch.zeros_like(last))                        # frame of codes_ext
+        age = torch.where(inside, j - last, carried_age).masked_fill(muted | recovered, 0).to(torch.uint8)
+        N, M = codes.shape[2], sf.shape[2]
+        got_codes = codes_ext.gather(1, src.unsqueeze(2).expand(B, k, N, C)).masked_fill(muted.unsqueeze(2), 0)
+        got_sf = sf_ext.gather(1, src.unsqueeze(2).expand(B, k, M, C)).masked_fill(muted.unsqueeze(2), 0)
+        got_codes = torch.where(recovered.unsqueeze(2), red_codes, got_codes)
+        got_sf = torch.where(recovered.unsqueeze(2), red_sf, got_sf)
+        self._inverse_chunk_into(self.psy.dequantize(got_codes, self.psy.conceal_fade(got_sf, age)), x, pcm16, stream)
+        # the state after the chunk, over its rows 0 .. k-1 whatever max_age was: as the concealing chunk leaves it
+        f = torch.arange(k, dtype=torch.int64, device=dev).view(1, k, 1)
+        final = f.expand(B, k, C).masked_fill(lost != 0, -1).max(dim=1).values          # [B, C]: the last row that arrived, or -1
+        has = final >= 0
+        at = final.clamp(min=0).view(B, 1, 1, C)
+        new_codes = torch.where(has.view(B, 1, 1, C), codes.gather(1, at.expand(B, 1, N, C)), row_codes)
+        new_sf = torch.where(has.view(B, 1, 1, C), sf.gather(1, at.expand(B, 1, M, C)), row_sf)
+        new_gap = torch.where(has, k - 1 - final, gap + k).clamp(max=32)
+        self._conceal = (new_codes, new_sf, new_gap)   # (after the synthesis, which leaves no source)
+        return x
+
+    def flush_packed(self, pcm16=False, out=None, stream=None, *, max_age=8):
+        """The last block of a delayed stream, x [B, N, C]: the frame of the deferred row, which no successor can recover
+        any more -- concealed where it was lost.  Exactly ``decode_packed_chunk`` with ``redundant_at`` on one row marked
+        lost, then :meth:`reset`: block ``K'`` of the one-shot call :meth:`decode_packed_chunk` names."""
+        self._packed_ready("flush_packed", False)
+        with self._on(stream):
+            data = torch.zeros((16,), dtype=torch.uint8, device=self.device)
+            index = torch.zeros((self.B, 1, self.C), dtype=torch.int64, device=self.device)
+            lost = torch.ones((self.B, 1, self.C), dtype=torch.uint8, device=self.device)
+        x = self.decode_packed_chunk(data, index, pcm16, out, stream, lost=lost, max_age=max_age, redundant_at=1)
+        with self._on(stream):   # (reset() enqueues on the current stream: behind the chunk)
+            self.reset()
         return x

@@ -348,18 +348,31 @@ int ac_protect_launches(const ac_psy_plan* psy, int C, int red_bits) {
   return (one ? 1 : 3) + (one && red_bits <= kPackRowsMaxBits ? 1 : 3);
 }
 
+// of one chunk of a stream (k_protect_ps): served exactly where the one-shot call is
+int ac_protect_chunk_launches(const ac_psy_plan* psy, int C, int red_bits) { return ac_protect_launches(psy, C, red_bits); }
+
 // ac_encode_fused_ex with AC_IN_PACKED | AC_EMIT_PACKED | AC_EMIT_REDUNDANT: rows [B,K+1,C] of `in` to the protected slots of
-// `out`
+// `out`; with AC_EMIT_CARRY the rows are one chunk of a stream and out1 its ac_protect_carry
 static int protect_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const ac_packed_rows* in, const float* X,
-                               const float* t, const float* thr, const ac_protected_out* out, const void* out1, int B, int K,
-                               int C, void* stream) {
+                               const float* t, const float* thr, const ac_protected_out* out, const void* out1, bool chunk,
+                               int B, int K, int C, void* stream) {
   int st = check_plan_pair(mdct, psy);
   if (!st) st = check_dims(B, K, C);
   if (!st) st = check_quant(psy, B, K + 1, C);
   if (st) return st;
   AC_REQUIRE(psy->row_bits != 0, "AC_EMIT_REDUNDANT needs a plan with a row budget (ac_psy_plan_with_row_budget)");
-  AC_REQUIRE(X == nullptr && t == nullptr && thr == nullptr && out1 == nullptr,
+  AC_REQUIRE(X == nullptr && t == nullptr && thr == nullptr && (chunk || out1 == nullptr),
              "AC_EMIT_REDUNDANT writes no X, t or thr and takes no out1: they must be NULL");
+  ac_protect_carry pc = {};
+  if (chunk) {
+    AC_REQUIRE(out1 != nullptr, "AC_EMIT_CARRY without its ac_protect_carry (out1)");
+    pc = *static_cast<const ac_protect_carry*>(out1);
+    AC_REQUIRE(pc.row_out != nullptr && pc.fits_out != nullptr && pc.offset_out != nullptr, "ac_protect_carry: a NULL output");
+    AC_REQUIRE(pc.row_in == nullptr || (pc.fits_in != nullptr && pc.offset_in != nullptr), "ac_protect_carry: row_in without fits_in, offset_in");
+    AC_REQUIRE(pc.row_in != pc.row_out && pc.fits_in != pc.fits_out && pc.offset_in != pc.offset_out,
+               "ac_protect_carry: in and out must be distinct buffers (the carry is double buffered)");
+    AC_REQUIRE_ALIGNED(pc.row_in, pc.row_out);
+  }
   AC_REQUIRE(in != nullptr, "AC_EMIT_REDUNDANT without its ac_packed_rows (x)");
   AC_REQUIRE(out != nullptr, "AC_EMIT_REDUNDANT without its ac_protected_out (out0)");
   const ac_packed_rows rows = *in;
@@ -381,6 +394,10 @@ static int protect_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy,
   if (st) return st;
   AC_REQUIRE_ALIGNED(po.data, po.offset, po.red_offset);
   DeviceGuard guard(psy->device);
+  if (chunk)
+    return launch_protect_stream(psy, rows.data, rows.nbytes, rows.index, po.data, po.row_bytes, po.red_bits, po.fits, po.red_fits,
+                                 po.offset, po.red_offset, pc.row_in, pc.fits_in, pc.offset_in, pc.row_out, pc.fits_out,
+                                 pc.offset_out, B, K + 1, C, (hipStream_t)stream);
   return launch_protect(psy, rows.data, rows.nbytes, rows.index, po.data, po.row_bytes, po.red_bits, po.fits, po.red_fits, po.offset,
                         po.red_offset, B, K + 1, C, (hipStream_t)stream);
 }
@@ -389,12 +406,13 @@ int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const f
                        float drown, int flags, void* noisy_v, void* db_norm_v, uint64_t seed, int B, int K, int C,
                        void* stream) {
   AC_REQUIRE((flags & ~(AC_EMIT_NOISY | AC_EMIT_DB_NORM | AC_EMIT_CODES | AC_EMIT_PACKED | AC_IN_PCM16 | AC_IN_PACKED |
-                        AC_EMIT_REDUNDANT)) == 0, "unknown flags %#x", flags);
-  if (flags & AC_EMIT_REDUNDANT) {
-    AC_REQUIRE(flags == (AC_IN_PACKED | AC_EMIT_PACKED | AC_EMIT_REDUNDANT),
-               "AC_EMIT_REDUNDANT goes with AC_IN_PACKED | AC_EMIT_PACKED alone (got %#x): packed rows are protected", flags);
+                        AC_EMIT_REDUNDANT | AC_EMIT_CARRY)) == 0, "unknown flags %#x", flags);
+  if (flags & (AC_EMIT_REDUNDANT | AC_EMIT_CARRY)) {
+    AC_REQUIRE((flags & ~AC_EMIT_CARRY) == (AC_IN_PACKED | AC_EMIT_PACKED | AC_EMIT_REDUNDANT),
+               "AC_EMIT_REDUNDANT goes with AC_IN_PACKED | AC_EMIT_PACKED alone, AC_EMIT_CARRY beside the three (got %#x): packed "
+               "rows are protected", flags);
     return protect_packed_rows(mdct, psy, reinterpret_cast<const ac_packed_rows*>(x), X, t, thr,
-                               static_cast<const ac_protected_out*>(noisy_v), db_norm_v, B, K, C, stream);
+                               static_cast<const ac_protected_out*>(noisy_v), db_norm_v, (flags & AC_EMIT_CARRY) != 0, B, K, C, stream);
   }
   if (flags & AC_IN_PACKED) {
     AC_REQUIRE(flags == (AC_IN_PACKED | AC_EMIT_PACKED),

@@ -9,12 +9,18 @@ extern "C" {
 // Every chunk call ends in one of these two: the kernels wrote the new state into the second buffer of its pair, so the pair
 // swaps roles.  The tail's swap also settles the concealment state, which nothing else may assign per
 // chunk: a concealing chunk wrote its other half, now current; any other synthesis left it behind the signal, stale.
+// recovering: the chunk was synthesised one frame behind its rows ("Streams"), which sets the stream's mode.
 static void advance_prev(ac_stream* s) { std::swap(s->d_prev_block, s->d_prev_tmp); }
-static void advance_tail(ac_stream* s, bool concealed) {
+static void advance_tail(ac_stream* s, bool concealed, bool recovering = false) {
   std::swap(s->d_tail, s->d_tail_tmp);
   if (concealed) s->conceal_cur ^= 1;
   s->conceal_stale = !concealed;
+  (recovering ? s->delayed : s->advanced) = true;
 }
+// every call that advances the synthesis as it is, on a stream whose recovering chunks run one frame behind
+#define AC_REQUIRE_NOT_DELAYED(s, what)                                                                                          \
+  AC_REQUIRE(!(s)->delayed, "%s on a stream that decodes recovering chunks, one frame behind its rows (AC_CONCEAL_REDUNDANT): " \
+             "flush it and call ac_stream_reset first", what)
 
 int ac_stream_create(const ac_mdct_plan* plan, int B, int C, ac_stream** out) {
   AC_REQUIRE(out != nullptr, "out is NULL");
@@ -63,6 +69,7 @@ int ac_stream_reset(ac_stream* s, void* stream) {
   if (s->d_prev64) AC_HIP_CHECK(hipMemsetAsync(s->d_prev64, 0, 2 * nb, (hipStream_t)stream));
   if (s->d_tail64) AC_HIP_CHECK(hipMemsetAsync(s->d_tail64, 0, 2 * nt, (hipStream_t)stream));
   s->conceal_stale = true;   // (the concealment state, where there is one: the next concealing chunk reads every gap as 32)
+  s->delayed = s->advanced = false;
   return AC_OK;
 }
 
@@ -144,6 +151,7 @@ int ac_stream_inverse(ac_stream* s, const float* X_chunk, float* x, int k, void*
   if (k == 0) return AC_OK;
   AC_REQUIRE(X_chunk != nullptr && x != nullptr, "NULL tensor pointer");
   AC_REQUIRE_ALIGNED(X_chunk, x);
+  AC_REQUIRE_NOT_DELAYED(s, "ac_stream_inverse");
   const ac_mdct_plan* p = s->plan;
   DeviceGuard guard(s->device);
   hipStream_t hs = (hipStream_t)stream;
@@ -177,6 +185,7 @@ static int settle_state(ac_stream* s, hipStream_t hs) {
 
 int ac_stream_settle(ac_stream* s, void* stream) {
   AC_REQUIRE(s != nullptr, "stream is NULL");
+  AC_REQUIRE_NOT_DELAYED(s, "ac_stream_settle");   // (it would leave no source: the deferred row would be lost unseen)
   return settle_state(s, (hipStream_t)stream);
 }
 
@@ -186,6 +195,7 @@ int ac_stream_run(ac_stream* s, const ac_psy_plan* psy, int nchunks, int k, cons
   AC_REQUIRE(s != nullptr, "stream is NULL");
   AC_REQUIRE(nchunks >= 0 && k >= 0, "negative chunk count / length (%d, %d)", nchunks, k);
   if (nchunks == 0 || k == 0) return AC_OK;
+  AC_REQUIRE_NOT_DELAYED(s, "ac_stream_run");   // (with or without synthesis: it settles the state, which leaves no source)
   AC_REQUIRE(x_chunks != nullptr && X_chunks != nullptr, "NULL chunk list");
   AC_REQUIRE(psy == nullptr || (t_chunks != nullptr && thr_chunks != nullptr), "NULL chunk list");
   for (int i = 0; i < nchunks; ++i) {
@@ -287,7 +297,9 @@ static bool stream_encode_packed_fuses(const ac_stream* s, const ac_psy_plan* ps
 
 int ac_stream_packed_launches(const ac_stream* s, const ac_psy_plan* psy, int decode) {
   if (!s || !plans_match(s->plan, psy)) return 0;
-  // ac_unpack, ac_dequantize, ac_stream_inverse (decode == 2, concealing: the fade between them is the caller's)
+  // ac_unpack, ac_dequantize, ac_stream_inverse (decode == 2, concealing: the fade between them is the caller's; decode == 3,
+  // recovering first, one frame behind: so are the plan and the deferred row)
+  if (decode == 3) return decode_packed_fuses(s->plan, psy, s->C) && fast_inv_packed_recover_stream_serves(s->plan, psy, s->C) ? 1 : 3;
   if (decode == 2) return decode_packed_fuses(s->plan, psy, s->C) && fast_inv_packed_conceal_stream_serves(s->plan, psy, s->C) ? 1 : 3;
   if (decode) return decode_packed_fuses(s->plan, psy, s->C) ? 1 : 3;
   if (!psy->row_bits) return 0;
@@ -353,7 +365,9 @@ static int stream_conceal_state(ac_stream* s, hipStream_t hs) {
 }
 
 // A chunk of packed rows through the synthesis (AC_PACKED), with the rows marked lost concealed (AC_PACKED | AC_CONCEAL): there
-// X_chunk addresses an ac_stream_packed_lost_in, which begins with the ac_stream_packed_in of the plain form
+// X_chunk addresses an ac_stream_packed_lost_in, which begins with the ac_stream_packed_in of the plain form.  A max_age there
+// that is not negative and has AC_CONCEAL_REDUNDANT set marks the longer ac_stream_packed_recover_in: the chunk recovers before it
+// conceals and is synthesised one frame behind its rows ("Streams").
 static int stream_inverse_packed(ac_stream* s, const void* X_chunk, bool conceal, void* x, int k, void* stream) {
   AC_REQUIRE(s != nullptr, "stream is NULL");
   AC_REQUIRE(k >= 0, "negative chunk length %d", k);
@@ -369,13 +383,33 @@ static int stream_inverse_packed(ac_stream* s, const void* X_chunk, bool conceal
   int st = check_plan_pair(p, psy);
   if (st) return st;
   AC_REQUIRE(pin.pcm16 == 0 || pin.pcm16 == 1, "ac_stream_packed_in: pcm16 must be 0 or 1 (got %d)", (int)pin.pcm16);
+  int64_t redundant_at = 0;   // nonzero: a recovering chunk
   if (conceal) {
+    if (li.max_age >= 0 && (li.max_age & AC_CONCEAL_REDUNDANT)) {
+      redundant_at = static_cast<const ac_stream_packed_recover_in*>(X_chunk)->redundant_at;
+      li.max_age &= ~AC_CONCEAL_REDUNDANT;
+      AC_REQUIRE(redundant_at >= 1 && redundant_at <= 2147483647ll, "ac_stream_packed_recover_in: redundant_at (%lld) outside "
+                 "[1, 2^31)", (long long)redundant_at);
+    }
     AC_REQUIRE(li.max_age >= 0 && li.max_age <= AC_CONCEAL_MAX_AGE, "ac_stream_packed_lost_in: max_age (%d) outside [0, %d]",
                (int)li.max_age, AC_CONCEAL_MAX_AGE);
     AC_REQUIRE(li.lost != nullptr, "ac_stream_packed_lost_in: lost is NULL");
   }
   if (k == 0) return AC_OK;
-  if (conceal && ac_stream_packed_launches(s, psy, 2) != 1) {
+  if (redundant_at) {
+    AC_REQUIRE(!s->advanced, "AC_CONCEAL_REDUNDANT on a stream whose synthesis has advanced without it since it was created or "
+               "reset: a recovering chunk is one frame behind its rows -- call ac_stream_reset first");
+    if (ac_stream_packed_launches(s, psy, 3) != 1) {
+      set_error("AC_PACKED | AC_CONCEAL with AC_CONCEAL_REDUNDANT: no kernel decodes a chunk of packed rows with lost rows recovered "
+                "in one launch for filters_n = %d, bark_bands_n = %d, %d channels here (ac_stream_packed_launches(s, psy, 3) != 1): "
+                "compose it from ac_unpack, the fade, ac_dequantize and ac_stream_inverse, and keep the deferred row yourself",
+                p->N, psy->M, s->C);
+      return AC_EUNSUPPORTED;
+    }
+  } else {
+    AC_REQUIRE_NOT_DELAYED(s, "ac_stream_inverse_typed without AC_CONCEAL_REDUNDANT");
+  }
+  if (conceal && !redundant_at && ac_stream_packed_launches(s, psy, 2) != 1) {
     set_error("AC_PACKED | AC_CONCEAL: no kernel decodes a chunk of packed rows with lost rows concealed in one launch for "
               "filters_n = %d, bark_bands_n = %d, %d channels here (ac_stream_packed_launches(s, psy, 2) != 1): compose it from "
               "ac_unpack, the fade, ac_dequantize and ac_stream_inverse, and carry the last row that arrived yourself",
@@ -402,14 +436,19 @@ static int stream_inverse_packed(ac_stream* s, const void* X_chunk, bool conceal
     uint8_t* rows[2] = {s->d_conceal, s->d_conceal + nr};
     uint8_t* gaps[2] = {s->d_conceal + 2 * nr, s->d_conceal + 2 * nr + ng};
     const int cur = s->conceal_cur;
-    st = launch_inv_fast_packed_conceal_stream(p, psy, pin.rows.data, pin.rows.nbytes, pin.rows.index, li.lost, li.max_age, x,
-                                               pin.pcm16 != 0, s->d_tail, s->d_tail_tmp, gaps[cur], rows[cur], gaps[cur ^ 1],
-                                               rows[cur ^ 1], s->conceal_stale, s->B, k, s->C, hs);
+    if (redundant_at)
+      st = launch_inv_fast_packed_recover_stream(p, psy, pin.rows.data, pin.rows.nbytes, pin.rows.index, li.lost, li.max_age,
+                                                 redundant_at, x, pin.pcm16 != 0, s->d_tail, s->d_tail_tmp, gaps[cur], rows[cur],
+                                                 gaps[cur ^ 1], rows[cur ^ 1], s->conceal_stale, s->B, k, s->C, hs);
+    else
+      st = launch_inv_fast_packed_conceal_stream(p, psy, pin.rows.data, pin.rows.nbytes, pin.rows.index, li.lost, li.max_age, x,
+                                                 pin.pcm16 != 0, s->d_tail, s->d_tail_tmp, gaps[cur], rows[cur], gaps[cur ^ 1],
+                                                 rows[cur ^ 1], s->conceal_stale, s->B, k, s->C, hs);
   } else {
     st = launch_inv_fast_packed(p, psy, pin.rows.data, pin.rows.nbytes, pin.rows.index, x, pin.pcm16 != 0, s->d_tail, s->d_tail_tmp,
                                 s->B, k, k, s->C, hs);
   }
-  if (!st) advance_tail(s, conceal);
+  if (!st) advance_tail(s, conceal, redundant_at != 0);
   return st;
 }
 
@@ -471,12 +510,14 @@ int ac_stream_inverse_typed(ac_stream* s, const void* X_chunk, void* x, int dtyp
   if (k == 0) return AC_OK;
   AC_REQUIRE(X_chunk != nullptr && x != nullptr, "NULL tensor pointer");
   AC_REQUIRE_ALIGNED(X_chunk, x);
+  AC_REQUIRE_NOT_DELAYED(s, "ac_stream_inverse_typed");
   DeviceGuard guard(s->device);
   if (dtype == AC_F64) {
     st = stream_state64(s, (hipStream_t)stream);
     if (!st) st = launch_inv_typed(s->plan, X_chunk, x, s->d_tail64, s->d_tail64_tmp, AC_F64, s->B, k, k, s->C, (hipStream_t)stream);
     if (st) return st;
     std::swap(s->d_tail64, s->d_tail64_tmp);
+    s->advanced = true;
     return AC_OK;
   }
   st = launch_inv_fast(s->plan, static_cast<const float*>(X_chunk), x, 2, s->d_tail, s->d_tail_tmp, s->B, k, k, s->C, (hipStream_t)stream);

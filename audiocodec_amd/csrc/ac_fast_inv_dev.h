@@ -1,6 +1,7 @@
 // Synthesis of the wave-level kernels for filters_n = 1024 / 2048 (ac_fast_dev.h): the body shared by k_inv_fast,
 // k_inv_fast_q (instantiated in ac_fast_inv.hip), k_inv_fast_p (ac_fast_inv_p.hip), its concealing forms k_inv_fast_pl
-// (ac_fast_inv_pl.hip), k_inv_fast_pls (ac_fast_inv_pls.hip) and k_inv_fast_plr (ac_fast_inv_plr.hip) and k_duplex_fast (ac_fast_fwd.hip), and
+// (ac_fast_inv_pl.hip), k_inv_fast_pls (ac_fast_inv_pls.hip), k_inv_fast_plr (ac_fast_inv_plr.hip) and k_inv_fast_plsr
+// (ac_fast_inv_plsr.hip) and k_duplex_fast (ac_fast_fwd.hip), and
 // prep_inv_fast(), the host code that fills its arguments for these objects (InvArgs has internal linkage, so no function
 // can pass it between them).
 #pragma once
@@ -77,7 +78,8 @@ __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const
   constexpr bool QUANT = IOF >= 3;
   constexpr bool PACKED = IOF >= 5;   // (IOF 5 / 6) the quantised spectra come as rows of the packed bitstream
   constexpr bool CONCEAL = IOF >= 7;  // (IOF 7 / 8) ... and a row that did not arrive is concealed (ConcealRows)
-  constexpr bool CSTREAM = IOF == 9 || IOF == 10;   // (IOF 9 / 10) ... with the last row of the chunks before as a source (ConcealState)
+  constexpr bool DELAYED = IOF == 13 || IOF == 14;  // (IOF 13 / 14) a chunk of a stream that recovers: synthesis frame n is row n - 1
+  constexpr bool CSTREAM = IOF == 9 || IOF == 10 || DELAYED;   // (IOF 9 / 10) ... with the last row of the chunks before as a source (ConcealState)
   constexpr bool REDUND = IOF >= 11;  // (IOF 11 / 12) one-shot, a lost row recovered from its successor's copy (RedundRows)
   static_assert(!PACKED || R == 8, "packed rows: filters_n = 1024");
   constexpr int OIOF = PACKED ? (IOF - 5) % 2 : QUANT ? IOF - 3 : IOF;   // format of the PCM side
@@ -177,7 +179,7 @@ __device__ __forceinline__ void inv_fast_body(const InvArgs& a, char* lds, const
   if constexpr (PACKED) {
     // slot 0 is frame n0-1, read only by a wave that transforms it itself
     if (valid)
-      parse_strip_p<CONCEAL, CSTREAM, REDUND>(*pr, pq.b0, pq.b1, pq.c0, pq.c1, a.Kp, C, n0 - 1, (left && !deferred) ? 0 : 1,
+      parse_strip_p<CONCEAL, CSTREAM, REDUND>(*pr, pq.b0, pq.b1, pq.c0, pq.c1, a.Kp, C, n0 - 1 - (DELAYED ? 1 : 0), (left && !deferred) ? 0 : 1,
                                               min(n1, a.Kp) - (n0 - 1), has1, lane, buf, rec, cl, cs, rd);
   }
   if (valid) {

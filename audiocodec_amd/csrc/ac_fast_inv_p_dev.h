@@ -31,6 +31,13 @@
 // 8g): a lost row whose successor arrived is read from index[b, f+1, c] + redundant_at -- the copy the successor's slot
 // carries -- with age 0, ahead of every rule above.  Beside the look-back the row's half wave loads lost[b, f+1, c] and, with
 // it, index[b, f+1, c]: frame f + 1 is usually outside the strip and only an address, as the source of a concealed row is.
+//
+// ... in a stream (parse_strip_p<true, true, true>, k_inv_fast_plsr in ac_fast_inv_plsr.hip; DESIGN.md section 8g, "Streams"):
+// the chunk is synthesised one frame behind its rows, so that the successor of every frame it synthesises is a row of the chunk
+// in hand.  The caller passes `base` in rows: synthesis frame n reads row n - 1, and row -1 is the deferred row D, the last row
+// of the chunk before -- lost unless gap == 0, and then the carried row itself, read from the state buffer at age 0.  The
+// look-back below gives that at f = -1 as it stands (lane k finds the carried row where k == gap); only the loads of `lost` and
+// `index` at f itself are kept to f >= 0.
 #pragma once
 #include "ac_fast_dev.h"
 
@@ -112,7 +119,8 @@ __device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0
                                               uint32_t* rec, const ConcealRows* cl = nullptr, const ConcealState* cs = nullptr,
                                               const RedundRows* rd = nullptr) {
   static_assert(CONCEAL || !STREAM, "the carried row is a source of concealment");
-  static_assert(!REDUND || (CONCEAL && !STREAM), "recovery: the one-shot concealing form only");
+  static_assert(!REDUND || CONCEAL, "recovery comes ahead of concealment");
+  constexpr bool DELAYED = STREAM && REDUND;         // frames base + slot may be row -1, the deferred row (above)
   uint32_t* st = reinterpret_cast<uint32_t*>(buf);   // [P_ROWS][P_HDR_WORDS]
   uint32_t* info = rec + P_ROWS * P_M;
   const int sig = lane >> 5, k = lane & 31;          // half a wave per row: slot t, signal sig
@@ -133,7 +141,7 @@ __device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0
       const long long b = sig ? b1 : b0;
       const int c = sig ? c1 : c0;
       const int f = base + t;
-      if (on && k < P_HDR_WORDS) own = pr.index[((size_t)b * (size_t)Kp + (size_t)f) * (size_t)C + (size_t)c];
+      if (on && k < P_HDR_WORDS && (!DELAYED || f >= 0)) own = pr.index[((size_t)b * (size_t)Kp + (size_t)f) * (size_t)C + (size_t)c];
       bool succ = false;   // (REDUND) frame f + 1 of the signal exists and arrived: one byte, the same in the half wave's lanes
       if constexpr (REDUND) {
         if (on && f + 1 < Kp) {
@@ -170,7 +178,7 @@ __device__ __forceinline__ void parse_strip_p(const PackedRows& pr, long long b0
       const int c = sig ? c1 : c0;
       int64_t a;
       bool carried = false;   // (STREAM) the source lies before the chunk: the carried row of (b, c)
-      if constexpr (STREAM) carried = !muted && age > base + t;
+      if constexpr (STREAM) carried = !muted && !recover && age > base + t;   // (D that arrived: age 0 > -1)
       if constexpr (CONCEAL) {
         a = own;
         if (age != 0 && !carried) a = pr.index[((size_t)b * (size_t)Kp + (size_t)(base + t - age)) * (size_t)C + (size_t)c];

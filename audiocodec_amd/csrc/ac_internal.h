@@ -222,6 +222,11 @@ struct ac_stream {
   uint8_t* d_conceal = nullptr;
   int conceal_cur = 0;
   bool conceal_stale = true;
+  // the recovering decode of chunks ("Streams") synthesises one frame behind its rows.  delayed: a
+  // recovering chunk has run since creation or the last reset, and every other call that advances the synthesis is refused;
+  // advanced: such a call has run since then, and a recovering chunk is refused
+  bool delayed = false;
+  bool advanced = false;
 };
 
 // ---- kernel launchers (each returns an AC_* status) -----------------------------------------
@@ -380,6 +385,15 @@ int launch_inv_fast_packed_conceal_stream(const ac_mdct_plan* p, const ac_psy_pl
                                           const int64_t* index, const uint8_t* lost, int max_age, void* x, bool pcm16,
                                           const float* tail_in, float* tail_out, const uint8_t* gap_in, const uint8_t* row_in,
                                           uint8_t* gap_out, uint8_t* row_out, bool stale, int B, int k, int C, hipStream_t s);
+// ... recovering first, as launch_inv_fast_packed_recover does one-shot (k_inv_fast_plsr, ac_fast_inv_plsr.hip; DESIGN.md section
+// 8g, "Streams"): the k blocks are the frames of the deferred row -- the last row of the chunk before, which the state carries
+// where gap_in is 0 -- and of rows 0 .. k-2; the state written is the one launch_inv_fast_packed_conceal_stream writes
+bool fast_inv_packed_recover_stream_serves(const ac_mdct_plan* p, const ac_psy_plan* psy, int C);
+int launch_inv_fast_packed_recover_stream(const ac_mdct_plan* p, const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes,
+                                          const int64_t* index, const uint8_t* lost, int max_age, int64_t redundant_at, void* x,
+                                          bool pcm16, const float* tail_in, float* tail_out, const uint8_t* gap_in,
+                                          const uint8_t* row_in, uint8_t* gap_out, uint8_t* row_out, bool stale, int B, int k,
+                                          int C, hipStream_t s);
 int launch_psy_fast(const ac_psy_plan* p, const float* X, const float* t_in, float* t_out, float* thr, float drown,
                     int B, int F, int C, hipStream_t s, int iof = 0);
 // streaming duplex: the analysis of a chunk of k_fwd blocks (psy: with the fused masking model) and the synthesis of a
@@ -462,6 +476,13 @@ bool protect_serves(const ac_psy_plan* psy, int red_bits);
 int launch_protect(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes, const int64_t* index, uint8_t* out,
                    int64_t row_bytes, int red_bits, uint8_t* fits, uint8_t* red_fits, int16_t* offset, int16_t* red_offset, int B,
                    int F, int C, hipStream_t s);
+// ... as one chunk of F frames of a stream (k_protect_ps, ac_protect_s.hip; DESIGN.md section 8g, "Streams"): the frame-0 slots
+// take the copy, fits and offset the chunk before left in row_in [B,C,red_bytes], fits_in, offset_in [B,C] (row_in NULL: a fresh
+// stream, zeros as above), and the copy of frame F - 1 goes to row_out, fits_out, offset_out, other buffers
+int launch_protect_stream(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes, const int64_t* index, uint8_t* out,
+                          int64_t row_bytes, int red_bits, uint8_t* fits, uint8_t* red_fits, int16_t* offset, int16_t* red_offset,
+                          const uint8_t* row_in, const uint8_t* fits_in, const int16_t* offset_in, uint8_t* row_out,
+                          uint8_t* fits_out, int16_t* offset_out, int B, int F, int C, hipStream_t s);
 // rate control per clip (ac_clip_rate.hip): one budget for the F*C rows of a clip (clip_budget [B] int64,
 // or the scalar budget where it is NULL); row_bits, clip_offset and clip_bits may be NULL; scratch of
 // clip_budget_scratch_bytes(p, B, F*C) bytes

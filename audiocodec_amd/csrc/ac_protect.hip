@@ -4,6 +4,18 @@
 #include "ac_protect_dev.h"
 
 namespace ac {
+namespace {
+
+// grid: ceil(rows / T_WAVES) workgroups of T_WAVES waves
+__global__ __launch_bounds__(T_WAVES * 64) void k_protect_p(ProtectArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[T_WAVES * T_WAVE_WORDS];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const long long r = (long long)blockIdx.x * T_WAVES + wave;
+  if (r >= a.rows) return;   // (no workgroup barrier anywhere: the waves of a workgroup share nothing)
+  protect_row(a, r, lane, lds + wave * T_WAVE_WORDS);
+}
+
+}  // namespace
 
 // where k_transrate_p serves the plan's budget, and a wave can stage the redundant part too; any channel count
 bool protect_serves(const ac_psy_plan* psy, int red_bits) {

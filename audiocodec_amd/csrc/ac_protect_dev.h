@@ -1,4 +1,4 @@
-// Packed rows to protected slots in one launch (k_protect_p, instantiated in ac_protect.hip): the
+// Packed rows to protected slots in one launch (k_protect_p, defined in ac_protect.hip): the
 // sibling of k_transrate_p (ac_transrate_dev.h), on its device functions as they are.  A slot of slot_bytes = row_bytes +
 // red_bytes holds the row at the plan's budget R (the primary part) and, behind it, the row of the frame before at the
 // redundant budget R2 (the redundant part).  One wave owns one input row r = (b F + f) C + c and lane j holds band j; rows are
@@ -11,6 +11,12 @@
 //          red_offset[r + C].  Skipped at f = F - 1: that copy has no slot.
 // The wave of a frame-0 row also zeroes the redundant part of its own slot (no wave packs into it) and sets red_fits there
 // to 1, red_offset to 0.  So every output byte is written by exactly one wave.
+//
+// As one chunk of a stream (protect_row<true>, k_protect_ps in ac_protect_s.hip; DESIGN.md section 8g, "Streams"): the copy of
+// the chunk's last input row is not dropped but packed into the carry (ProtectCarry), and the wave of a frame-0 row copies the
+// carried words and flags of the chunk before into its slot where it zeroes above; on a fresh stream (row_in NULL) it zeroes.
+// The carry is double buffered -- read from one half, written to the other, flipped by the host -- so still no wave waits for
+// another and every output byte has one writer.
 #pragma once
 #include "ac_transrate_dev.h"
 
@@ -28,6 +34,16 @@ struct ProtectArgs {
   int F, C;
   int row_bits, red_bits;     // R, R2
   int row_bytes, red_bytes;   // ceil(R / 32) * 4, ceil(R2 / 32) * 4
+};
+
+// (streams) the copy of the last input row of a chunk, per clip and channel sg = b C + c: what the next chunk's frame-0 slots hold
+struct ProtectCarry {
+  const uint8_t* row_in;      // [B, C, red_bytes], or null: a fresh stream
+  const uint8_t* fits_in;     // [B, C]
+  const int16_t* offset_in;   // [B, C]
+  uint8_t* row_out;           // the other half: written by the waves of the frame-(F-1) rows
+  uint8_t* fits_out;
+  int16_t* offset_out;
 };
 
 // the search and the pack of transrate_row at `budget` bits into nw_out words at dst; returns (offset << 1) | fits in every lane
@@ -85,7 +101,8 @@ __device__ __forceinline__ int protect_pack(const uint32_t (&bw)[8], const uint3
 }
 
 // row r of a.in -> the primary part of slot r and the redundant part of slot r + C; w: the wave's slice of LDS
-__device__ __forceinline__ void protect_row(const ProtectArgs& a, long long r, int lane, uint32_t* w) {
+template <bool STREAM = false>
+__device__ __forceinline__ void protect_row(const ProtectArgs& a, long long r, int lane, uint32_t* w, const ProtectCarry* pc = nullptr) {
   uint32_t* st_in = w;
   uint32_t* st_out = w + T_IN_WORDS;
   uint32_t* rec_in = st_out + T_OUT_WORDS;
@@ -95,6 +112,7 @@ __device__ __forceinline__ void protect_row(const ProtectArgs& a, long long r, i
   const PackedRows& pr = a.in;
   const int f = (int)((r / a.C) % a.F);
   const size_t slot_bytes = (size_t)a.row_bytes + (size_t)a.red_bytes;
+  const size_t sg = (size_t)(r / ((long long)a.F * a.C)) * (size_t)a.C + (size_t)(r % a.C);   // (STREAM) the row's clip and channel
 
   // ---- parse: the header, the band records, then the rest of the row (transrate_row's)
   int64_t at = pr.index[r];
@@ -104,10 +122,21 @@ __device__ __forceinline__ void protect_row(const ProtectArgs& a, long long r, i
   qmn[lane] = INT_MAX;
   if (f == 0) {   // no wave packs into the redundant part of a frame-0 slot
     uint32_t* red = reinterpret_cast<uint32_t*>(a.data + (size_t)r * slot_bytes + (size_t)a.row_bytes);
-    for (int k = lane; k < (a.red_bytes >> 2); k += 64) red[k] = 0u;
-    if (lane == 0) {
-      a.red_fits[r] = 1;
-      if (a.red_offset) a.red_offset[r] = 0;
+    bool fresh = true;
+    if constexpr (STREAM) fresh = pc->row_in == nullptr;
+    if (fresh) {
+      for (int k = lane; k < (a.red_bytes >> 2); k += 64) red[k] = 0u;
+      if (lane == 0) {
+        a.red_fits[r] = 1;
+        if (a.red_offset) a.red_offset[r] = 0;
+      }
+    } else if constexpr (STREAM) {   // the copy of the chunk before's last row of this clip and channel
+      const uint32_t* src = reinterpret_cast<const uint32_t*>(pc->row_in + sg * (size_t)a.red_bytes);
+      for (int k = lane; k < (a.red_bytes >> 2); k += 64) red[k] = src[k];
+      if (lane == 0) {
+        a.red_fits[r] = pc->fits_in[sg];
+        if (a.red_offset) a.red_offset[r] = pc->offset_in[sg];
+      }
     }
   }
   wave_sync();
@@ -176,7 +205,19 @@ __device__ __forceinline__ void protect_row(const ProtectArgs& a, long long r, i
     a.fits[r] = (uint8_t)(p0 & 1);
     if (a.offset) a.offset[r] = (int16_t)(p0 >> 1);
   }
-  if (f == a.F - 1) return;   // the copy of a clip's last frame has no slot
+  if constexpr (STREAM) {
+    if (f == a.F - 1) {   // the copy of the chunk's last frame goes into the carry
+      const int pl = protect_pack(bw, cw, rec_in, rec_out, st_out, meta, kx, kn, first, len, a.red_bits, a.red_bytes >> 2,
+                                  reinterpret_cast<uint32_t*>(pc->row_out + sg * (size_t)a.red_bytes), lane);
+      if (lane == 0) {
+        pc->fits_out[sg] = (uint8_t)(pl & 1);
+        pc->offset_out[sg] = (int16_t)(pl >> 1);
+      }
+      return;
+    }
+  } else {
+    if (f == a.F - 1) return;   // the copy of a clip's last frame has no slot
+  }
   // ---- the redundant part of slot r + C: the same frame of input at R2
   const int p1 = protect_pack(bw, cw, rec_in, rec_out, st_out, meta, kx, kn, first, len, a.red_bits, a.red_bytes >> 2,
                               reinterpret_cast<uint32_t*>(slot + (size_t)a.C * slot_bytes + (size_t)a.row_bytes), lane);
@@ -184,15 +225,6 @@ __device__ __forceinline__ void protect_row(const ProtectArgs& a, long long r, i
     a.red_fits[r + a.C] = (uint8_t)(p1 & 1);
     if (a.red_offset) a.red_offset[r + a.C] = (int16_t)(p1 >> 1);
   }
-}
-
-// grid: ceil(rows / T_WAVES) workgroups of T_WAVES waves
-__global__ __launch_bounds__(T_WAVES * 64) void k_protect_p(ProtectArgs a) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[T_WAVES * T_WAVE_WORDS];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const long long r = (long long)blockIdx.x * T_WAVES + wave;
-  if (r >= a.rows) return;   // (no workgroup barrier anywhere: the waves of a workgroup share nothing)
-  protect_row(a, r, lane, lds + wave * T_WAVE_WORDS);
 }
 
 }  // namespace

@@ -55,7 +55,9 @@ extern "C" {
                           * ac_transrate_launches; lost rows concealed in a stream: AC_CONCEAL,
                           * ac_stream_packed_lost_in; protected rows and the decode that recovers from them:
                           * AC_EMIT_REDUNDANT, ac_protected_out, ac_protect_launches, AC_CONCEAL_REDUNDANT,
-                          * ac_conceal_redundant); additions only, so the number stays.
+                          * ac_conceal_redundant; the recovering decode chunk by chunk: ac_stream_packed_recover_in,
+                          * and protecting chunk by chunk: AC_EMIT_CARRY, ac_protect_carry, ac_protect_chunk_launches);
+                          * additions only, so the number stays.
                           * 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
                           * with a 5-smooth half up to 8192, float32); masking model for general band layouts up to 4096 bins.
                           * 0.1.7: only the ac_* entry points are exported; ac_stream_settle (home buffers for the streaming state);
@@ -284,8 +286,17 @@ AC_API int ac_encode_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
  *     where ac_protect_launches returns 1; AC_EUNSUPPORTED elsewhere (run the composition).
  * out0 / out1: float* noisy, float* db_norm under AC_EMIT_NOISY / AC_EMIT_DB_NORM; int16_t* codes, int8_t* sf under
  * AC_EMIT_CODES; ac_packed_out*, NULL under AC_EMIT_PACKED (NULL or int16_t* offset with AC_IN_PACKED). */
+/*   AC_EMIT_CARRY  protecting chunk by chunk ("Streams"), valid only beside AC_IN_PACKED | AC_EMIT_PACKED |
+ *     AC_EMIT_REDUNDANT: the rows are the K+1 frames of one chunk of a stream and out1 addresses one ac_protect_carry.  As
+ *     the call above, but the redundant part, red_fits and red_offset of frame 0 are the copy at red_bits of the chunk before's
+ *     last INPUT row, read from row_in [B,C,red_bytes], fits_in [B,C], offset_in [B,C] (row_in == NULL: a fresh stream, the
+ *     f = 0 values above), and the copy of this chunk's last input row is written to row_out, fits_out, offset_out for the
+ *     next call.  in and out must be distinct buffers (the carry is double buffered: the caller flips them), else
+ *     AC_EINVAL.  So for any split into chunks the slots, flags and offsets, put together along frames, are those of the
+ *     one-shot call on all rows.  Served where ac_protect_chunk_launches returns 1 (where ac_protect_launches does);
+ *     AC_EUNSUPPORTED elsewhere, nothing written. */
 enum { AC_EMIT_NOISY = 1, AC_EMIT_DB_NORM = 2, AC_EMIT_CODES = 4, AC_EMIT_PACKED = 8, AC_IN_PCM16 = 32, AC_IN_PACKED = 64,
-       AC_EMIT_REDUNDANT = 256 };
+       AC_EMIT_REDUNDANT = 256, AC_EMIT_CARRY = 512 };
 /* The largest row budget the one launch of AC_EMIT_PACKED serves: a wave stages both rows of its frame pair in the 4 KB of
  * its LDS buffer that the masking model has left, 2 KB = 16384 bits each. */
 #define AC_PACK_ROWS_MAX_BITS 16384
@@ -303,6 +314,14 @@ typedef struct ac_protected_out {
   int16_t* offset;     /* [B,K+1,C] offsets of the primary search (device), or NULL */
   int16_t* red_offset; /* [B,K+1,C] offsets of the redundant search, by the slot that holds the copy; 0 at f = 0; or NULL */
 } ac_protected_out;
+typedef struct ac_protect_carry {
+  const uint8_t* row_in;     /* [B,C,red_bytes] the copies the chunk before left, or NULL: a fresh stream (device) */
+  const uint8_t* fits_in;    /* [B,C] */
+  const int16_t* offset_in;  /* [B,C] */
+  uint8_t* row_out;          /* the same three for the next chunk: other buffers */
+  uint8_t* fits_out;
+  int16_t* offset_out;
+} ac_protect_carry;
 AC_API int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
                        float drown, int flags, void* out0, void* out1, uint64_t seed, int B, int K, int C,
                        void* stream);
@@ -334,6 +353,9 @@ AC_API int ac_transrate_launches(const ac_psy_plan* psy, int C);
  * AC_PROTECT_NOFUSE=1 is set in the environment: read per call).  0 for a NULL plan, C < 1, a plan without a row budget or
  * red_bits below 5 * bark_bands_n.  The bytes do not depend on it. */
 AC_API int ac_protect_launches(const ac_psy_plan* psy, int C, int red_bits);
+/* The same for one chunk of a stream (AC_EMIT_CARRY): 1 where ac_protect_launches is 1, else its value (the composition's two
+ * transrating calls; the copies to and from the carry are the caller's). */
+AC_API int ac_protect_chunk_launches(const ac_psy_plan* psy, int C, int red_bits);
 
 /* 16-bit PCM at the boundary (extension; the reference takes float PCM in [-1, 1] only, mdctransformer.py:104):
  * x = pcm / 32768 on the way in; on the way out pcm = 0 if x is NaN else clamp(rint(fp32(32768 x)), -32768, 32767), rint
@@ -662,7 +684,7 @@ AC_API int ac_stream_inverse_typed(ac_stream* s, const void* X_chunk, void* x, i
  * ac_stream_packed_launches(s, psy, decode): library launches of a chunk on this stream.  decode = 0: 1 where
  *   ac_encode_packed_launches is 1 for the stream's channels and the kernel instance with streaming state passed its register
  *   gate (stereo with the f32 spreading product did not), else ac_encode_launches + 2.  decode != 0: 1 where
- *   ac_decode_packed_launches is 1, else 3 (decode = 2: of the concealing decode, below).  AC_ENCODE_PACKED_NOFUSE=1 / AC_DECODE_PACKED_NOFUSE=1 apply as they do one-shot
+ *   ac_decode_packed_launches is 1, else 3 (decode = 2: of the concealing decode, decode = 3: of the recovering one, below).  AC_ENCODE_PACKED_NOFUSE=1 / AC_DECODE_PACKED_NOFUSE=1 apply as they do one-shot
  *   (read per call).  0 for NULL or mismatched arguments, or (decode = 0) a plan without a row budget.
  * 16-bit PCM into the encoder: ac_stream_encode_typed(..., dtype = AC_PACKED | AC_IN_PCM16 (48), ...) takes x_chunk as int16
  *   [B,k*N,C], x = pcm / 32768: the rows, and the float32 state it leaves, are those of the AC_PACKED call on that float32
@@ -699,6 +721,31 @@ typedef struct ac_stream_packed_lost_in {
   const uint8_t* lost;      /* [B,k,C]: nonzero = the row did not arrive */
   int32_t max_age;          /* 0 .. AC_CONCEAL_MAX_AGE */
 } ac_stream_packed_lost_in;
+/* Lost rows recovered in a stream (extension; DESIGN.md section 8g, "Streams"): in the call above, a max_age that is not negative
+ * and has AC_CONCEAL_REDUNDANT set marks X_chunk as the longer ac_stream_packed_recover_in, whose leading members are
+ * ac_stream_packed_lost_in's; max_age is the rest of the field.  redundant_at outside [1, 2^31) is AC_EINVAL.
+ *   A delayed stream: the k blocks written are the frames of D, row 0, ..., row k-2, where D is the deferred row -- the last row
+ *     of the chunk before; on a new or reset stream a row that did not arrive and has no source before it -- and the chunk's last
+ *     row becomes the next D.  A frame that is lost (D: g != 0) and whose successor in the chunk arrived (of D: row 0; of row f:
+ *     row f+1) is read from index[b, successor, c] + redundant_at as ac_unpack reads any start, with no fade.  Every other frame
+ *     as AC_CONCEAL alone reads it, D from the carried row where g == 0.  The state afterwards is the one AC_CONCEAL alone
+ *     leaves for rows 0 .. k-1.  So the chunk calls of any split of index [B,K',C] give blocks 0 .. K'-1 of ac_decode_quantized
+ *     with an ac_conceal_redundant on that index and lost with one lost frame put in front (index[:, :1], 1), bit for bit;
+ *     block K' is a last chunk of one row marked lost (any index, data may be empty), after which ac_stream_reset is due.
+ *   Mode: from its first such chunk until ac_stream_reset a stream is delayed, and every other call that advances the synthesis
+ *     (ac_stream_inverse, ac_stream_inverse_typed in any other form, ac_stream_run) and ac_stream_settle are AC_EINVAL; so is such a chunk on a stream
+ *     whose synthesis one of those calls has advanced since it was created or reset.  A refused call leaves all state untouched.
+ *   ONE launch where ac_stream_packed_launches(s, psy, 3) returns 1 (where decode = 1 does); AC_EUNSUPPORTED elsewhere, with all
+ *   state untouched, and the query returns 3: ac_unpack, ac_dequantize, ac_stream_inverse, with the plan of sources, the fade, the
+ *   carried and the deferred row kept by the caller. */
+/*   (A caller's ac_stream_packed_lost_in whose max_age has the bit set, valid or not, is read as the longer struct: 8 bytes
+ *   past its end.  Keep the bit out of a max_age that is not meant to carry it.) */
+typedef struct ac_stream_packed_recover_in {
+  ac_stream_packed_in in;
+  const uint8_t* lost;      /* [B,k,C]: nonzero = the row did not arrive */
+  int32_t max_age;          /* (0 .. AC_CONCEAL_MAX_AGE) | AC_CONCEAL_REDUNDANT */
+  int64_t redundant_at;     /* bytes from a row's start to the copy of the row before it, in [1, 2^31) */
+} ac_stream_packed_recover_in;
 AC_API int ac_stream_packed_launches(const ac_stream* s, const ac_psy_plan* psy, int decode);
 AC_API int ac_stream_packed_launches_pcm16(const ac_stream* s, const ac_psy_plan* psy);
 AC_API int ac_amplitude_to_db_typed(const void* a, void* out, size_t n, int norm, int dtype, void* stream);

@@ -23,7 +23,10 @@ python tools/pack_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--step
 --conceal-stream: the same chunk by chunk on a StreamingMDCT, the last good row carried across chunks, against
 decode_packed_chunk without `lost` (conceal_stream_rows(); profiles/pack/pack_bench_conceal_stream.txt).
 --protect [--red-bits 341]: protect_packed_rows against its composition and transrate_packed_rows alone, then decode_packed with
-redundant_at against without (protect_rows(); profiles/pack/pack_bench_protect.txt)."""
+redundant_at against without (protect_rows(); profiles/pack/pack_bench_protect.txt).
+--protect-stream [--red-bits 341]: decode_packed_chunk with redundant_at chunk by chunk on a StreamingMDCT, against the concealing
+chunk on the same `lost` and against its composition; then protect_chunk against the one-shot protect_packed_rows on the same rows
+and against its composition (protect_stream_rows(); profiles/pack/pack_bench_protect_stream.txt)."""
 import argparse
 import ctypes
 import os
@@ -469,8 +472,116 @@ def conceal_stream_rows(a):
                 print("    (b) / (a) = %.3f   (c) / (a) = %.3f   (c) / (d) = %.3f" % (med[1] / med[0], med[2] / med[0], med[2] / med[3]))
 
 
+def protect_stream_rows(a):
+    """The recovering decode of chunks ("Streams") on protected slots -- rows of
+    encode_packed_rows_chunk at 2730 bits, protected chunk by chunk to --row-bits with a copy at --red-bits -- per workload:
+    (a) decode_packed_chunk with `lost`, the concealing chunk (k_inv_fast_pls), on the same `lost` as (c): the yardstick; (b)
+    with redundant_at and nothing lost; (c) with redundant_at and 1 % of the rows lost at random, max_age 8 -- both the one
+    launch of k_inv_fast_plsr; (d) the composition of (c) (AC_DECODE_PACKED_NOFUSE=1, read per call).  (c) and (d) compared
+    byte for byte first, flush included, then alternating, --rounds rounds of --round-steps passes over the workload's chunks,
+    float32 and 16-bit PCM out.  Two workloads: one stereo clip in chunks of 256 blocks and --clips x --blocks as one chunk."""
+    N, C = a.filters, a.channels
+    base = audiocodec_amd.AudioCodec(48000, N)
+    src, dst = base.with_row_budget(2730), base.with_row_budget(a.row_bits)
+    o = dst.row_bytes
+    for name, B, k, n in (("one clip, chunks of 256 blocks", 1, 256, 8), ("%d clips x %d blocks, one chunk" % (a.clips, a.blocks), a.clips, a.blocks, 1)):
+        g = torch.Generator("cuda").manual_seed(1)
+        enc, pls, dec, comp = src.stream(B, C), dst.stream(B, C), dst.stream(B, C), dst.stream(B, C)
+        packed = []
+        for _ in range(n):
+            data, index, _ = enc.encode_packed_rows_chunk(torch.rand((B, k * N, C), device="cuda", generator=g) * 2 - 1)
+            packed.append(dst.protect_packed_rows(data, index, a.red_bits)[:2])
+        none = torch.zeros((B, k, C), dtype=torch.uint8, device="cuda")
+        some = [(torch.rand((B, k, C), device="cuda", generator=g) < 0.01).to(torch.uint8) for _ in range(n)]
+
+        def recovering(st, lost, pcm16):
+            st.reset()
+            return [st.decode_packed_chunk(d, i, pcm16=pcm16, lost=s, max_age=8, redundant_at=o) for (d, i), s in zip(packed, lost)]
+
+        def composition(pcm16):
+            os.environ["AC_DECODE_PACKED_NOFUSE"] = "1"   # (read per call)
+            try:
+                return recovering(comp, some, pcm16)
+            finally:
+                del os.environ["AC_DECODE_PACKED_NOFUSE"]
+
+        def concealing(pcm16):
+            pls.reset()
+            return [pls.decode_packed_chunk(d, i, pcm16=pcm16, lost=s, max_age=8) for (d, i), s in zip(packed, some)]
+
+        v = torch.int16
+        for pcm16 in (False, True):
+            one = recovering(dec, some, pcm16) + [dec.flush_packed(pcm16)]
+            os.environ["AC_DECODE_PACKED_NOFUSE"] = "1"
+            try:
+                two = recovering(comp, some, pcm16) + [comp.flush_packed(pcm16)]
+            finally:
+                del os.environ["AC_DECODE_PACKED_NOFUSE"]
+            for p, q in zip(one, two):
+                assert p.dtype == q.dtype and torch.equal(p.view(v), q.view(v)), "the two forms differ"
+            del one, two
+        print("protect stream: %s  (B=%d k=%d N=%d C=%d, %d chunks per pass, %d + %d bits per slot, %.2f %% of the rows lost, max_age 8)  %s"
+              "  launches: %d; the one launch and the composition agree byte for byte, flush included (float32 and 16-bit PCM)"
+              % (name, B, k, N, C, n, a.row_bits, a.red_bits, 100.0 * float(torch.stack(some).float().mean()), torch.cuda.get_device_name(),
+                 dec.packed_chunk_launches(decode=True, conceal=True, recover=True)))
+        for pcm16 in (False, True):
+            forms = [("(a) concealing chunk, 1 % lost", lambda: concealing(pcm16)),
+                     ("(b) recovering, none lost", lambda: recovering(dec, [none] * n, pcm16)),
+                     ("(c) recovering, 1 % lost", lambda: recovering(dec, some, pcm16)),
+                     ("(d) recovering, composition", lambda: composition(pcm16))]
+            runs = dict((f, []) for f, _ in forms)
+            for _ in range(a.rounds):
+                for f, fn in forms:
+                    runs[f].append(timed(fn, a.round_steps, 1) / n * 1e3)
+            med = []
+            print("  %s out:" % ("16-bit PCM" if pcm16 else "float32"))
+            for f, _ in forms:
+                t = sorted(runs[f])
+                med.append(t[len(t) // 2])
+                print("    %-32s median %9.1f us per chunk  min %9.1f  max %9.1f  (%d alternating rounds of %d)"
+                      % (f, med[-1], t[0], t[-1], len(t), a.round_steps))
+            print("    (b) / (a) = %.3f   (c) / (a) = %.3f   (c) / (d) = %.3f" % (med[1] / med[0], med[2] / med[0], med[2] / med[3]))
+        # ---- the sending side: protect_chunk against the one-shot protect on the same rows, and against its composition
+        rows = []
+        enc.reset()
+        g = torch.Generator("cuda").manual_seed(1)
+        for _ in range(n):
+            rows.append(enc.encode_packed_rows_chunk(torch.rand((B, k * N, C), device="cuda", generator=g) * 2 - 1)[:2])
+        ps, pc = dst.protect_stream(B, C, a.red_bits), dst.protect_stream(B, C, a.red_bits)
+
+        def chunks(p, nofuse=False):
+            if nofuse:
+                os.environ["AC_PROTECT_NOFUSE"] = "1"   # (read per call)
+            try:
+                p.reset()
+                return [p.protect_chunk(d, i, True) for d, i in rows]
+            finally:
+                if nofuse:
+                    del os.environ["AC_PROTECT_NOFUSE"]
+
+        for p, q in zip(chunks(ps), chunks(pc, True)):
+            for t, u in zip(p, q):
+                assert t.dtype == u.dtype and torch.equal(t, u), "protect_chunk: the two forms differ"
+        forms = [("(a) protect_packed_rows, one-shot", lambda: [dst.protect_packed_rows(d, i, a.red_bits, True) for d, i in rows]),
+                 ("(b) protect_chunk, one launch", lambda: chunks(ps)),
+                 ("(c) protect_chunk, composition", lambda: chunks(pc, True))]
+        runs = dict((f, []) for f, _ in forms)
+        for _ in range(a.rounds):
+            for f, fn in forms:
+                runs[f].append(timed(fn, a.round_steps, 1) / n * 1e3)
+        med = []
+        print("  protect, launches %d; the one launch and the composition agree byte for byte:" % ps.launches())
+        for f, _ in forms:
+            t = sorted(runs[f])
+            med.append(t[len(t) // 2])
+            print("    %-36s median %9.1f us per chunk  min %9.1f  max %9.1f  (%d alternating rounds of %d)"
+                  % (f, med[-1], t[0], t[-1], len(t), a.round_steps))
+        print("    (b) / (a) = %.3f   (b) / (c) = %.3f" % (med[1] / med[0], med[1] / med[2]))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--protect-stream", action="store_true", help="only decode_packed_chunk with redundant_at, against the concealing chunk and its composition")
     ap.add_argument("--conceal-stream", action="store_true", help="only decode_packed_chunk with lost rows concealed, against without")
     ap.add_argument("--protect", action="store_true", help="only protect_packed_rows and the recovering decode (2730 -> 1365 with --red-bits)")
     ap.add_argument("--red-bits", type=int, default=341, help="the redundant budget of --protect (16 kbit/s)")
@@ -491,6 +602,8 @@ def main():
     ap.add_argument("--round-steps", type=int, default=30)
     a = ap.parse_args()
     B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    if a.protect_stream:
+        return protect_stream_rows(a)
     if a.protect:
         return protect_rows(a)
     if a.conceal:
