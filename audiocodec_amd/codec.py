@@ -31,6 +31,14 @@ def _pack_rows_of_spectra(psy, X, thr, index, row_bytes):
     dev = X.device
     row_bits, min_offset = psy.row_budget
     codes, sf, _, bits = psy.quantize_to_budget(X, thr, row_bits, min_offset)
+    return _pack_rows_of_codes(psy, codes, sf, bits, index, row_bytes)
+
+
+def _pack_rows_of_codes(psy, codes, sf, bits, index, row_bytes):
+    """The tail of :func:`_pack_rows_of_spectra`, which :meth:`AudioCodec.mix_packed_rows`' composition shares: codes
+    [B, F, N, C], sf (changed in place) and their packed lengths ``bits`` [B, F, C] -> (data, fits)."""
+    B, F, _, C = codes.shape
+    dev = codes.device
     fits = bits <= 8 * row_bytes
     sf.masked_fill_(~fits.unsqueeze(2), -128)   # width 31 follows whatever the codes are
     data = torch.zeros((B * F * C * row_bytes,), dtype=torch.uint8, device=dev)
@@ -459,6 +467,80 @@ class AudioCodec:
         with _host.on_device(dev):
             _lib.check(self._lib.ac_pack(psy, _host.ptr(codes), _host.ptr(sf), _host.ptr(index_out), _host.ptr(out_data), B, F, C,
                                          _host.stream_ptr(dev)))
+        return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
+
+    # ---- mixing the packed rows of several sources (extension) ----------------------------
+    def mix_packed_rows_launches(self, channels_n=2, device=None, *, sources_n):
+        """Library launches :meth:`mix_packed_rows` takes for ``sources_n`` sources of ``channels_n`` channels
+        (``ac_mix_launches``): 1 = one kernel reads, sums, quantises and packs each row (where
+        :meth:`transrate_packed_rows_launches` is 1 and ``sources_n`` is at most ``_lib.AC_MIX_MAX_SOURCES``), else
+        ``2 * sources_n + 2``: :meth:`PsychoacousticModel.unpack` and ``dequantize`` per source, ``quantize_to_budget`` and the
+        packer (everywhere while ``AC_MIX_NOFUSE=1`` is set: read per call).  0 on a codec without a row budget."""
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return int(self._lib.ac_mix_launches(self.psy._plan(dev), int(channels_n), int(sources_n)))
+
+    def mix_packed_rows(self, sources, gains=None, active=None, return_offset=False):
+        """On a codec made by :meth:`with_bitrate` / :meth:`with_row_budget`: the packed rows of several sources of this
+        codec on one frame grid -> their sum at this codec's bitrate, without decoding (the MDCT is linear).  ``sources``: a
+        list of S >= 1 pairs (data uint8 [nbytes_i], index int64 [B, F, C]), every index of the same shape on one device ->
+        (data' uint8 [B*F*C*row_bytes], index' int64 [B, F, C], fits' bool [B, F, C]), and offset int16 [B, F, C] with
+        ``return_offset=True`` -- the fixed-stride layout of :meth:`encode_packed_rows`.
+
+        Every ``index`` holds any row starts, read as :meth:`PsychoacousticModel.unpack` reads them, damaged rows included:
+        :meth:`encode_packed` output, fixed-stride rows of any stride, protected slots, slices and a stream's chunks may be
+        mixed with each other.  ``gains``: S ints in [-254, 254] in scale-factor units (one is 2^(1/4), 1.505 dB; default 0);
+        ``active``: uint8 / bool [S, B, F, C] on the device, 0 = the row is never read and adds nothing (a silent participant,
+        a lost row; default all 1).  The rules are :meth:`PsychoacousticModel.mix_to_budget`'s at this codec's ``row_bits``:
+        where sources overlap in a band the coarsest of their steps is where the search starts.  A sum that passes +-32767
+        codes at offset 0 clamps there and its 16-bit widths raise the offset.  With one source and gain 0 the result is
+        :meth:`transrate_packed_rows`'.  A row longer than its slot at offset 254 is stored as the marked row, ``fits`` False.
+        One launch where :meth:`mix_packed_rows_launches` is 1, else the composition on ``unpack``, ``mix_to_budget`` and the
+        packer: the same bytes.  It never synchronises with the device, only enqueues on the current stream, and can be
+        captured in a graph.  float32 only."""
+        _host.require_float32(self.compute_dtype, "mix_packed_rows")
+        if self.row_bits is None:
+            raise ValueError("mix_packed_rows needs a codec with a row budget: make one with with_bitrate() or with_row_budget()")
+        sources = list(sources)
+        if not sources:
+            raise ValueError("mix_packed_rows needs at least one source")
+        S = len(sources)
+        gains = self.psy._check_gains(gains, S)
+        pairs = []
+        for i, (data, index) in enumerate(sources):
+            data = self.psy._check_quant_tensor(data, "data of source %d" % i, torch.uint8, ndim=1)
+            index = self.psy._check_quant_tensor(index, "index of source %d" % i, torch.int64, device=data.device, ndim=3)
+            if pairs and (index.shape != pairs[0][1].shape or index.device != pairs[0][1].device):
+                raise ValueError("index of source %d has shape %s on %s, that of source 0 shape %s on %s"
+                                 % (i, tuple(index.shape), index.device, tuple(pairs[0][1].shape), pairs[0][1].device))
+            pairs.append((data, index))
+        B, F, C = pairs[0][1].shape
+        dev, rb = pairs[0][1].device, self.row_bytes
+        active = self.psy._check_active(active, S, (B, F, C), dev)
+        rows = B * F * C
+        index_out = (torch.arange(rows, dtype=torch.int64, device=dev) * rb).view(B, F, C)
+        if rows == 0:
+            out = (torch.empty((0,), dtype=torch.uint8, device=dev), index_out, torch.empty((B, F, C), dtype=torch.bool, device=dev))
+            return out + (torch.empty((B, F, C), dtype=torch.int16, device=dev),) if return_offset else out
+        psy = self.psy._plan(dev)
+        if self._lib.ac_mix_launches(psy, C, S) == 1:
+            out_data = torch.empty((rows * rb,), dtype=torch.uint8, device=dev)
+            fits = torch.empty((B, F, C), dtype=torch.bool, device=dev)
+            offset = torch.empty((B, F, C), dtype=torch.int16, device=dev) if return_offset else None
+            src = (_lib.PackedRows * S)(*[_lib.PackedRows(d.data_ptr(), d.numel(), ix.data_ptr()) for d, ix in pairs])
+            gain = (ctypes.c_int32 * S)(*gains)
+            mix = _lib.MixRows(S, src, gain, active.data_ptr() if active is not None else None)
+            dst = _lib.PackedOut(out_data.data_ptr(), rb, fits.data_ptr())
+            with _host.on_device(dev):
+                _lib.check(self._lib.ac_encode_fused_ex(self.mdct._plan(dev), psy, ctypes.addressof(mix), None, None, None, 0.0,
+                                                        _lib.AC_IN_PACKED | _lib.AC_EMIT_PACKED | _lib.AC_IN_MIX,
+                                                        ctypes.addressof(dst), _host.ptr(offset) if return_offset else None, 0,
+                                                        B, F - 1, C, _host.stream_ptr(dev)))
+            return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
+        # the composition: every source unpacked, the rows mixed at the budget, rows longer than their slot marked, then the
+        # packer at the fixed row starts (on plain allocations: nothing here may wait for the device)
+        unpacked = [self.psy.unpack(d, ix) for d, ix in pairs]
+        codes, sf, offset, bits = self.psy.mix_to_budget(unpacked, gains, self.row_bits, active)
+        out_data, fits = _pack_rows_of_codes(self.psy, codes, sf, bits, index_out, rb)
         return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
 
     # ---- protected rows: a redundant copy of the frame before in every slot (extension; DESIGN.md section 8g) ---

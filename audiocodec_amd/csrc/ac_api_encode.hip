@@ -37,6 +37,17 @@ int check_row_bytes(const ac_packed_out& po, const ac_psy_plan* psy) {
              (long long)po.row_bytes, psy->row_bits, (long long)plan_row_bytes(psy));
   return AC_OK;
 }
+// what the calls that take packed rows to packed rows (AC_IN_PACKED, AC_IN_MIX) ask of their plans and float tensors
+int check_rows_to_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* X, const float* t, const float* thr, int B,
+                       int K, int C, const char* flag) {
+  int st = check_plan_pair(mdct, psy);
+  if (!st) st = check_dims(B, K, C);
+  if (!st) st = check_quant(psy, B, K + 1, C);
+  if (st) return st;
+  AC_REQUIRE(psy->row_bits != 0, "%s needs a plan with a row budget (ac_psy_plan_with_row_budget)", flag);
+  AC_REQUIRE(X == nullptr && t == nullptr && thr == nullptr, "%s writes no X, t or thr: they must be NULL", flag);
+  return AC_OK;
+}
 static int refuse_pcm16() {
   set_error("16-bit PCM is served at filters_n 64 ... 2048 in powers of two ('vorbis' or 'sine' window; below 1024: mono / "
             "stereo) and at 120 / 240 / 480 / 960 / 1920 / 576 / 1152 (mono / stereo)");
@@ -93,6 +104,11 @@ bool encode_packed_fuses(const ac_mdct_plan* mdct, const ac_psy_plan* psy, int C
 static bool transrate_fuses(const ac_psy_plan* psy) {
   if (env_is_1("AC_TRANSRATE_NOFUSE")) return false;
   return !g_force_generic && transrate_serves(psy);
+}
+// whether the packed rows of S sources are mixed in one launch (k_mix_p); AC_MIX_NOFUSE=1: as above
+static bool mix_fuses(const ac_psy_plan* psy, int S) {
+  if (env_is_1("AC_MIX_NOFUSE")) return false;
+  return transrate_fuses(psy) && mix_serves(psy, S);
 }
 // whether packed rows are protected in one launch (k_protect_p); AC_PROTECT_NOFUSE=1: as above
 static bool protect_fuses(const ac_psy_plan* psy, int red_bits) {
@@ -311,12 +327,8 @@ int ac_transrate_launches(const ac_psy_plan* psy, int C) {
 static int transrate_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const ac_packed_rows* in, const float* X,
                                  const float* t, const float* thr, const ac_packed_out* out, int16_t* offset, int B, int K,
                                  int C, void* stream) {
-  int st = check_plan_pair(mdct, psy);
-  if (!st) st = check_dims(B, K, C);
-  if (!st) st = check_quant(psy, B, K + 1, C);
+  int st = check_rows_to_rows(mdct, psy, X, t, thr, B, K, C, "AC_IN_PACKED");
   if (st) return st;
-  AC_REQUIRE(psy->row_bits != 0, "AC_IN_PACKED needs a plan with a row budget (ac_psy_plan_with_row_budget)");
-  AC_REQUIRE(X == nullptr && t == nullptr && thr == nullptr, "AC_IN_PACKED writes no X, t or thr: they must be NULL");
   AC_REQUIRE(in != nullptr, "AC_IN_PACKED without its ac_packed_rows (x)");
   AC_REQUIRE(out != nullptr, "AC_IN_PACKED without its ac_packed_out (out0)");
   const ac_packed_rows rows = *in;
@@ -338,6 +350,49 @@ static int transrate_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* ps
   DeviceGuard guard(psy->device);
   return launch_transrate(psy, rows.data, rows.nbytes, rows.index, po.data, po.row_bytes, po.fits, offset,
                           (long long)B * (K + 1) * C, (hipStream_t)stream);
+}
+
+int ac_mix_launches(const ac_psy_plan* psy, int C, int S) {
+  if (!psy || C < 1 || S < 1 || !psy->row_bits) return 0;
+  return mix_fuses(psy, S) ? 1 : 2 * S + 2;   // S ac_unpack, S ac_dequantize, ac_quantize_budget, ac_pack
+}
+
+// ac_encode_fused_ex with AC_IN_PACKED | AC_EMIT_PACKED | AC_IN_MIX: rows [B,K+1,C] of every source of `in` summed into slots of
+// `out` at the plan's row budget
+static int mix_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const ac_mix_rows* in, const float* X, const float* t,
+                           const float* thr, const ac_packed_out* out, int16_t* offset, int B, int K, int C, void* stream) {
+  int st = check_rows_to_rows(mdct, psy, X, t, thr, B, K, C, "AC_IN_MIX");
+  if (st) return st;
+  AC_REQUIRE(in != nullptr, "AC_IN_MIX without its ac_mix_rows (x)");
+  AC_REQUIRE(out != nullptr, "AC_IN_MIX without its ac_packed_out (out0)");
+  const ac_mix_rows mix = *in;
+  const ac_packed_out po = *out;
+  st = check_row_bytes(po, psy);
+  if (st) return st;
+  AC_REQUIRE(mix.sources_n >= 1, "sources_n (%d) below 1", (int)mix.sources_n);
+  AC_REQUIRE(mix.src != nullptr, "ac_mix_rows: src is NULL");
+  for (int i = 0; i < mix.sources_n; ++i) {
+    AC_REQUIRE(mix.gain == nullptr || (mix.gain[i] >= -254 && mix.gain[i] <= 254), "gain[%d] (%d) outside [-254, 254]", i,
+               mix.gain ? (int)mix.gain[i] : 0);
+    AC_REQUIRE(mix.src[i].nbytes >= 0, "source %d: negative nbytes (%lld)", i, (long long)mix.src[i].nbytes);
+    AC_REQUIRE(mix.src[i].index != nullptr || B == 0 || C == 0, "source %d: index is NULL", i);
+  }
+  if (B == 0 || C == 0) return AC_OK;
+  if (!mix_fuses(psy, mix.sources_n)) {
+    set_error("AC_IN_MIX: no kernel mixes the packed rows of %d sources in one launch for filters_n = %d, bark_bands_n = %d, row "
+              "budget %d here (ac_mix_launches() != 1): use the composition -- ac_unpack and ac_dequantize per source at sf + "
+              "gain, float32 adds in source order, ac_quantize_budget at kmin 0 under thr = step(s0) sqrt(3), then ac_pack at row "
+              "starts r * row_bytes into zero-filled data", (int)mix.sources_n, psy->N, psy->M, psy->row_bits);
+    return AC_EUNSUPPORTED;
+  }
+  for (int i = 0; i < mix.sources_n; ++i) {
+    st = check_packed_rows(mix.src[i], true, po.data != nullptr && po.fits != nullptr);
+    if (st) return st;
+  }
+  AC_REQUIRE_ALIGNED(po.data, offset);
+  DeviceGuard guard(psy->device);
+  return launch_mix(psy, mix.sources_n, mix.src, mix.gain, mix.active, po.data, po.row_bytes, po.fits, offset,
+                    (long long)B * (K + 1) * C, (hipStream_t)stream);
 }
 
 int ac_protect_launches(const ac_psy_plan* psy, int C, int red_bits) {
@@ -406,7 +461,13 @@ int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const f
                        float drown, int flags, void* noisy_v, void* db_norm_v, uint64_t seed, int B, int K, int C,
                        void* stream) {
   AC_REQUIRE((flags & ~(AC_EMIT_NOISY | AC_EMIT_DB_NORM | AC_EMIT_CODES | AC_EMIT_PACKED | AC_IN_PCM16 | AC_IN_PACKED |
-                        AC_EMIT_REDUNDANT | AC_EMIT_CARRY)) == 0, "unknown flags %#x", flags);
+                        AC_EMIT_REDUNDANT | AC_EMIT_CARRY | AC_IN_MIX)) == 0, "unknown flags %#x", flags);
+  if (flags & AC_IN_MIX) {
+    AC_REQUIRE(flags == (AC_IN_PACKED | AC_EMIT_PACKED | AC_IN_MIX),
+               "AC_IN_MIX goes with AC_IN_PACKED | AC_EMIT_PACKED alone (got %#x): the packed rows of several sources are mixed", flags);
+    return mix_packed_rows(mdct, psy, reinterpret_cast<const ac_mix_rows*>(x), X, t, thr, static_cast<const ac_packed_out*>(noisy_v),
+                           static_cast<int16_t*>(db_norm_v), B, K, C, stream);
+  }
   if (flags & (AC_EMIT_REDUNDANT | AC_EMIT_CARRY)) {
     AC_REQUIRE((flags & ~AC_EMIT_CARRY) == (AC_IN_PACKED | AC_EMIT_PACKED | AC_EMIT_REDUNDANT),
                "AC_EMIT_REDUNDANT goes with AC_IN_PACKED | AC_EMIT_PACKED alone, AC_EMIT_CARRY beside the three (got %#x): packed "

@@ -35,6 +35,8 @@ inline bool plans_match(const ac_mdct_plan* mdct, const ac_psy_plan* psy) {
   return mdct && psy && mdct->N == psy->N && mdct->device == psy->device;
 }
 int check_row_bytes(const ac_packed_out& po, const ac_psy_plan* psy);
+int check_rows_to_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* X, const float* t, const float* thr, int B,
+                       int K, int C, const char* flag);
 int mdct_inverse(const ac_mdct_plan* p, const float* X, void* x, bool pcm16, int B, int Kp, int C, void* stream);
 // Where both plans are wave-level the encode is one fused launch, except at filters_n = 2048 for mono input and for 16-bit
 // PCM with 3 or more channels, where the fused kernel would spill registers (7 / 4 at the 256 budget): there two wave-level

@@ -469,6 +469,13 @@ int launch_requantize_budget(const ac_psy_plan* p, const int16_t* codes_in, cons
 bool transrate_serves(const ac_psy_plan* psy);
 int launch_transrate(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes, const int64_t* index, uint8_t* out,
                      int64_t row_bytes, uint8_t* fits, int16_t* offset, long long rows, hipStream_t s);
+// ... of several sources summed bin by bin (k_mix_p, ac_mix.hip): src [sources_n] (host) holds data, nbytes
+// and index [rows] of every source, gain [sources_n] (host, or NULL: zeros) its scale-factor units, active [sources_n][rows]
+// (device, or NULL) which rows are read; out, fits, offset as launch_transrate's.  Where transrate_serves() and sources_n in
+// [1, AC_MIX_MAX_SOURCES]
+bool mix_serves(const ac_psy_plan* psy, int sources_n);
+int launch_mix(const ac_psy_plan* psy, int sources_n, const ac_packed_rows* src, const int32_t* gain, const uint8_t* active,
+               uint8_t* out, int64_t row_bytes, uint8_t* fits, int16_t* offset, long long rows, hipStream_t s);
 // ... and to protected slots (k_protect_p, ac_protect.hip): slot r of out [rows (row_bytes + red_bytes)]
 // holds launch_transrate's slot of row r, then -- for f >= 1 -- its slot of row r - C at the budget red_bits (zeros at f = 0);
 // fits, red_fits [rows], offset, red_offset [rows] (or NULL).  Where transrate_serves() and red_bits in [5 M, kPackRowsMaxBits]

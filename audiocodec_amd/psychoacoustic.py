@@ -155,6 +155,7 @@ class PsychoacousticModel:
         self._plans = _host.PlanCache(self, create, lib.ac_psy_plan_destroy)
         self._row_budget = None
         self._base = None
+        self._band_ids = {}       # device -> the band of every bin (mix_to_budget); shared with the models made from this one
 
     def with_row_budget(self, row_bits, min_offset=0):
         """A model with the same constants whose plans carry a row budget (``ac_psy_plan_with_row_budget``; DESIGN.md
@@ -499,6 +500,100 @@ class PsychoacousticModel:
                 int(min_offset), _host.ptr(out_codes), _host.ptr(out_sf), _host.ptr(offset), _host.ptr(bits), B, F, C,
                 _host.stream_ptr(dev)))
         return out_codes, out_sf, offset, bits
+
+    # ---- mixing quantised rows (extension) ----------------------------------------
+    @staticmethod
+    def _check_gains(gains, sources_n):
+        """``gains`` of a mix as a list of ``sources_n`` ints in [-254, 254]; None: zeros."""
+        if gains is None:
+            return [0] * sources_n
+        gains = list(gains)
+        if len(gains) != sources_n:
+            raise ValueError("%d gains for %d sources" % (len(gains), sources_n))
+        for g in gains:
+            if isinstance(g, bool) or not isinstance(g, (int, np.integer)):
+                raise TypeError("a gain must be an int (scale-factor units of 2^(1/4)), got %s" % type(g).__name__)
+            if not -254 <= int(g) <= 254:
+                raise ValueError("gain (%d) outside [-254, 254]" % g)
+        return [int(g) for g in gains]
+
+    def _check_active(self, active, sources_n, shape, device):
+        """``active`` of a mix: None, or a uint8 / bool tensor [S, B, F, C] on ``device``; returned as uint8."""
+        if active is None:
+            return None
+        if not isinstance(active, torch.Tensor):
+            raise TypeError("active must be a torch.Tensor or None, got %s" % type(active).__name__)
+        if active.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("active has dtype %s, expected torch.uint8 or torch.bool" % active.dtype)
+        if tuple(active.shape) != (sources_n,) + tuple(shape):
+            raise ValueError("active must have shape %s, got %s" % ((sources_n,) + tuple(shape), tuple(active.shape)))
+        if active.device != device:
+            raise ValueError("active lives on %s but the rows on %s" % (active.device, device))
+        active = active.contiguous()
+        return active.view(torch.uint8) if active.dtype == torch.bool else active
+
+    def _band_of_bins(self, device):
+        """int64 [N] on ``device``: the scale-factor band of every bin.  Built on the device from the host's offsets (no
+        copy that would wait for it) and kept per device."""
+        cache = self._band_ids
+        if device not in cache:
+            i = torch.arange(self.filter_bands_n, dtype=torch.int64, device=device)
+            band = torch.zeros_like(i)
+            for o in self.scale_band_offsets[1:-1].tolist():
+                band += i >= o
+            cache[device] = band
+        return cache[device]
+
+    def mix_to_budget(self, rows, gains, row_bits, active=None):
+        """Sums quantised rows of several sources in the spectral domain and quantises the sum to a budget (DESIGN.md
+        section 8h): ``rows`` a list of S pairs (codes int16 [B, F, N, C], sf int8 [B, F, M, C]) of equal shapes on one
+        device -> (codes, sf, offset int16 [B, F, C], row_bits_out int32 [B, F, C]) as :meth:`quantize_to_budget` returns them.
+
+        ``gains``: S ints in [-254, 254] in scale-factor units (one is 2^(1/4), 1.505 dB), or None; ``active``: None or a
+        uint8 / bool tensor [S, B, F, C], 0 = the row adds nothing.  Source i is dequantised at ``clamp(sf + gains[i], -127,
+        127)`` (a band with sf = -128 stays one: NaN), the spectra are added in float32 in source order, and the sum is
+        quantised by :meth:`quantize_to_budget` from offset 0 under a threshold that makes its scale factor at offset 0 the
+        band's s0: -128 where a source has the band at -128, else the largest gained scale factor over the sources that hold
+        a non-zero code in it, else 0 -- the coarsest step wins.  The input need not be canonical (as in
+        :meth:`requantize_to_budget`).  2 S + 1 library launches between torch's own; nothing waits for the device.
+        ``row_bits`` as in :meth:`quantize_to_budget`; not differentiable; float32 only."""
+        _host.require_float32(self.compute_dtype, "the quantiser")
+        rows = list(rows)
+        if not rows:
+            raise ValueError("mix_to_budget needs at least one source")
+        gains = self._check_gains(gains, len(rows))
+        pairs = []
+        for i, pair in enumerate(rows):
+            codes, sf = self._check_codes(*pair)
+            if pairs and (codes.shape != pairs[0][0].shape or codes.device != pairs[0][0].device):
+                raise ValueError("source %d has codes of shape %s on %s, source 0 of shape %s on %s"
+                                 % (i, tuple(codes.shape), codes.device, tuple(pairs[0][0].shape), pairs[0][0].device))
+            pairs.append((codes, sf))
+        B, F, N, C = pairs[0][0].shape
+        M, dev = self.bark_bands_n, pairs[0][0].device
+        active = self._check_active(active, len(pairs), (B, F, C), dev)
+        band = self._band_of_bins(dev)
+        total = bad = s0 = None
+        for i, (codes, sf) in enumerate(pairs):
+            is_bad = sf == -128
+            g = torch.where(is_bad, -128, (sf.to(torch.int16) + gains[i]).clamp_(-127, 127)).to(torch.int16)
+            X = self.dequantize(codes, g.to(torch.int8))
+            holds = torch.zeros((B, F, M, C), dtype=torch.int32, device=dev).index_add_(2, band, (codes != 0).to(torch.int32)) > 0
+            stored = holds & ~is_bad
+            if active is not None:
+                on = active[i].unsqueeze(2) != 0
+                X = torch.where(on, X, 0.0)
+                is_bad, stored = is_bad & on, stored & on
+            cand = torch.where(stored, g, -129)
+            total = X if total is None else total + X
+            bad = is_bad if bad is None else bad | is_bad
+            s0 = cand if s0 is None else torch.maximum(s0, cand)
+        s = torch.where(bad | (s0 == -129), 0, s0).to(torch.int32)   # (any finite threshold does where the band is bad)
+        r = s & 3
+        mant = torch.where(r == 0, 0, torch.where(r == 1, 0x1837f0, torch.where(r == 2, 0x3504f3, 0x5744fd))).to(torch.int32)
+        step = (((127 + (s >> 2)) << 23) | mant).view(torch.float32)      # step(s) = ldexp(fp32(2^((s & 3) / 4)), s >> 2)
+        thr = (step * float(np.float32(np.sqrt(np.float32(3.0))))).index_select(2, band)
+        return self.quantize_to_budget(total, thr, row_bits, 0)
 
     # ---- rate control per clip (extension; DESIGN.md section 8d) ---------------------------------------
     def quantize_to_clip_budget(self, mdct_amplitudes, masking_threshold, clip_bits, min_offset=0):

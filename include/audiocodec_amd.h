@@ -56,7 +56,8 @@ extern "C" {
                           * ac_stream_packed_lost_in; protected rows and the decode that recovers from them:
                           * AC_EMIT_REDUNDANT, ac_protected_out, ac_protect_launches, AC_CONCEAL_REDUNDANT,
                           * ac_conceal_redundant; the recovering decode chunk by chunk: ac_stream_packed_recover_in,
-                          * and protecting chunk by chunk: AC_EMIT_CARRY, ac_protect_carry, ac_protect_chunk_launches);
+                          * and protecting chunk by chunk: AC_EMIT_CARRY, ac_protect_carry, ac_protect_chunk_launches; rows
+                          * of several sources mixed without decoding: AC_IN_MIX, ac_mix_rows, ac_mix_launches);
                           * additions only, so the number stays.
                           * 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
                           * with a 5-smooth half up to 8192, float32); masking model for general band layouts up to 4096 bins.
@@ -295,8 +296,27 @@ AC_API int ac_encode_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
  *     AC_EINVAL.  So for any split into chunks the slots, flags and offsets, put together along frames, are those of the
  *     one-shot call on all rows.  Served where ac_protect_chunk_launches returns 1 (where ac_protect_launches does);
  *     AC_EUNSUPPORTED elsewhere, nothing written. */
+/*   AC_IN_MIX  mixing, valid only as AC_IN_PACKED | AC_EMIT_PACKED | AC_IN_MIX: the packed rows of
+ *     sources_n sources of the same codec and frame grid summed bin by bin in the spectral domain into fixed-stride packed
+ *     rows at the plan's row budget, in ONE launch that never decodes.  x addresses one ac_mix_rows (a host struct, read
+ *     during the call) whose src is a host array of sources_n ac_packed_rows, each with an index [B,K+1,C] of any int64 row
+ *     starts, read as ac_unpack reads them, damaged rows included; out0 addresses one ac_packed_out as under AC_IN_PACKED; out1
+ *     is NULL or int16_t* offset [B,K+1,C]; X, t and thr must be NULL.  gain (NULL: zeros) holds sources_n host ints in
+ *     [-254, 254] in scale-factor units of 2^(1/4); active (NULL: all ones) is a device uint8 [sources_n,B,K+1,C], 0 = the
+ *     row is never read and adds nothing.  With (q_i, s_i) the codes and scale factors ac_unpack returns for source i's row:
+ *     X_i = fp32(q_i * step(g_i)), g_i = -128 where s_i = -128 (X_i is NaN there), else clamp(s_i + gain[i], -127, 127); the sum
+ *     is ((X_0 + X_1) + X_2) + ... in float32; s0 of a band is -128 where any active source has it at -128, else the largest
+ *     g_i over the active sources that hold a non-zero code in it, else 0.  Slot r of data holds what ac_quantize_budget at
+ *     the plan's row_bits with kmin 0 gives for that sum under the threshold fp32(step(s0) * fp32(sqrt 3)) throughout each
+ *     band (its scale factor at offset 0 is then s0), sf = -128 in rows with row_bits_out > 8 row_bytes, ac_pack at r row_bytes
+ *     into zero-filled data; fits[r] and offset[r] as under AC_IN_PACKED.  A sum whose code passes +-32767 at offset 0 clamps
+ *     there, and the 16-bit widths make the search raise the offset.  With one source and gain 0 the bytes are those of the
+ *     AC_IN_PACKED call.  AC_EINVAL: any other combination with the bit, sources_n < 1, a gain outside [-254, 254], a NULL src
+ *     or source, a plan without a row budget; a refused call writes nothing.  Served where ac_mix_launches returns 1;
+ *     AC_EUNSUPPORTED elsewhere (run the composition).  Inputs and output must not overlap. */
 enum { AC_EMIT_NOISY = 1, AC_EMIT_DB_NORM = 2, AC_EMIT_CODES = 4, AC_EMIT_PACKED = 8, AC_IN_PCM16 = 32, AC_IN_PACKED = 64,
        AC_EMIT_REDUNDANT = 256, AC_EMIT_CARRY = 512 };
+enum { AC_IN_MIX = 1024 };   /* a flag of the same argument (above) */
 /* The largest row budget the one launch of AC_EMIT_PACKED serves: a wave stages both rows of its frame pair in the 4 KB of
  * its LDS buffer that the masking model has left, 2 KB = 16384 bits each. */
 #define AC_PACK_ROWS_MAX_BITS 16384
@@ -322,6 +342,14 @@ typedef struct ac_protect_carry {
   uint8_t* fits_out;
   int16_t* offset_out;
 } ac_protect_carry;
+#define AC_MIX_MAX_SOURCES 8 /* the most sources the one launch of AC_IN_MIX reads */
+struct ac_packed_rows;
+typedef struct ac_mix_rows {
+  int32_t sources_n;                 /* >= 1 */
+  const struct ac_packed_rows* src;  /* [sources_n] (host): data, nbytes, index [B,K+1,C] of every source */
+  const int32_t* gain;               /* [sources_n] (host) scale-factor units in [-254, 254], or NULL: zeros */
+  const uint8_t* active;             /* [sources_n,B,K+1,C] (device) 0 = the row is never read, or NULL: all ones */
+} ac_mix_rows;
 AC_API int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
                        float drown, int flags, void* out0, void* out1, uint64_t seed, int B, int K, int C,
                        void* stream);
@@ -347,6 +375,12 @@ AC_API int ac_encode_packed_launches_pcm16(const ac_mdct_plan* mdct, const ac_ps
  * of the composition above (also everywhere while AC_TRANSRATE_NOFUSE=1 is set in the environment: read per call).  0 for a
  * NULL plan, C < 1, or a plan without a row budget.  The bytes do not depend on it. */
 AC_API int ac_transrate_launches(const ac_psy_plan* psy, int C);
+/* Library launches of mixing the rows of S sources of C channels to the plan's row budget: 1 = ac_encode_fused_ex with
+ * AC_IN_PACKED | AC_EMIT_PACKED | AC_IN_MIX serves it (where ac_transrate_launches returns 1 and S <= AC_MIX_MAX_SOURCES), else
+ * 2 S + 2: S ac_unpack, S ac_dequantize, ac_quantize_budget and ac_pack of the composition above (also everywhere while
+ * AC_MIX_NOFUSE=1 is set in the environment: read per call).  0 for a NULL plan, C < 1, S < 1 or a plan without a row budget.
+ * The bytes do not depend on it. */
+AC_API int ac_mix_launches(const ac_psy_plan* psy, int C, int S);
 /* Library launches of protecting rows of C channels with a redundant budget of red_bits: 1 = ac_encode_fused_ex with
  * AC_IN_PACKED | AC_EMIT_PACKED | AC_EMIT_REDUNDANT serves it (where ac_transrate_launches returns 1 and red_bits is at most
  * AC_PACK_ROWS_MAX_BITS), else the launches of the composition's two transrating calls, each 1 or 3 (also everywhere while

@@ -16,7 +16,7 @@ the one launch on int16 (k_fwd_fast_qp16 / qps16), the conversion to(float32) / 
 caller did before), and the float32 one launch on a resident float32 tensor; compared byte for byte, then alternating
 (profiles/pack/pack_bench_pcm16.txt).
 python tools/pack_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7] [--round-steps 30]
-                           [--row-bits 1365] [--only-rows] [--stream] [--pcm16] [--transrate [--targets 1365 682]] [--conceal] [--conceal-stream] [--protect]
+                           [--row-bits 1365] [--only-rows] [--stream] [--pcm16] [--transrate [--targets 1365 682]] [--conceal] [--conceal-stream] [--protect] [--mix]
 --transrate: rows at 2730 bits transrated to each of --targets (transrate_rows(); profiles/pack/pack_bench_transrate.txt).
 --conceal: decode_packed with lost rows concealed -- none lost, and 1 % lost at random -- against decode_packed without `lost`
 (conceal_rows(); profiles/pack/pack_bench_conceal.txt).
@@ -26,7 +26,10 @@ decode_packed_chunk without `lost` (conceal_stream_rows(); profiles/pack/pack_be
 redundant_at against without (protect_rows(); profiles/pack/pack_bench_protect.txt).
 --protect-stream [--red-bits 341]: decode_packed_chunk with redundant_at chunk by chunk on a StreamingMDCT, against the concealing
 chunk on the same `lost` and against its composition; then protect_chunk against the one-shot protect_packed_rows on the same rows
-and against its composition (protect_stream_rows(); profiles/pack/pack_bench_protect_stream.txt)."""
+and against its composition (protect_stream_rows(); profiles/pack/pack_bench_protect_stream.txt).
+--mix [--sources 2 4]: mix_packed_rows of S sources at 2730 bits to 1365 in its one launch, against its composition, the decode
+route (S decode_packed, the adds, encode_packed_rows) and transrate_packed_rows of one source (mix_rows();
+profiles/pack/pack_bench_mix.txt)."""
 import argparse
 import ctypes
 import os
@@ -352,6 +355,63 @@ def protect_rows(a):
                [("(b) / (a)", 1, 0), ("(d) / (c)", 3, 2), ("(d) / (e)", 3, 4)])
 
 
+def mix_rows(a):
+    """Mixing: --sources S sources (2 and 4) of encode_packed_rows at 2730 bits, mixed to 1365.  (a)
+    mix_packed_rows in its one launch (k_mix_p); (b) its composition (AC_MIX_NOFUSE=1, read per call); (c) the decode route:
+    S decode_packed, the adds, encode_packed_rows; (d) transrate_packed_rows of one source alone, the S = 1 floor.  The two
+    forms are compared byte for byte first, then all alternate, --rounds rounds of --round-steps."""
+    B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    base = audiocodec_amd.AudioCodec(48000, N)
+    src, dst = base.with_row_budget(2730), base.with_row_budget(1365)
+    gen = torch.Generator("cuda").manual_seed(0)
+    all_sources = []
+    for _ in range(max(a.sources)):
+        x = torch.rand((B, K * N, C), device="cuda", generator=gen) * 2 - 1
+        all_sources.append(src.encode_packed_rows(x)[:2])
+        del x
+    rows = all_sources[0][1].numel()
+    print("mix: B=%d K=%d N=%d C=%d  rows=%d per source at 2730 bits (%.1f MB each) -> 1365 bits (%.1f MB)  %s"
+          % (B, K, N, C, rows, all_sources[0][0].numel() / 1e6, rows * dst.row_bytes / 1e6, torch.cuda.get_device_name()))
+
+    def composition(sources, offset=False):
+        os.environ["AC_MIX_NOFUSE"] = "1"   # (read per call)
+        try:
+            return dst.mix_packed_rows(sources, None, None, offset)
+        finally:
+            del os.environ["AC_MIX_NOFUSE"]
+
+    def decode_route(sources):
+        pcm = dst.decode_packed(*sources[0])
+        for d, i in sources[1:]:
+            pcm = pcm + dst.decode_packed(d, i)
+        return dst.encode_packed_rows(pcm[:, N:-N].contiguous())   # (K + 1 frames decode to K + 2 blocks: the K in the middle)
+
+    for S in a.sources:
+        sources = all_sources[:S]
+        one, two = dst.mix_packed_rows(sources, None, None, True), composition(sources, True)
+        assert all(torch.equal(g, r) for g, r in zip(one, two)), "the two forms differ"
+        print("S = %d: launches %d (composition %d); the one launch and the composition agree byte for byte; %d rows do not fit; "
+              "%.1f %% of the rows at offset 0, mean offset %.2f" % (S, dst.mix_packed_rows_launches(C, sources_n=S), 2 * S + 2,
+                                                                    int((~one[2]).sum()), 100.0 * float((one[3] == 0).float().mean()), float(one[3].float().mean())))
+        del one, two
+        forms = [("(a) mix_packed_rows, %d launch" % dst.mix_packed_rows_launches(C, sources_n=S), lambda: dst.mix_packed_rows(sources)),
+                 ("(b) mix_packed_rows, composition", lambda: composition(sources)),
+                 ("(c) %d decode_packed + adds + encode_packed_rows" % S, lambda: decode_route(sources)),
+                 ("(d) transrate_packed_rows of one source", lambda: dst.transrate_packed_rows(*sources[0]))]
+        runs = dict((n, []) for n, _ in forms)
+        for _ in range(a.rounds):
+            for n, fn in forms:
+                runs[n].append(timed(fn, a.round_steps, 1))
+        med = []
+        for n, _ in forms:
+            v = sorted(runs[n])
+            med.append(v[len(v) // 2])
+            print("  %-52s median %.3f ms  min %.3f  max %.3f  (%d alternating rounds of %d)" % (n, med[-1], v[0], v[-1], len(v), a.round_steps))
+        read = S * all_sources[0][0].numel() + rows * dst.row_bytes
+        print("  (a) / (b) = %.3f   (a) / (c) = %.3f   (a) / (d) = %.3f   per added source: %.3f of one transrate   (a) moves %.1f MB: %.0f GB/s"
+              % (med[0] / med[1], med[0] / med[2], med[0] / med[3], (med[0] - med[3]) / max(S - 1, 1) / med[3], read / 1e6, read / med[0] / 1e6))
+
+
 def conceal_rows(a):
     """Concealment of lost rows on the rows of encode_packed_rows at --row-bits: (a) decode_packed
     without `lost`, the yardstick; (b) with `lost` all false; (c) with 1 % of the rows lost at random, max_age 8 -- both the
@@ -583,6 +643,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--protect-stream", action="store_true", help="only decode_packed_chunk with redundant_at, against the concealing chunk and its composition")
     ap.add_argument("--conceal-stream", action="store_true", help="only decode_packed_chunk with lost rows concealed, against without")
+    ap.add_argument("--mix", action="store_true", help="only mix_packed_rows: --sources sources at 2730 bits mixed to 1365")
+    ap.add_argument("--sources", type=int, nargs="+", default=[2, 4], help="the source counts of --mix")
     ap.add_argument("--protect", action="store_true", help="only protect_packed_rows and the recovering decode (2730 -> 1365 with --red-bits)")
     ap.add_argument("--red-bits", type=int, default=341, help="the redundant budget of --protect (16 kbit/s)")
     ap.add_argument("--conceal", action="store_true", help="only decode_packed with lost rows concealed, against without")
@@ -604,6 +666,8 @@ def main():
     B, K, N, C = a.clips, a.blocks, a.filters, a.channels
     if a.protect_stream:
         return protect_stream_rows(a)
+    if a.mix:
+        return mix_rows(a)
     if a.protect:
         return protect_rows(a)
     if a.conceal:
