@@ -24,6 +24,10 @@ AC_EMIT_REDUNDANT = 256   # beside AC_IN_PACKED | AC_EMIT_PACKED: out0 is one ac
 AC_EMIT_CARRY = 512   # beside the three flags of protecting: the rows are a chunk of a stream, out1 is one ac_protect_carry
 AC_IN_MIX = 1024   # beside AC_IN_PACKED | AC_EMIT_PACKED: x is one ac_mix_rows (the rows of several sources mixed)
 AC_MIX_MAX_SOURCES = 8   # the most sources the one launch of AC_IN_MIX reads (the header's macro)
+AC_IN_ROUTE = 2048   # beside AC_IN_PACKED | AC_EMIT_PACKED: x is one ac_route_rows (the rows of several sources to several mixes)
+AC_ROUTE_MAX_SOURCES = 4   # the most sources and ...
+AC_ROUTE_MAX_OUTPUTS = 8   # ... outputs the one launch of AC_IN_ROUTE serves (the header's macros)
+AC_ROUTE_MUTE = -32768   # in ac_route_rows' gain: the output does not hear the source (the header's macro)
 AC_CONCEAL_REDUNDANT = 256   # in ac_conceal's max_age: the struct is an ac_conceal_redundant (lost rows recovered)
 AC_CONCEAL = 128   # beside AC_PACKED in ac_stream_inverse_typed's dtype: X_chunk is one ac_stream_packed_lost_in
 AC_PACK_ROWS_MAX_BITS = 16384 # the largest row budget AC_EMIT_PACKED serves in one launch (the header's macro)
@@ -129,6 +133,7 @@ PROTOTYPES = {
     "ac_stream_packed_launches_pcm16": (c_int, [c_void_p, c_void_p]),
     "ac_transrate_launches": (c_int, [c_void_p, c_int]),
     "ac_mix_launches": (c_int, [c_void_p, c_int, c_int]),
+    "ac_route_launches": (c_int, [c_void_p, c_int, c_int, c_int]),
     "ac_protect_launches": (c_int, [c_void_p, c_int, c_int]),
     "ac_protect_chunk_launches": (c_int, [c_void_p, c_int, c_int]),
     "ac_pack_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
@@ -152,6 +157,12 @@ class PackedRows(ctypes.Structure):
 class MixRows(ctypes.Structure):
     """``ac_mix_rows``: what ``ac_encode_fused_ex`` takes for ``x`` under ``AC_IN_MIX``."""
     _fields_ = [("sources_n", ctypes.c_int32), ("src", POINTER(PackedRows)), ("gain", POINTER(ctypes.c_int32)), ("active", c_void_p)]
+
+
+class RouteRows(ctypes.Structure):
+    """``ac_route_rows``: what ``ac_encode_fused_ex`` takes for ``x`` under ``AC_IN_ROUTE``."""
+    _fields_ = [("sources_n", ctypes.c_int32), ("outputs_n", ctypes.c_int32), ("src", POINTER(PackedRows)),
+                ("gain", POINTER(ctypes.c_int32)), ("active", c_void_p)]
 
 
 class Conceal(ctypes.Structure):

@@ -12,6 +12,7 @@ from __future__ import annotations
 import copy
 import ctypes
 import math
+import os
 
 import numpy as np
 import torch
@@ -541,6 +542,120 @@ class AudioCodec:
         unpacked = [self.psy.unpack(d, ix) for d, ix in pairs]
         codes, sf, offset, bits = self.psy.mix_to_budget(unpacked, gains, self.row_bits, active)
         out_data, fits = _pack_rows_of_codes(self.psy, codes, sf, bits, index_out, rb)
+        return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
+
+    # ---- routing the packed rows of several sources to several mixes (extension) --------------
+    @staticmethod
+    def mix_minus_routes(sources_n, gains=None):
+        """The route table of a conference bridge for :meth:`route_packed_rows`: ``sources_n`` outputs, output o hears every
+        source but o, source i at ``gains[i]`` (default 0) -- ``None`` on the diagonal."""
+        if isinstance(sources_n, bool) or not isinstance(sources_n, (int, np.integer)):
+            raise TypeError("sources_n must be an int, got %s" % type(sources_n).__name__)
+        if sources_n < 1:
+            raise ValueError("mix_minus_routes needs at least one source, got %d" % sources_n)
+        gains = PsychoacousticModel._check_gains(gains, int(sources_n))
+        return [[None if i == o else gains[i] for i in range(sources_n)] for o in range(sources_n)]
+
+    @staticmethod
+    def _check_routes(routes, sources_n):
+        """``routes`` of :meth:`route_packed_rows` as a list of O >= 1 lists of ``sources_n`` entries, each an int in
+        [-254, 254] or None."""
+        routes = [list(row) for row in routes]
+        if not routes:
+            raise ValueError("route_packed_rows needs at least one output")
+        for o, row in enumerate(routes):
+            if len(row) != sources_n:
+                raise ValueError("route %d has %d entries for %d sources" % (o, len(row), sources_n))
+            for g in row:
+                if g is None:
+                    continue
+                if isinstance(g, bool) or not isinstance(g, (int, np.integer)):
+                    raise TypeError("a route's gain must be an int (scale-factor units of 2^(1/4)) or None, got %s" % type(g).__name__)
+                if not -254 <= int(g) <= 254:
+                    raise ValueError("gain (%d) of route %d outside [-254, 254]" % (g, o))
+        return [[None if g is None else int(g) for g in row] for row in routes]
+
+    def route_packed_rows_launches(self, channels_n=2, device=None, *, sources_n, outputs_n):
+        """Library launches :meth:`route_packed_rows` takes for ``outputs_n`` outputs that each hear ``sources_n`` sources of
+        ``channels_n`` channels (``ac_route_launches``): 1 = one kernel stages every source row once and packs every output's
+        row from it (where :meth:`mix_packed_rows_launches` is 1, ``sources_n`` is at most ``_lib.AC_ROUTE_MAX_SOURCES`` and ``outputs_n`` at most
+        ``_lib.AC_ROUTE_MAX_OUTPUTS``),
+        else ``outputs_n`` times :meth:`mix_packed_rows_launches`, the composition (everywhere while ``AC_ROUTE_NOFUSE=1`` is
+        set: read per call).  0 on a codec without a row budget."""
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return int(self._lib.ac_route_launches(self.psy._plan(dev), int(channels_n), int(sources_n), int(outputs_n)))
+
+    def route_packed_rows(self, sources, routes, active=None, return_offset=False):
+        """On a codec made by :meth:`with_bitrate` / :meth:`with_row_budget`: the packed rows of S sources -> O mixes of
+        them at this codec's bitrate, without decoding -- a bridge's mix-minus (:meth:`mix_minus_routes`), monitor mixes,
+        talk-over at a level per listener.  ``sources`` and ``active`` are :meth:`mix_packed_rows`'; ``routes`` holds O >= 1
+        sequences of S entries, each an int gain in [-254, 254] in scale-factor units or ``None``: the output does not hear
+        that source -> (data' uint8 [O, B*F*C*row_bytes], index' int64 [B, F, C], fits' bool [O, B, F, C]), and offset int16
+        [O, B, F, C] with ``return_offset=True``.  ``(data'[o], index')`` is a packed-rows pair as
+        :meth:`encode_packed_rows` returns it.
+
+        Output o is, byte for byte, flags and offsets included, ``mix_packed_rows`` of the sources it hears, in source order,
+        at its gains, with their part of ``active``; an output that hears nothing holds the slots of a mix whose sources are
+        all inactive.  A damaged row or a band without a finite scale factor spoils only the outputs that hear it, and a row
+        that no output hears is never read.  One launch where :meth:`route_packed_rows_launches` is 1 -- every source row is
+        read and parsed once, not once per output that hears it -- else one :meth:`mix_packed_rows` per output: the same
+        bytes.  It never synchronises with the device, only enqueues on the current stream, and can be captured in a graph.
+        float32 only."""
+        _host.require_float32(self.compute_dtype, "route_packed_rows")
+        if self.row_bits is None:
+            raise ValueError("route_packed_rows needs a codec with a row budget: make one with with_bitrate() or with_row_budget()")
+        sources = list(sources)
+        if not sources:
+            raise ValueError("route_packed_rows needs at least one source")
+        S = len(sources)
+        routes = self._check_routes(routes, S)
+        O = len(routes)
+        pairs = []
+        for i, (data, index) in enumerate(sources):
+            data = self.psy._check_quant_tensor(data, "data of source %d" % i, torch.uint8, ndim=1)
+            index = self.psy._check_quant_tensor(index, "index of source %d" % i, torch.int64, device=data.device, ndim=3)
+            if pairs and (index.shape != pairs[0][1].shape or index.device != pairs[0][1].device):
+                raise ValueError("index of source %d has shape %s on %s, that of source 0 shape %s on %s"
+                                 % (i, tuple(index.shape), index.device, tuple(pairs[0][1].shape), pairs[0][1].device))
+            pairs.append((data, index))
+        B, F, C = pairs[0][1].shape
+        dev, rb = pairs[0][1].device, self.row_bytes
+        active = self.psy._check_active(active, S, (B, F, C), dev)
+        rows = B * F * C
+        index_out = (torch.arange(rows, dtype=torch.int64, device=dev) * rb).view(B, F, C)
+        out_data = torch.empty((O, rows * rb), dtype=torch.uint8, device=dev)
+        fits = torch.empty((O, B, F, C), dtype=torch.bool, device=dev)
+        offset = torch.empty((O, B, F, C), dtype=torch.int16, device=dev) if return_offset else None
+        if rows == 0:
+            return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
+        psy = self.psy._plan(dev)
+        # (a single output's composition is one launch too: the switch itself decides there)
+        if self._lib.ac_route_launches(psy, C, S, O) == 1 and os.environ.get("AC_ROUTE_NOFUSE") != "1":
+            src = (_lib.PackedRows * S)(*[_lib.PackedRows(d.data_ptr(), d.numel(), ix.data_ptr()) for d, ix in pairs])
+            gain = (ctypes.c_int32 * (O * S))(*[_lib.AC_ROUTE_MUTE if g is None else g for row in routes for g in row])
+            route = _lib.RouteRows(S, O, src, gain, active.data_ptr() if active is not None else None)
+            dst = _lib.PackedOut(out_data.data_ptr(), rb, fits.data_ptr())
+            with _host.on_device(dev):
+                _lib.check(self._lib.ac_encode_fused_ex(self.mdct._plan(dev), psy, ctypes.addressof(route), None, None, None, 0.0,
+                                                        _lib.AC_IN_PACKED | _lib.AC_EMIT_PACKED | _lib.AC_IN_ROUTE,
+                                                        ctypes.addressof(dst), _host.ptr(offset) if return_offset else None, 0,
+                                                        B, F - 1, C, _host.stream_ptr(dev)))
+            return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
+        # the composition: one mix per output on the sources it hears (an output that hears nothing: source 0, never read)
+        silent = None
+        for o, row in enumerate(routes):
+            inc = [i for i, g in enumerate(row) if g is not None]
+            if inc:
+                act = None if active is None else torch.stack([active[i] for i in inc])   # (no index tensor: nothing to upload)
+                one = self.mix_packed_rows([pairs[i] for i in inc], [row[i] for i in inc], act, return_offset)
+            else:
+                if silent is None:
+                    silent = torch.zeros((1, B, F, C), dtype=torch.uint8, device=dev)
+                one = self.mix_packed_rows(pairs[:1], [0], silent, return_offset)
+            out_data[o].copy_(one[0])
+            fits[o].copy_(one[2])
+            if return_offset:
+                offset[o].copy_(one[3])
         return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
 
     # ---- protected rows: a redundant copy of the frame before in every slot (extension; DESIGN.md section 8g) ---

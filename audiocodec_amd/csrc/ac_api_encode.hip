@@ -110,6 +110,11 @@ static bool mix_fuses(const ac_psy_plan* psy, int S) {
   if (env_is_1("AC_MIX_NOFUSE")) return false;
   return transrate_fuses(psy) && mix_serves(psy, S);
 }
+// whether the packed rows of S sources are routed to O outputs in one launch (k_route_p); AC_ROUTE_NOFUSE=1: as above
+static bool route_fuses(const ac_psy_plan* psy, int S, int O) {
+  if (env_is_1("AC_ROUTE_NOFUSE")) return false;
+  return mix_fuses(psy, S) && route_serves(psy, S, O);
+}
 // whether packed rows are protected in one launch (k_protect_p); AC_PROTECT_NOFUSE=1: as above
 static bool protect_fuses(const ac_psy_plan* psy, int red_bits) {
   if (env_is_1("AC_PROTECT_NOFUSE")) return false;
@@ -395,6 +400,53 @@ static int mix_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, con
                     (long long)B * (K + 1) * C, (hipStream_t)stream);
 }
 
+int ac_route_launches(const ac_psy_plan* psy, int C, int S, int O) {
+  if (!psy || C < 1 || S < 1 || O < 1 || !psy->row_bits) return 0;
+  return route_fuses(psy, S, O) ? 1 : O * ac_mix_launches(psy, C, S);   // the AC_IN_MIX call of every output
+}
+
+// ac_encode_fused_ex with AC_IN_PACKED | AC_EMIT_PACKED | AC_IN_ROUTE: rows [B,K+1,C] of every source of `in` mixed into slots of
+// every output of `out` at the plan's row budget
+static int route_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const ac_route_rows* in, const float* X,
+                             const float* t, const float* thr, const ac_packed_out* out, int16_t* offset, int B, int K, int C,
+                             void* stream) {
+  int st = check_rows_to_rows(mdct, psy, X, t, thr, B, K, C, "AC_IN_ROUTE");
+  if (st) return st;
+  AC_REQUIRE(in != nullptr, "AC_IN_ROUTE without its ac_route_rows (x)");
+  AC_REQUIRE(out != nullptr, "AC_IN_ROUTE without its ac_packed_out (out0)");
+  const ac_route_rows route = *in;
+  const ac_packed_out po = *out;
+  st = check_row_bytes(po, psy);
+  if (st) return st;
+  AC_REQUIRE(route.sources_n >= 1, "sources_n (%d) below 1", (int)route.sources_n);
+  AC_REQUIRE(route.outputs_n >= 1, "outputs_n (%d) below 1", (int)route.outputs_n);
+  AC_REQUIRE(route.src != nullptr, "ac_route_rows: src is NULL");
+  AC_REQUIRE(route.gain != nullptr, "ac_route_rows: gain is NULL");
+  for (long long k = 0; k < (long long)route.outputs_n * route.sources_n; ++k)
+    AC_REQUIRE(route.gain[k] == AC_ROUTE_MUTE || (route.gain[k] >= -254 && route.gain[k] <= 254),
+               "gain[%lld] (%d) is neither in [-254, 254] nor AC_ROUTE_MUTE", k, (int)route.gain[k]);
+  for (int i = 0; i < route.sources_n; ++i) {
+    AC_REQUIRE(route.src[i].nbytes >= 0, "source %d: negative nbytes (%lld)", i, (long long)route.src[i].nbytes);
+    AC_REQUIRE(route.src[i].index != nullptr || B == 0 || C == 0, "source %d: index is NULL", i);
+  }
+  if (B == 0 || C == 0) return AC_OK;
+  if (!route_fuses(psy, route.sources_n, route.outputs_n)) {
+    set_error("AC_IN_ROUTE: no kernel routes the packed rows of %d sources to %d outputs in one launch for filters_n = %d, "
+              "bark_bands_n = %d, row budget %d here (ac_route_launches() != 1): use the composition -- AC_IN_MIX per output on the "
+              "sources it hears, in source order, at its gains", (int)route.sources_n, (int)route.outputs_n, psy->N, psy->M,
+              psy->row_bits);
+    return AC_EUNSUPPORTED;
+  }
+  for (int i = 0; i < route.sources_n; ++i) {
+    st = check_packed_rows(route.src[i], true, po.data != nullptr && po.fits != nullptr);
+    if (st) return st;
+  }
+  AC_REQUIRE_ALIGNED(po.data, offset);
+  DeviceGuard guard(psy->device);
+  return launch_route(psy, route.sources_n, route.outputs_n, route.src, route.gain, route.active, po.data, po.row_bytes, po.fits,
+                      offset, (long long)B * (K + 1) * C, (hipStream_t)stream);
+}
+
 int ac_protect_launches(const ac_psy_plan* psy, int C, int red_bits) {
   if (!psy || C < 1 || !psy->row_bits || red_bits < 5 * psy->M) return 0;
   if (protect_fuses(psy, red_bits)) return 1;
@@ -461,7 +513,14 @@ int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const f
                        float drown, int flags, void* noisy_v, void* db_norm_v, uint64_t seed, int B, int K, int C,
                        void* stream) {
   AC_REQUIRE((flags & ~(AC_EMIT_NOISY | AC_EMIT_DB_NORM | AC_EMIT_CODES | AC_EMIT_PACKED | AC_IN_PCM16 | AC_IN_PACKED |
-                        AC_EMIT_REDUNDANT | AC_EMIT_CARRY | AC_IN_MIX)) == 0, "unknown flags %#x", flags);
+                        AC_EMIT_REDUNDANT | AC_EMIT_CARRY | AC_IN_MIX | AC_IN_ROUTE)) == 0, "unknown flags %#x", flags);
+  if (flags & AC_IN_ROUTE) {
+    AC_REQUIRE(flags == (AC_IN_PACKED | AC_EMIT_PACKED | AC_IN_ROUTE),
+               "AC_IN_ROUTE goes with AC_IN_PACKED | AC_EMIT_PACKED alone (got %#x): the packed rows of several sources are routed to "
+               "several mixes", flags);
+    return route_packed_rows(mdct, psy, reinterpret_cast<const ac_route_rows*>(x), X, t, thr,
+                             static_cast<const ac_packed_out*>(noisy_v), static_cast<int16_t*>(db_norm_v), B, K, C, stream);
+  }
   if (flags & AC_IN_MIX) {
     AC_REQUIRE(flags == (AC_IN_PACKED | AC_EMIT_PACKED | AC_IN_MIX),
                "AC_IN_MIX goes with AC_IN_PACKED | AC_EMIT_PACKED alone (got %#x): the packed rows of several sources are mixed", flags);

@@ -476,6 +476,14 @@ int launch_transrate(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes
 bool mix_serves(const ac_psy_plan* psy, int sources_n);
 int launch_mix(const ac_psy_plan* psy, int sources_n, const ac_packed_rows* src, const int32_t* gain, const uint8_t* active,
                uint8_t* out, int64_t row_bytes, uint8_t* fits, int16_t* offset, long long rows, hipStream_t s);
+// ... and routed into outputs_n mixes, every source row read once (k_route_p, ac_route.hip): gain
+// [outputs_n * sources_n] (host) holds AC_ROUTE_MUTE where output o does not hear source i; out [outputs_n][rows row_bytes], fits
+// and offset (or NULL) [outputs_n][rows].  Where transrate_serves(), sources_n in [1, AC_ROUTE_MAX_SOURCES] and outputs_n in
+// [1, AC_ROUTE_MAX_OUTPUTS]
+bool route_serves(const ac_psy_plan* psy, int sources_n, int outputs_n);
+int launch_route(const ac_psy_plan* psy, int sources_n, int outputs_n, const ac_packed_rows* src, const int32_t* gain,
+                 const uint8_t* active, uint8_t* out, int64_t row_bytes, uint8_t* fits, int16_t* offset, long long rows,
+                 hipStream_t s);
 // ... and to protected slots (k_protect_p, ac_protect.hip): slot r of out [rows (row_bytes + red_bytes)]
 // holds launch_transrate's slot of row r, then -- for f >= 1 -- its slot of row r - C at the budget red_bits (zeros at f = 0);
 // fits, red_fits [rows], offset, red_offset [rows] (or NULL).  Where transrate_serves() and red_bits in [5 M, kPackRowsMaxBits]

@@ -57,7 +57,8 @@ extern "C" {
                           * AC_EMIT_REDUNDANT, ac_protected_out, ac_protect_launches, AC_CONCEAL_REDUNDANT,
                           * ac_conceal_redundant; the recovering decode chunk by chunk: ac_stream_packed_recover_in,
                           * and protecting chunk by chunk: AC_EMIT_CARRY, ac_protect_carry, ac_protect_chunk_launches; rows
-                          * of several sources mixed without decoding: AC_IN_MIX, ac_mix_rows, ac_mix_launches);
+                          * of several sources mixed without decoding: AC_IN_MIX, ac_mix_rows, ac_mix_launches; and routed
+                          * to several mixes: AC_IN_ROUTE, ac_route_rows, ac_route_launches);
                           * additions only, so the number stays.
                           * 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
                           * with a 5-smooth half up to 8192, float32); masking model for general band layouts up to 4096 bins.
@@ -317,6 +318,19 @@ AC_API int ac_encode_launches(const ac_mdct_plan* mdct, const ac_psy_plan* psy, 
 enum { AC_EMIT_NOISY = 1, AC_EMIT_DB_NORM = 2, AC_EMIT_CODES = 4, AC_EMIT_PACKED = 8, AC_IN_PCM16 = 32, AC_IN_PACKED = 64,
        AC_EMIT_REDUNDANT = 256, AC_EMIT_CARRY = 512 };
 enum { AC_IN_MIX = 1024 };   /* a flag of the same argument (above) */
+/*   AC_IN_ROUTE  routing, valid only as AC_IN_PACKED | AC_EMIT_PACKED | AC_IN_ROUTE: the packed rows of
+ *     sources_n sources mixed into outputs_n outputs (a bridge's mix-minus, monitor mixes) in ONE launch that reads every
+ *     source row once and never decodes.  x addresses one ac_route_rows (a host struct, read during the call): src and active
+ *     as ac_mix_rows', gain a host array [outputs_n * sources_n], gain[o * sources_n + i] in [-254, 254] or AC_ROUTE_MUTE:
+ *     output o does not hear source i.  out0 addresses one ac_packed_out whose data is [outputs_n][B (K+1) C row_bytes] and
+ *     fits [outputs_n][B,K+1,C]; out1 is NULL or int16_t* offset [outputs_n][B,K+1,C]; X, t and thr must be NULL.  Output o
+ *     is, byte for byte, flags and offsets included, what AC_IN_MIX gives for the sources it hears, in source order, at its
+ *     gains, with their rows of active; an output that hears nothing is the slot of a mix whose sources are all inactive.
+ *     A row that no output hears, or that is inactive, is never read.  AC_EINVAL: any other combination with the bit,
+ *     sources_n < 1, outputs_n < 1, a gain outside [-254, 254] that is not AC_ROUTE_MUTE, a NULL src, gain or source, a plan
+ *     without a row budget; a refused call writes nothing.  Served where ac_route_launches returns 1; AC_EUNSUPPORTED
+ *     elsewhere (run AC_IN_MIX, or its composition, per output).  Inputs and output must not overlap. */
+enum { AC_IN_ROUTE = 2048 };   /* a flag of the same argument (above) */
 /* The largest row budget the one launch of AC_EMIT_PACKED serves: a wave stages both rows of its frame pair in the 4 KB of
  * its LDS buffer that the masking model has left, 2 KB = 16384 bits each. */
 #define AC_PACK_ROWS_MAX_BITS 16384
@@ -350,6 +364,17 @@ typedef struct ac_mix_rows {
   const int32_t* gain;               /* [sources_n] (host) scale-factor units in [-254, 254], or NULL: zeros */
   const uint8_t* active;             /* [sources_n,B,K+1,C] (device) 0 = the row is never read, or NULL: all ones */
 } ac_mix_rows;
+#define AC_ROUTE_MAX_SOURCES 4 /* the most sources and ... */
+#define AC_ROUTE_MAX_OUTPUTS 8 /* ... outputs the one launch of AC_IN_ROUTE serves (section 8i: beyond four sources the
+                                * staged rows leave too few waves on a CU, and one AC_IN_MIX call per output is faster) */
+#define AC_ROUTE_MUTE (-32768) /* in ac_route_rows' gain: the output does not hear the source */
+typedef struct ac_route_rows {
+  int32_t sources_n;                 /* >= 1 */
+  int32_t outputs_n;                 /* >= 1 */
+  const struct ac_packed_rows* src;  /* [sources_n] (host): data, nbytes, index [B,K+1,C] of every source */
+  const int32_t* gain;               /* [outputs_n * sources_n] (host): [-254, 254] or AC_ROUTE_MUTE */
+  const uint8_t* active;             /* [sources_n,B,K+1,C] (device) 0 = the row is never read, or NULL: all ones */
+} ac_route_rows;
 AC_API int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const float* x, float* X, float* t, float* thr,
                        float drown, int flags, void* out0, void* out1, uint64_t seed, int B, int K, int C,
                        void* stream);
@@ -381,6 +406,13 @@ AC_API int ac_transrate_launches(const ac_psy_plan* psy, int C);
  * AC_MIX_NOFUSE=1 is set in the environment: read per call).  0 for a NULL plan, C < 1, S < 1 or a plan without a row budget.
  * The bytes do not depend on it. */
 AC_API int ac_mix_launches(const ac_psy_plan* psy, int C, int S);
+/* Library launches of routing the rows of S sources of C channels to O outputs that hear all of them: 1 = ac_encode_fused_ex
+ * with AC_IN_PACKED | AC_EMIT_PACKED | AC_IN_ROUTE serves it (where ac_mix_launches returns 1 for S, S <= AC_ROUTE_MAX_SOURCES and O <=
+ * AC_ROUTE_MAX_OUTPUTS), else O ac_mix_launches(psy, C, S), the AC_IN_MIX calls of the composition (an output that hears
+ * fewer sources takes ac_mix_launches of its count; also everywhere while AC_ROUTE_NOFUSE=1 is set in the environment: read
+ * per call -- with O = 1 that count is 1 too, and the call is refused all the same while the variable is set).  0 for a NULL
+ * plan, C < 1, S < 1, O < 1 or a plan without a row budget.  The bytes do not depend on it. */
+AC_API int ac_route_launches(const ac_psy_plan* psy, int C, int S, int O);
 /* Library launches of protecting rows of C channels with a redundant budget of red_bits: 1 = ac_encode_fused_ex with
  * AC_IN_PACKED | AC_EMIT_PACKED | AC_EMIT_REDUNDANT serves it (where ac_transrate_launches returns 1 and red_bits is at most
  * AC_PACK_ROWS_MAX_BITS), else the launches of the composition's two transrating calls, each 1 or 3 (also everywhere while

@@ -16,7 +16,7 @@ the one launch on int16 (k_fwd_fast_qp16 / qps16), the conversion to(float32) / 
 caller did before), and the float32 one launch on a resident float32 tensor; compared byte for byte, then alternating
 (profiles/pack/pack_bench_pcm16.txt).
 python tools/pack_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7] [--round-steps 30]
-                           [--row-bits 1365] [--only-rows] [--stream] [--pcm16] [--transrate [--targets 1365 682]] [--conceal] [--conceal-stream] [--protect] [--mix]
+                           [--row-bits 1365] [--only-rows] [--stream] [--pcm16] [--transrate [--targets 1365 682]] [--conceal] [--conceal-stream] [--protect] [--mix] [--route]
 --transrate: rows at 2730 bits transrated to each of --targets (transrate_rows(); profiles/pack/pack_bench_transrate.txt).
 --conceal: decode_packed with lost rows concealed -- none lost, and 1 % lost at random -- against decode_packed without `lost`
 (conceal_rows(); profiles/pack/pack_bench_conceal.txt).
@@ -29,7 +29,10 @@ chunk on the same `lost` and against its composition; then protect_chunk against
 and against its composition (protect_stream_rows(); profiles/pack/pack_bench_protect_stream.txt).
 --mix [--sources 2 4]: mix_packed_rows of S sources at 2730 bits to 1365 in its one launch, against its composition, the decode
 route (S decode_packed, the adds, encode_packed_rows) and transrate_packed_rows of one source (mix_rows();
-profiles/pack/pack_bench_mix.txt)."""
+profiles/pack/pack_bench_mix.txt).
+--route [--sources 2 3 4 8]: route_packed_rows as mix-minus of S = O parties at 2730 bits to 1365 in its one launch, against O calls
+of mix_packed_rows and the decode route (S decode_packed, the adds, O encode_packed_rows) (route_rows();
+profiles/pack/pack_bench_route.txt)."""
 import argparse
 import ctypes
 import os
@@ -412,6 +415,67 @@ def mix_rows(a):
               % (med[0] / med[1], med[0] / med[2], med[0] / med[3], (med[0] - med[3]) / max(S - 1, 1) / med[3], read / 1e6, read / med[0] / 1e6))
 
 
+def route_rows(a):
+    """Routing: mix-minus of S = O parties (--sources, default 2 3 4 8), independent noise per source,
+    encode_packed_rows at 2730 bits routed to 1365.  (a) route_packed_rows in its one launch (k_route_p); (b) O calls of
+    mix_packed_rows, each one launch of k_mix_p; (c) what a bridge did before mixing: S decode_packed, the adds, O
+    encode_packed_rows.  (a) and (b) are compared byte for byte first, then all alternate, --rounds rounds of --round-steps."""
+    B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    base = audiocodec_amd.AudioCodec(48000, N)
+    src, dst = base.with_row_budget(2730), base.with_row_budget(1365)
+    gen = torch.Generator("cuda").manual_seed(0)
+    counts = a.sources if a.sources != [2, 4] else [2, 3, 4, 8]
+    all_sources = []
+    for _ in range(max(counts)):
+        x = torch.rand((B, K * N, C), device="cuda", generator=gen) * 2 - 1
+        all_sources.append(src.encode_packed_rows(x)[:2])
+        del x
+    rows = all_sources[0][1].numel()
+    print("route: B=%d K=%d N=%d C=%d  rows=%d per source at 2730 bits (%.1f MB each) -> 1365 bits (%.1f MB per output)  %s"
+          % (B, K, N, C, rows, all_sources[0][0].numel() / 1e6, rows * dst.row_bytes / 1e6, torch.cuda.get_device_name()))
+
+    def mixes(sources, routes, offset=False):
+        return [dst.mix_packed_rows([sources[i] for i, g in enumerate(r) if g is not None], [g for g in r if g is not None], None, offset)
+                for r in routes]
+
+    def decode_route(sources):
+        pcm = [dst.decode_packed(d, i) for d, i in sources]
+        total = pcm[0]
+        for p in pcm[1:]:
+            total = total + p
+        return [dst.encode_packed_rows((total - p)[:, N:-N].contiguous()) for p in pcm]
+
+    for S in counts:
+        sources, routes = all_sources[:S], dst.mix_minus_routes(S)
+        launches = dst.route_packed_rows_launches(C, sources_n=S, outputs_n=S)
+        one, two = dst.route_packed_rows(sources, routes, None, True), mixes(sources, routes, True)
+        for o in range(S):
+            assert torch.equal(one[0][o], two[o][0]) and torch.equal(one[2][o], two[o][2]) and torch.equal(one[3][o], two[o][3]), "the two forms differ"
+        print("S = O = %d: launches %d (%d mix_packed_rows: %d); the one launch and the mixes agree byte for byte; %d rows do not fit; "
+              "mean offset %.2f" % (S, launches, S, S * dst.mix_packed_rows_launches(C, sources_n=max(S - 1, 1)), int((~one[2]).sum()),
+                                    float(one[3].float().mean())))
+        del one, two
+        forms = [("(a) route_packed_rows, %d launch" % launches, lambda: dst.route_packed_rows(sources, routes)),
+                 ("(b) %d mix_packed_rows of %d sources" % (S, S - 1), lambda: mixes(sources, routes)),
+                 ("(c) %d decode_packed + adds + %d encode_packed_rows" % (S, S), lambda: decode_route(sources))]
+        runs = dict((n, []) for n, _ in forms)
+        for _ in range(a.rounds):
+            for n, fn in forms:
+                runs[n].append(timed(fn, a.round_steps, 1))
+        med, spread = [], []
+        for n, _ in forms:
+            v = sorted(runs[n])
+            med.append(v[len(v) // 2])
+            spread.append(v[-1] - v[0])
+            print("  %-52s median %.3f ms  min %.3f  max %.3f  (%d alternating rounds of %d)" % (n, med[-1], v[0], v[-1], len(v), a.round_steps))
+        moved_a = S * all_sources[0][0].numel() + S * rows * dst.row_bytes
+        moved_b = S * (S - 1) * all_sources[0][0].numel() + S * rows * dst.row_bytes
+        print("  (a) / (b) = %.3f   (a) / (c) = %.3f   (b) - (a) = %.3f ms against a spread of %.3f   per output: (a) %.3f ms, (b) %.3f ms   "
+              "(a) moves %.1f MB: %.0f GB/s, (b) %.1f MB"
+              % (med[0] / med[1], med[0] / med[2], med[1] - med[0], max(spread[0], spread[1]), med[0] / S, med[1] / S, moved_a / 1e6,
+                 moved_a / med[0] / 1e6, moved_b / 1e6))
+
+
 def conceal_rows(a):
     """Concealment of lost rows on the rows of encode_packed_rows at --row-bits: (a) decode_packed
     without `lost`, the yardstick; (b) with `lost` all false; (c) with 1 % of the rows lost at random, max_age 8 -- both the
@@ -644,7 +708,8 @@ def main():
     ap.add_argument("--protect-stream", action="store_true", help="only decode_packed_chunk with redundant_at, against the concealing chunk and its composition")
     ap.add_argument("--conceal-stream", action="store_true", help="only decode_packed_chunk with lost rows concealed, against without")
     ap.add_argument("--mix", action="store_true", help="only mix_packed_rows: --sources sources at 2730 bits mixed to 1365")
-    ap.add_argument("--sources", type=int, nargs="+", default=[2, 4], help="the source counts of --mix")
+    ap.add_argument("--sources", type=int, nargs="+", default=[2, 4], help="the source counts of --mix (--route: 2 3 4 8 by default)")
+    ap.add_argument("--route", action="store_true", help="only route_packed_rows: mix-minus of --sources parties at 2730 bits to 1365")
     ap.add_argument("--protect", action="store_true", help="only protect_packed_rows and the recovering decode (2730 -> 1365 with --red-bits)")
     ap.add_argument("--red-bits", type=int, default=341, help="the redundant budget of --protect (16 kbit/s)")
     ap.add_argument("--conceal", action="store_true", help="only decode_packed with lost rows concealed, against without")
@@ -668,6 +733,8 @@ def main():
         return protect_stream_rows(a)
     if a.mix:
         return mix_rows(a)
+    if a.route:
+        return route_rows(a)
     if a.protect:
         return protect_rows(a)
     if a.conceal:
