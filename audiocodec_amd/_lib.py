@@ -28,6 +28,9 @@ AC_IN_ROUTE = 2048   # beside AC_IN_PACKED | AC_EMIT_PACKED: x is one ac_route_r
 AC_ROUTE_MAX_SOURCES = 4   # the most sources and ...
 AC_ROUTE_MAX_OUTPUTS = 8   # ... outputs the one launch of AC_IN_ROUTE serves (the header's macros)
 AC_ROUTE_MUTE = -32768   # in ac_route_rows' gain: the output does not hear the source (the header's macro)
+AC_EMIT_LEVEL = 4096   # beside AC_IN_PACKED alone: out0 is float energy, out1 NULL or uint8 bad (the level of packed rows)
+AC_SELECT_ACTIVE = 8192   # alone: x is one ac_select_rows, out0 uint8 active (the n loudest sources)
+AC_SELECT_MAX_SOURCES = 64   # the most sources AC_SELECT_ACTIVE ranks (the header's macro)
 AC_CONCEAL_REDUNDANT = 256   # in ac_conceal's max_age: the struct is an ac_conceal_redundant (lost rows recovered)
 AC_CONCEAL = 128   # beside AC_PACKED in ac_stream_inverse_typed's dtype: X_chunk is one ac_stream_packed_lost_in
 AC_PACK_ROWS_MAX_BITS = 16384 # the largest row budget AC_EMIT_PACKED serves in one launch (the header's macro)
@@ -134,6 +137,7 @@ PROTOTYPES = {
     "ac_transrate_launches": (c_int, [c_void_p, c_int]),
     "ac_mix_launches": (c_int, [c_void_p, c_int, c_int]),
     "ac_route_launches": (c_int, [c_void_p, c_int, c_int, c_int]),
+    "ac_level_launches": (c_int, [c_void_p, c_int]),
     "ac_protect_launches": (c_int, [c_void_p, c_int, c_int]),
     "ac_protect_chunk_launches": (c_int, [c_void_p, c_int, c_int]),
     "ac_pack_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
@@ -163,6 +167,12 @@ class RouteRows(ctypes.Structure):
     """``ac_route_rows``: what ``ac_encode_fused_ex`` takes for ``x`` under ``AC_IN_ROUTE``."""
     _fields_ = [("sources_n", ctypes.c_int32), ("outputs_n", ctypes.c_int32), ("src", POINTER(PackedRows)),
                 ("gain", POINTER(ctypes.c_int32)), ("active", c_void_p)]
+
+
+class SelectRows(ctypes.Structure):
+    """``ac_select_rows``: what ``ac_encode_fused_ex`` takes for ``x`` under ``AC_SELECT_ACTIVE``."""
+    _fields_ = [("sources_n", ctypes.c_int32), ("energy", c_void_p), ("valid", c_void_p), ("n", ctypes.c_int32),
+                ("release", c_float), ("gate", c_float), ("state", c_void_p)]
 
 
 class Conceal(ctypes.Structure):

@@ -658,6 +658,148 @@ class AudioCodec:
                 offset[o].copy_(one[3])
         return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
 
+    # ---- the level of packed rows and the loudest sources (extension) ------------------------
+    def packed_rows_level_launches(self, channels_n=2, device=None):
+        """Library launches :meth:`packed_rows_level` takes for rows of ``channels_n`` channels (``ac_level_launches``): 1 =
+        one kernel reads each row and sums its energy (filters_n = 1024, bark_bands_n = 64; any channel count; with or
+        without a row budget), 0 = the library has no launch of its own and the method runs the composition on
+        :meth:`PsychoacousticModel.unpack` and :meth:`PsychoacousticModel.level` (everywhere while ``AC_LEVEL_NOFUSE=1`` is
+        set: read per call)."""
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return int(self._lib.ac_level_launches(self.psy._plan(dev), int(channels_n)))
+
+    def packed_rows_level(self, data, index, return_bad=False):
+        """The energy of packed rows, from the rows themselves, without decoding: data uint8 [nbytes], index int64 [B, F, C]
+        -> energy float32 [B, F, C], and bad uint8 [B, F, C] with ``return_bad=True``.
+
+        ``energy`` is the sum of the squared dequantised spectrum over the row's bins (DESIGN.md section 8j has the exact
+        arithmetic; within 2^-20 relative of the float64 sum), finite and never negative; by Parseval it follows the PCM
+        energy of the frame's window.  A band without a finite scale factor adds nothing and sets ``bad`` for its row: marked
+        rows, damaged widths, NaN-carrying input.  ``index`` holds any row starts, read as
+        :meth:`PsychoacousticModel.unpack` reads them: :meth:`encode_packed` output, fixed-stride rows, protected slots,
+        slices, a stream's chunks.  One launch where :meth:`packed_rows_level_launches` is 1, else the composition: the same
+        bits.  It never synchronises with the device, only enqueues on the current stream, and can be captured in a graph.
+        Works with or without a row budget.  float32 only."""
+        _host.require_float32(self.compute_dtype, "packed_rows_level")
+        data = self.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
+        index = self.psy._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
+        B, F, C = index.shape
+        dev = data.device
+        if B * F * C == 0:
+            energy = torch.empty((B, F, C), dtype=torch.float32, device=dev)
+            return (energy, torch.empty((B, F, C), dtype=torch.uint8, device=dev)) if return_bad else energy
+        psy = self.psy._plan(dev)
+        if self._lib.ac_level_launches(psy, C) == 1:
+            energy = torch.empty((B, F, C), dtype=torch.float32, device=dev)
+            bad = torch.empty((B, F, C), dtype=torch.uint8, device=dev) if return_bad else None
+            src = _lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr())
+            with _host.on_device(dev):
+                _lib.check(self._lib.ac_encode_fused_ex(self.mdct._plan(dev), psy, ctypes.addressof(src), None, None, None, 0.0,
+                                                        _lib.AC_IN_PACKED | _lib.AC_EMIT_LEVEL, _host.ptr(energy),
+                                                        _host.ptr(bad) if return_bad else None, 0, B, F - 1, C,
+                                                        _host.stream_ptr(dev)))
+            return (energy, bad) if return_bad else energy
+        # the composition (the kernel's reference): the rows unpacked, then the band sums and the fold tree as tensor operations
+        energy, bad = self.psy.level(*self.psy.unpack(data, index))
+        return (energy, bad) if return_bad else energy
+
+    def select_loudest(self, energy, n, valid=None, release=0.5, gate=0.0, state=None):
+        """The ``n`` loudest of S sources per clip and frame: the levels of :meth:`packed_rows_level` -> ``active`` uint8
+        [S, B, F, C], ready for ``mix_packed_rows(active=)`` and ``route_packed_rows(active=)``.
+
+        ``energy``: a list of S float32 tensors [B, F, C] or one stacked tensor [S, B, F, C]; ``valid``: uint8 / bool
+        [S, B, F, C], 0 = the row does not count and is never active (a lost or bad row; default all 1).  A source's level
+        at a frame is the sum of its valid channels' energies (NaN, negative values and -0 count as 0), held as a peak that
+        falls by ``release`` in [0, 1] per frame: ``P[f] = max(level[f], P[f-1] * release)``.  A source is selected where
+        its peak is above ``gate`` >= 0 and fewer than ``n`` sources are louder (of equal peaks the lower index is the
+        louder); ``active`` is the selection on the valid rows.  ``state``: float32 [S, B], the peaks carried from one chunk
+        of frames to the next, updated in place (default: zeros, nothing kept) -- any split of the frames gives the bits of
+        the one-shot call.  One launch for S <= ``_lib.AC_SELECT_MAX_SOURCES``; more sources take a loop of tensor
+        operations over the frames, a slow reference route with the same values.  It never synchronises with the device,
+        only enqueues on the current stream, and can be captured in a graph."""
+        # (the host arguments first: their errors need no device)
+        parts = None
+        if isinstance(energy, torch.Tensor):
+            if energy.dim() != 4:
+                raise ValueError("energy must have 4 dimensions [S, B, F, C], got shape %s" % (tuple(energy.shape),))
+            S = energy.shape[0]
+        else:
+            parts = list(energy)
+            S = len(parts)
+        if S < 1:
+            raise ValueError("energy: select_loudest needs at least one source")
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+            raise TypeError("n must be an int, got %s" % type(n).__name__)
+        if not 0 <= int(n) <= S:
+            raise ValueError("n (%d) outside [0, %d sources]" % (n, S))
+        for name, v in (("release", release), ("gate", gate)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise TypeError("%s must be a number, got %s" % (name, type(v).__name__))
+        release, gate = float(np.float32(release)), float(np.float32(gate))
+        if not 0.0 <= release <= 1.0:
+            raise ValueError("release (%r) outside [0, 1]" % release)
+        if not gate >= 0.0:
+            raise ValueError("gate (%r) is negative or NaN" % gate)
+        if parts is None:
+            energy = self.psy._check_quant_tensor(energy, "energy", torch.float32, ndim=4)
+        else:
+            parts = [self.psy._check_quant_tensor(e, "energy of source %d" % i, torch.float32, ndim=3) for i, e in enumerate(parts)]
+            for i, e in enumerate(parts):
+                if e.shape != parts[0].shape or e.device != parts[0].device:
+                    raise ValueError("energy of source %d has shape %s on %s, that of source 0 shape %s on %s"
+                                     % (i, tuple(e.shape), e.device, tuple(parts[0].shape), parts[0].device))
+            energy = torch.stack(parts)
+        S, B, F, C = energy.shape
+        dev = energy.device
+        if valid is not None:
+            if not isinstance(valid, torch.Tensor):
+                raise TypeError("valid must be a torch.Tensor or None, got %s" % type(valid).__name__)
+            if valid.dtype not in (torch.uint8, torch.bool):
+                raise ValueError("valid has dtype %s, expected torch.uint8 or torch.bool" % valid.dtype)
+            if tuple(valid.shape) != (S, B, F, C):
+                raise ValueError("valid must have shape %s, got %s" % ((S, B, F, C), tuple(valid.shape)))
+            if valid.device != dev:
+                raise ValueError("valid lives on %s but energy on %s" % (valid.device, dev))
+            valid = valid.contiguous()
+            valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid
+        if state is not None:
+            if not isinstance(state, torch.Tensor):
+                raise TypeError("state must be a torch.Tensor or None, got %s" % type(state).__name__)
+            if state.dtype != torch.float32 or tuple(state.shape) != (S, B) or state.device != dev or not state.is_contiguous():
+                raise ValueError("state must be a contiguous float32 tensor of shape %s on %s, got %s %s on %s"
+                                 % ((S, B), dev, state.dtype, tuple(state.shape), state.device))
+        active = torch.empty((S, B, F, C), dtype=torch.uint8, device=dev)
+        if B * F * C == 0:
+            return active
+        if S <= _lib.AC_SELECT_MAX_SOURCES:
+            sel = _lib.SelectRows(S, energy.data_ptr(), valid.data_ptr() if valid is not None else None, int(n), release, gate,
+                                  state.data_ptr() if state is not None else None)
+            with _host.on_device(dev):
+                _lib.check(self._lib.ac_encode_fused_ex(self.mdct._plan(dev), self.psy._plan(dev), ctypes.addressof(sel), None, None,
+                                                        None, 0.0, _lib.AC_SELECT_ACTIVE, _host.ptr(active), None, 0, B, F - 1, C,
+                                                        _host.stream_ptr(dev)))
+            return active
+        # more sources than a wave has lanes: the rules frame by frame as tensor operations (slow; the same values)
+        ok = energy > 0
+        if valid is not None:
+            ok &= valid != 0
+        level = torch.where(ok, energy, 0.0)
+        total = level[..., 0]
+        for c in range(1, C):
+            total = total + level[..., c]
+        P = state.clone() if state is not None else torch.zeros((S, B), dtype=torch.float32, device=dev)
+        src = torch.arange(S, device=dev)
+        first = (src.view(1, S) < src.view(S, 1)).unsqueeze(2)      # [s, t, 1]: t comes before s
+        for f in range(F):
+            d = P * release
+            P = torch.where(d > total[:, :, f], d, total[:, :, f])
+            above = ((P.unsqueeze(0) > P.unsqueeze(1)) | ((P.unsqueeze(0) == P.unsqueeze(1)) & first)).sum(dim=1)
+            chosen = ((P > gate) & (above < int(n))).unsqueeze(2)
+            active[:, :, f, :] = chosen if valid is None else chosen & (valid[:, :, f, :] != 0)
+        if state is not None:
+            state.copy_(P)
+        return active
+
     # ---- protected rows: a redundant copy of the frame before in every slot (extension; DESIGN.md section 8g) ---
     def _check_red_bits(self, red_bits, what):
         if self.row_bits is None:

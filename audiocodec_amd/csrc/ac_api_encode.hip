@@ -115,6 +115,11 @@ static bool route_fuses(const ac_psy_plan* psy, int S, int O) {
   if (env_is_1("AC_ROUTE_NOFUSE")) return false;
   return mix_fuses(psy, S) && route_serves(psy, S, O);
 }
+// whether the level of packed rows is one launch (k_level_p); AC_LEVEL_NOFUSE=1: as above
+static bool level_fuses(const ac_psy_plan* psy) {
+  if (env_is_1("AC_LEVEL_NOFUSE")) return false;
+  return !g_force_generic && level_serves(psy);
+}
 // whether packed rows are protected in one launch (k_protect_p); AC_PROTECT_NOFUSE=1: as above
 static bool protect_fuses(const ac_psy_plan* psy, int red_bits) {
   if (env_is_1("AC_PROTECT_NOFUSE")) return false;
@@ -447,6 +452,65 @@ static int route_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, c
                       offset, (long long)B * (K + 1) * C, (hipStream_t)stream);
 }
 
+int ac_level_launches(const ac_psy_plan* psy, int C) {
+  if (!psy || C < 1) return 0;
+  return level_fuses(psy) ? 1 : 0;   // (elsewhere the library has no launch of its own: ac_unpack and the caller's sums)
+}
+
+// ac_encode_fused_ex with AC_IN_PACKED | AC_EMIT_LEVEL: the energy of rows [B,K+1,C] of `in`, and whether a row holds a bad band
+// 
+static int level_packed_rows(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const ac_packed_rows* in, const float* X,
+                             const float* t, const float* thr, float* energy, uint8_t* bad, int B, int K, int C, void* stream) {
+  int st = check_plan_pair(mdct, psy);
+  if (!st) st = check_dims(B, K, C);
+  if (!st) st = check_quant(psy, B, K + 1, C);
+  if (st) return st;
+  AC_REQUIRE(X == nullptr && t == nullptr && thr == nullptr, "AC_EMIT_LEVEL writes no X, t or thr: they must be NULL");
+  AC_REQUIRE(in != nullptr, "AC_EMIT_LEVEL without its ac_packed_rows (x)");
+  const ac_packed_rows rows = *in;
+  AC_REQUIRE(rows.nbytes >= 0, "negative nbytes (%lld)", (long long)rows.nbytes);
+  AC_REQUIRE(energy != nullptr || B == 0 || C == 0, "AC_EMIT_LEVEL without its energy tensor (out0)");
+  if (B == 0 || C == 0) return AC_OK;
+  if (!level_fuses(psy)) {
+    set_error("AC_EMIT_LEVEL: no kernel takes the level of packed rows in one launch for filters_n = %d, bark_bands_n = %d here "
+              "(ac_level_launches() != 1): use the composition -- ac_unpack, the squares of the codes summed per band as "
+              "integers, fp32(fp32(Q) fp32(step(sf) step(sf))) per band, the fold tree of float32 adds", psy->N, psy->M);
+    return AC_EUNSUPPORTED;
+  }
+  st = check_packed_rows(rows, true, true);
+  if (st) return st;
+  AC_REQUIRE_ALIGNED(energy);
+  DeviceGuard guard(psy->device);
+  return launch_level(psy, rows.data, rows.nbytes, rows.index, energy, bad, (long long)B * (K + 1) * C, (hipStream_t)stream);
+}
+
+// ac_encode_fused_ex with AC_SELECT_ACTIVE: the levels of S sources [S,B,K+1,C] to the active mask of the n loudest
+static int select_active(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const ac_select_rows* in, const float* X, const float* t,
+                         const float* thr, uint8_t* active, const void* out1, int B, int K, int C, void* stream) {
+  int st = check_plan_pair(mdct, psy);
+  if (!st) st = check_dims(B, K, C);
+  if (st) return st;
+  AC_REQUIRE(X == nullptr && t == nullptr && thr == nullptr && out1 == nullptr,
+             "AC_SELECT_ACTIVE writes no X, t or thr and takes no out1: they must be NULL");
+  AC_REQUIRE(in != nullptr, "AC_SELECT_ACTIVE without its ac_select_rows (x)");
+  const ac_select_rows sel = *in;
+  AC_REQUIRE(sel.sources_n >= 1, "sources_n (%d) below 1", (int)sel.sources_n);
+  AC_REQUIRE(sel.n >= 0 && sel.n <= sel.sources_n, "n (%d) outside [0, sources_n = %d]", (int)sel.n, (int)sel.sources_n);
+  AC_REQUIRE(sel.release >= 0.f && sel.release <= 1.f, "release (%g) outside [0, 1]", (double)sel.release);   // (NaN fails both)
+  AC_REQUIRE(sel.gate >= 0.f, "gate (%g) is negative or NaN", (double)sel.gate);
+  AC_REQUIRE((sel.energy != nullptr && active != nullptr) || B == 0 || C == 0, "AC_SELECT_ACTIVE: energy or the output (out0) is NULL");
+  if (sel.sources_n > AC_SELECT_MAX_SOURCES) {
+    set_error("AC_SELECT_ACTIVE: %d sources, the kernel ranks at most AC_SELECT_MAX_SOURCES = %d (a lane of a wave each): rank them "
+              "frame by frame by the rules of the header", (int)sel.sources_n, AC_SELECT_MAX_SOURCES);
+    return AC_EUNSUPPORTED;
+  }
+  if (B == 0 || C == 0) return AC_OK;
+  AC_REQUIRE_ALIGNED(sel.energy, sel.state);
+  DeviceGuard guard(psy->device);
+  return launch_select(sel.energy, sel.valid, active, sel.state, sel.sources_n, B, K + 1, C, sel.n, sel.release, sel.gate,
+                       (hipStream_t)stream);
+}
+
 int ac_protect_launches(const ac_psy_plan* psy, int C, int red_bits) {
   if (!psy || C < 1 || !psy->row_bits || red_bits < 5 * psy->M) return 0;
   if (protect_fuses(psy, red_bits)) return 1;
@@ -513,7 +577,19 @@ int ac_encode_fused_ex(const ac_mdct_plan* mdct, const ac_psy_plan* psy, const f
                        float drown, int flags, void* noisy_v, void* db_norm_v, uint64_t seed, int B, int K, int C,
                        void* stream) {
   AC_REQUIRE((flags & ~(AC_EMIT_NOISY | AC_EMIT_DB_NORM | AC_EMIT_CODES | AC_EMIT_PACKED | AC_IN_PCM16 | AC_IN_PACKED |
-                        AC_EMIT_REDUNDANT | AC_EMIT_CARRY | AC_IN_MIX | AC_IN_ROUTE)) == 0, "unknown flags %#x", flags);
+                        AC_EMIT_REDUNDANT | AC_EMIT_CARRY | AC_IN_MIX | AC_IN_ROUTE | AC_EMIT_LEVEL | AC_SELECT_ACTIVE)) == 0,
+             "unknown flags %#x", flags);
+  if (flags & AC_SELECT_ACTIVE) {
+    AC_REQUIRE(flags == AC_SELECT_ACTIVE, "AC_SELECT_ACTIVE goes alone (got %#x): levels are ranked into an active mask", flags);
+    return select_active(mdct, psy, reinterpret_cast<const ac_select_rows*>(x), X, t, thr, static_cast<uint8_t*>(noisy_v), db_norm_v,
+                         B, K, C, stream);
+  }
+  if (flags & AC_EMIT_LEVEL) {
+    AC_REQUIRE(flags == (AC_IN_PACKED | AC_EMIT_LEVEL),
+               "AC_EMIT_LEVEL goes with AC_IN_PACKED alone (got %#x): the level of packed rows is taken", flags);
+    return level_packed_rows(mdct, psy, reinterpret_cast<const ac_packed_rows*>(x), X, t, thr, static_cast<float*>(noisy_v),
+                             static_cast<uint8_t*>(db_norm_v), B, K, C, stream);
+  }
   if (flags & AC_IN_ROUTE) {
     AC_REQUIRE(flags == (AC_IN_PACKED | AC_EMIT_PACKED | AC_IN_ROUTE),
                "AC_IN_ROUTE goes with AC_IN_PACKED | AC_EMIT_PACKED alone (got %#x): the packed rows of several sources are routed to "

@@ -498,6 +498,16 @@ int launch_protect_stream(const ac_psy_plan* psy, const uint8_t* data, int64_t n
                           int64_t row_bytes, int red_bits, uint8_t* fits, uint8_t* red_fits, int16_t* offset, int16_t* red_offset,
                           const uint8_t* row_in, const uint8_t* fits_in, const int16_t* offset_in, uint8_t* row_out,
                           uint8_t* fits_out, int16_t* offset_out, int B, int F, int C, hipStream_t s);
+// The level of packed rows (k_level_p, ac_level.hip): energy [rows] = the sum of X^ squared over the row's
+// bins in the section's arithmetic, bad [rows] (or NULL) = 1 where a band of the row has sf = -128.  Where N = 1024 and M = 64,
+// with or without a row budget
+bool level_serves(const ac_psy_plan* psy);
+int launch_level(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes, const int64_t* index, float* energy, uint8_t* bad,
+                 long long rows, hipStream_t s);
+// ... and the n loudest of S <= AC_SELECT_MAX_SOURCES sources per clip and frame (k_select_loudest, ac_select.hip): energy, valid
+// (or NULL: all ones) and active [S,B,F,C], state [S,B] (or NULL) read and written in place
+int launch_select(const float* energy, const uint8_t* valid, uint8_t* active, float* state, int S, int B, int F, int C, int n,
+                  float release, float gate, hipStream_t s);
 // rate control per clip (ac_clip_rate.hip): one budget for the F*C rows of a clip (clip_budget [B] int64,
 // or the scalar budget where it is NULL); row_bits, clip_offset and clip_bits may be NULL; scratch of
 // clip_budget_scratch_bytes(p, B, F*C) bytes

@@ -595,6 +595,41 @@ class PsychoacousticModel:
         thr = (step * float(np.float32(np.sqrt(np.float32(3.0))))).index_select(2, band)
         return self.quantize_to_budget(total, thr, row_bits, 0)
 
+    # ---- the level of quantised rows (extension) -----------------------------------
+    def level(self, codes, sf):
+        """The energy of quantised rows from their codes and scale factors: codes int16 [B, F, N, C],
+        sf int8 [B, F, M, C] -> (energy float32 [B, F, C], bad uint8 [B, F, C]).
+
+        Per band j: Q_j, the sum of the squared codes as an exact integer, times w(sf_j) = fp32(step step) of the band's
+        step, one float32 product; a band with sf = -128 is *bad* and adds +0.  The 64 (or next power of two) band energies
+        are added as the fold tree ``v[i] += v[i + d]``, d = P/2 ... 1, so the value equals, bit for bit, what a wave's xor
+        butterfly gives.  ``energy`` is the sum of :meth:`dequantize` squared over the row's good bands within 2^-20
+        relative, finite and never negative; ``bad`` is 1 where any band of the row is bad.  Any filter_bands_n and band
+        layout; torch operations only, nothing waits for the device.  float32 plans only."""
+        _host.require_float32(self.compute_dtype, "the quantiser")
+        codes, sf = self._check_codes(codes, sf)
+        B, F, N, C = codes.shape
+        M, dev = self.bark_bands_n, codes.device
+        band = self._band_of_bins(dev)
+        is_bad = sf == -128
+        q = codes.to(torch.int64)
+        Q = torch.zeros((B, F, M, C), dtype=torch.int64, device=dev).index_add_(2, band, q * q)   # (integer adds: exact)
+        s = torch.arange(-127, 128, dtype=torch.int32, device=dev)
+        r = s & 3
+        mant = torch.where(r == 0, 0, torch.where(r == 1, 0x1837f0, torch.where(r == 2, 0x3504f3, 0x5744fd))).to(torch.int32)
+        step = (((127 + (s >> 2)) << 23) | mant).view(torch.float32)      # step(s) = ldexp(fp32(2^((s & 3) / 4)), s >> 2)
+        w = (step * step)[(sf.to(torch.int64) + 127).clamp_(min=0)]       # the 255-entry table, looked up per band
+        e = torch.where(is_bad, 0.0, Q.to(torch.float32) * w)
+        P = 1
+        while P < M:
+            P *= 2
+        v = torch.zeros((B, F, C, P), dtype=torch.float32, device=dev)
+        v[..., :M] = e.permute(0, 1, 3, 2)
+        while P > 1:
+            P //= 2
+            v = v[..., :P] + v[..., P:2 * P]
+        return v[..., 0].contiguous(), is_bad.any(dim=2).to(torch.uint8)
+
     # ---- rate control per clip (extension; DESIGN.md section 8d) ---------------------------------------
     def quantize_to_clip_budget(self, mdct_amplitudes, masking_threshold, clip_bits, min_offset=0):
         """:meth:`quantize_to_budget` with one budget for the whole clip: X, thr [B, F, N, C] float32 -> (codes int16

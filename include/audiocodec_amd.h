@@ -58,7 +58,8 @@ extern "C" {
                           * ac_conceal_redundant; the recovering decode chunk by chunk: ac_stream_packed_recover_in,
                           * and protecting chunk by chunk: AC_EMIT_CARRY, ac_protect_carry, ac_protect_chunk_launches; rows
                           * of several sources mixed without decoding: AC_IN_MIX, ac_mix_rows, ac_mix_launches; and routed
-                          * to several mixes: AC_IN_ROUTE, ac_route_rows, ac_route_launches);
+                          * to several mixes: AC_IN_ROUTE, ac_route_rows, ac_route_launches; the level of packed rows and
+                          * the loudest sources: AC_EMIT_LEVEL, ac_level_launches, AC_SELECT_ACTIVE, ac_select_rows);
                           * additions only, so the number stays.
                           * 0.1.8: ac_mdct_plan_tier; 16-bit PCM at the Opus / MP3 frame lengths; the LDS-FFT tier on 16-byte kernels with compile-time instances (filters_n % 4 == 0
                           * with a 5-smooth half up to 8192, float32); masking model for general band layouts up to 4096 bins.
@@ -331,6 +332,40 @@ enum { AC_IN_MIX = 1024 };   /* a flag of the same argument (above) */
  *     without a row budget; a refused call writes nothing.  Served where ac_route_launches returns 1; AC_EUNSUPPORTED
  *     elsewhere (run AC_IN_MIX, or its composition, per output).  Inputs and output must not overlap. */
 enum { AC_IN_ROUTE = 2048 };   /* a flag of the same argument (above) */
+/*   AC_EMIT_LEVEL  the level of packed rows, valid only as AC_IN_PACKED | AC_EMIT_LEVEL: the energy of
+ *     every row from the row's own fields, in ONE launch that never decodes.  x addresses one ac_packed_rows with an index
+ *     [B,K+1,C] of any int64 row starts, read as ac_unpack reads them, damaged rows included; out0 is float* energy [B,K+1,C];
+ *     out1 is NULL or uint8_t* bad [B,K+1,C]; X, t and thr must be NULL; a plan without a row budget is accepted.  With
+ *     (q, s) the codes and scale factors ac_unpack returns for a row: band j is bad where s_j = -128; Q_j is the exact integer
+ *     sum of q_n^2 over band j (0 in a bad band); w(s) = fp32(step(s) step(s)); e_j = fp32(fp32(Q_j) w(s_j)), the conversion of
+ *     the 64-bit Q_j rounding to nearest even, +0 in a bad band; energy is the fold tree over v[0 .. 64) = e: for d = 32, 16,
+ *     ..., 1, v[i] = fp32(v[i] + v[i+d]) for i < d, then v[0].  bad is 1 where any band of the row is bad (marked rows, widths
+ *     17 .. 30, a stored sf of -128), else 0.  energy is finite and >= +0 always.  AC_EINVAL: any other combination with the
+ *     bit, a NULL struct or energy; a refused call writes nothing.  Served where ac_level_launches returns 1;
+ *     AC_EUNSUPPORTED elsewhere (run the composition: ac_unpack, then the sums above).
+ *   AC_SELECT_ACTIVE  the n loudest sources, valid only alone: levels of S sources -> the active mask
+ *     AC_IN_MIX and AC_IN_ROUTE take.  x addresses one ac_select_rows (a host struct, read during the call); out0 is uint8_t*
+ *     active [S,B,K+1,C]; out1, X, t and thr must be NULL; the plans are checked as in every other form and not used.  With
+ *     E'_c = energy[s,b,f,c] where valid (NULL: all ones) is non-zero and the energy > 0, else +0 (NaN, negatives and -0 count
+ *     as +0; +Inf stays): E[s,b,f] = ((E'_0 + E'_1) + ...) in float32; d = fp32(P[s,b,f-1] release), P[s,b,f] = d where d >
+ *     E[s,b,f], else E[s,b,f] (peak hold with exponential release; a NaN d, Inf times 0, gives E), P[s,b,-1] = state[s,b]
+ *     (NULL: 0).  Source s is selected at (b,f) where P[s,b,f] > gate and fewer than n sources t have P[t,b,f] > P[s,b,f] or
+ *     (P[t,b,f] == P[s,b,f] and t < s).  active[s,b,f,c] = selected and valid[s,b,f,c] != 0; afterwards state[s,b] =
+ *     P[s,b,K] (updated in place), so any split of the frames with state carried equals the one-shot call.  AC_EINVAL: any
+ *     other combination with the bit, a NULL struct, energy or output, sources_n < 1, n outside [0, sources_n], release
+ *     outside [0, 1] or NaN, gate negative or NaN; AC_EUNSUPPORTED: sources_n > AC_SELECT_MAX_SOURCES.  A refused call
+ *     writes nothing. */
+enum { AC_EMIT_LEVEL = 4096, AC_SELECT_ACTIVE = 8192 };   /* flags of the same argument (above) */
+#define AC_SELECT_MAX_SOURCES 64 /* the most sources AC_SELECT_ACTIVE ranks: a lane of a wave each */
+typedef struct ac_select_rows {
+  int32_t sources_n;     /* S >= 1 */
+  const float* energy;   /* [S,B,K+1,C] (device) */
+  const uint8_t* valid;  /* [S,B,K+1,C] (device) 0 = the row does not count and is never active, or NULL: all ones */
+  int32_t n;             /* at most n sources are selected per clip and frame, in [0, S] */
+  float release;         /* in [0, 1]: what a frame keeps of the peak before it */
+  float gate;            /* >= 0: a source is selected only above it */
+  float* state;          /* [S,B] (device) the peaks carried from chunk to chunk, updated in place, or NULL: zeros */
+} ac_select_rows;
 /* The largest row budget the one launch of AC_EMIT_PACKED serves: a wave stages both rows of its frame pair in the 4 KB of
  * its LDS buffer that the masking model has left, 2 KB = 16384 bits each. */
 #define AC_PACK_ROWS_MAX_BITS 16384
@@ -413,6 +448,12 @@ AC_API int ac_mix_launches(const ac_psy_plan* psy, int C, int S);
  * per call -- with O = 1 that count is 1 too, and the call is refused all the same while the variable is set).  0 for a NULL
  * plan, C < 1, S < 1, O < 1 or a plan without a row budget.  The bytes do not depend on it. */
 AC_API int ac_route_launches(const ac_psy_plan* psy, int C, int S, int O);
+/* Library launches of the level of rows of C channels: 1 = ac_encode_fused_ex with AC_IN_PACKED | AC_EMIT_LEVEL serves it
+ * (float32 plans with filters_n = 1024 and bark_bands_n = 64, with or without a row budget; any C, rows being independent),
+ * 0 = the library has no launch of its own for it: ac_unpack and the caller's sums are the composition (also everywhere
+ * while AC_LEVEL_NOFUSE=1 is set in the environment: read per call).  0 too for a NULL plan or C < 1.  The values do not
+ * depend on it. */
+AC_API int ac_level_launches(const ac_psy_plan* psy, int C);
 /* Library launches of protecting rows of C channels with a redundant budget of red_bits: 1 = ac_encode_fused_ex with
  * AC_IN_PACKED | AC_EMIT_PACKED | AC_EMIT_REDUNDANT serves it (where ac_transrate_launches returns 1 and red_bits is at most
  * AC_PACK_ROWS_MAX_BITS), else the launches of the composition's two transrating calls, each 1 or 3 (also everywhere while

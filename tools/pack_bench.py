@@ -16,7 +16,7 @@ the one launch on int16 (k_fwd_fast_qp16 / qps16), the conversion to(float32) / 
 caller did before), and the float32 one launch on a resident float32 tensor; compared byte for byte, then alternating
 (profiles/pack/pack_bench_pcm16.txt).
 python tools/pack_bench.py [--clips 256] [--blocks 468] [--filters 1024] [--steps 50] [--warmup 5] [--rounds 7] [--round-steps 30]
-                           [--row-bits 1365] [--only-rows] [--stream] [--pcm16] [--transrate [--targets 1365 682]] [--conceal] [--conceal-stream] [--protect] [--mix] [--route]
+                           [--row-bits 1365] [--only-rows] [--stream] [--pcm16] [--transrate [--targets 1365 682]] [--conceal] [--conceal-stream] [--protect] [--mix] [--route] [--level]
 --transrate: rows at 2730 bits transrated to each of --targets (transrate_rows(); profiles/pack/pack_bench_transrate.txt).
 --conceal: decode_packed with lost rows concealed -- none lost, and 1 % lost at random -- against decode_packed without `lost`
 (conceal_rows(); profiles/pack/pack_bench_conceal.txt).
@@ -32,7 +32,10 @@ route (S decode_packed, the adds, encode_packed_rows) and transrate_packed_rows 
 profiles/pack/pack_bench_mix.txt).
 --route [--sources 2 3 4 8]: route_packed_rows as mix-minus of S = O parties at 2730 bits to 1365 in its one launch, against O calls
 of mix_packed_rows and the decode route (S decode_packed, the adds, O encode_packed_rows) (route_rows();
-profiles/pack/pack_bench_route.txt)."""
+profiles/pack/pack_bench_route.txt).
+--level: packed_rows_level in its one launch against its composition, the decode route (decode_packed and a per-block energy pass)
+and transrate_packed_rows of the same rows; select_loudest at S = 4 and 8; a bridge of four with everyone routed against levels +
+select_loudest(n = 2) + route_packed_rows (level_rows(); profiles/pack/pack_bench_level.txt)."""
 import argparse
 import ctypes
 import os
@@ -476,6 +479,79 @@ def route_rows(a):
                  moved_a / med[0] / 1e6, moved_b / 1e6))
 
 
+def level_rows(a):
+    """Levels and the selector on sources of encode_packed_rows at 2730 bits.  (a) packed_rows_level in
+    its one launch (k_level_p); (b) its composition (AC_LEVEL_NOFUSE=1, read per call); (c) what a caller did before:
+    decode_packed and a per-block energy pass over the PCM; (d) transrate_packed_rows of the same rows to 1365 bits, the
+    parse-search-pack yardstick; (e) select_loudest at S = 4 and S = 8 on those levels; (f) a bridge of four, mix-minus to 1365
+    bits: everyone routed, against levels + select_loudest(n = 2) + route_packed_rows(active=).  (a) and (b) are compared bit
+    for bit first, then all alternate, --rounds rounds of --round-steps."""
+    B, K, N, C = a.clips, a.blocks, a.filters, a.channels
+    base = audiocodec_amd.AudioCodec(48000, N)
+    src, dst = base.with_row_budget(2730), base.with_row_budget(1365)
+    gen = torch.Generator("cuda").manual_seed(0)
+    sources = []
+    for _ in range(4):
+        x = torch.rand((B, K * N, C), device="cuda", generator=gen) * 2 - 1
+        sources.append(src.encode_packed_rows(x)[:2])
+        del x
+    data, index = sources[0]
+    rows = index.numel()
+    print("level: B=%d K=%d N=%d C=%d  rows=%d per source at 2730 bits (%.1f MB each)  %s"
+          % (B, K, N, C, rows, data.numel() / 1e6, torch.cuda.get_device_name()))
+
+    def composition():
+        os.environ["AC_LEVEL_NOFUSE"] = "1"   # (read per call)
+        try:
+            return base.packed_rows_level(data, index, True)
+        finally:
+            del os.environ["AC_LEVEL_NOFUSE"]
+
+    def decode_route():
+        pcm = base.decode_packed(data, index)
+        return pcm.view(B, -1, N, C).square().sum(dim=2)   # the energy of every block
+
+    one, two = base.packed_rows_level(data, index, True), composition()
+    assert all(torch.equal(g, r) for g, r in zip(one, two)), "the two forms differ"
+    print("launches %d; the one launch and the composition agree bit for bit; %d bad rows; mean energy %.4g"
+          % (base.packed_rows_level_launches(C), int(one[1].sum()), float(one[0].mean())))
+    del one, two
+    gen = torch.Generator("cuda").manual_seed(1)
+    levels = {S: torch.rand((S, B, K + 1, C), device="cuda", generator=gen) * (torch.rand((S, B, K + 1, 1), device="cuda", generator=gen) < 0.25)
+              for S in (4, 8)}
+    states = {S: torch.zeros((S, B), device="cuda") for S in (4, 8)}
+    routes = dst.mix_minus_routes(4)
+
+    def bridge():
+        lv = [base.packed_rows_level(d, i, True) for d, i in sources]
+        active = base.select_loudest([e for e, _ in lv], 2, torch.stack([bad == 0 for _, bad in lv]), 0.5, 0.0)
+        return dst.route_packed_rows(sources, routes, active)
+
+    forms = [("(a) packed_rows_level, %d launch" % base.packed_rows_level_launches(C), lambda: base.packed_rows_level(data, index, True)),
+             ("(b) packed_rows_level, composition", composition),
+             ("(c) decode_packed + energy of every PCM block", decode_route),
+             ("(d) transrate_packed_rows to 1365 bits", lambda: dst.transrate_packed_rows(data, index)),
+             ("(e) select_loudest, S = 4, n = 2", lambda: base.select_loudest(levels[4], 2, None, 0.5, 0.0, states[4])),
+             ("(e) select_loudest, S = 8, n = 2", lambda: base.select_loudest(levels[8], 2, None, 0.5, 0.0, states[8])),
+             ("(f) bridge of 4: everyone routed", lambda: dst.route_packed_rows(sources, routes)),
+             ("(f) bridge of 4: 4 levels + select (n = 2) + route", bridge)]
+    runs = dict((n, []) for n, _ in forms)
+    for _ in range(a.rounds):
+        for n, fn in forms:
+            runs[n].append(timed(fn, a.round_steps, 1))
+    med, spread = [], []
+    for n, _ in forms:
+        v = sorted(runs[n])
+        med.append(v[len(v) // 2])
+        spread.append(v[-1] - v[0])
+        print("  %-52s median %.3f ms  min %.3f  max %.3f  (%d alternating rounds of %d)" % (n, med[-1], v[0], v[-1], len(v), a.round_steps))
+    read = data.numel() + rows * 13
+    print("  (a) / (b) = %.3f   (b) - (a) = %.3f ms against a spread of %.3f   (a) / (c) = %.3f   (a) / (d) = %.3f   (a) moves %.1f MB: %.0f GB/s"
+          % (med[0] / med[1], med[1] - med[0], max(spread[0], spread[1]), med[0] / med[2], med[0] / med[3], read / 1e6, read / med[0] / 1e6))
+    print("  bridge: selected / everyone = %.3f   everyone - selected = %.3f ms against a spread of %.3f"
+          % (med[7] / med[6], med[6] - med[7], max(spread[6], spread[7])))
+
+
 def conceal_rows(a):
     """Concealment of lost rows on the rows of encode_packed_rows at --row-bits: (a) decode_packed
     without `lost`, the yardstick; (b) with `lost` all false; (c) with 1 % of the rows lost at random, max_age 8 -- both the
@@ -707,6 +783,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--protect-stream", action="store_true", help="only decode_packed_chunk with redundant_at, against the concealing chunk and its composition")
     ap.add_argument("--conceal-stream", action="store_true", help="only decode_packed_chunk with lost rows concealed, against without")
+    ap.add_argument("--level", action="store_true", help="only packed_rows_level and select_loudest on sources at 2730 bits")
     ap.add_argument("--mix", action="store_true", help="only mix_packed_rows: --sources sources at 2730 bits mixed to 1365")
     ap.add_argument("--sources", type=int, nargs="+", default=[2, 4], help="the source counts of --mix (--route: 2 3 4 8 by default)")
     ap.add_argument("--route", action="store_true", help="only route_packed_rows: mix-minus of --sources parties at 2730 bits to 1365")
@@ -731,6 +808,8 @@ def main():
     B, K, N, C = a.clips, a.blocks, a.filters, a.channels
     if a.protect_stream:
         return protect_stream_rows(a)
+    if a.level:
+        return level_rows(a)
     if a.mix:
         return mix_rows(a)
     if a.route:
