@@ -27,17 +27,10 @@ int launch_level(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes, co
     set_error("internal: no level kernel for filters_n = %d, %d bands", psy->N, psy->M);
     return AC_EUNSUPPORTED;
   }
-  const long long groups = (rows + T_WAVES - 1) / T_WAVES;
-  if (groups > 2147483647ll) {
-    set_error("problem too large for one launch (%lld rows)", rows);
-    return AC_EINVAL;
-  }
+  long long groups;
+  if (!row_groups(rows, T_WAVES, &groups)) return AC_EINVAL;
   LevelArgs a;
-  a.in.data = data;
-  a.in.nbytes = nbytes;
-  a.in.index = index;
-  a.in.band32 = reinterpret_cast<const uint32_t*>(psy->d_qband);
-  a.in.off = psy->d_qoff;
+  a.in = plan_rows(psy, data, nbytes, index);
   a.energy = energy;
   a.bad = bad;
   a.rows = rows;

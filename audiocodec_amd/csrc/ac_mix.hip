@@ -30,11 +30,8 @@ int launch_mix(const ac_psy_plan* psy, int sources_n, const ac_packed_rows* src,
               sources_n);
     return AC_EUNSUPPORTED;
   }
-  const long long groups = (rows + T_WAVES - 1) / T_WAVES;
-  if (groups > 2147483647ll) {
-    set_error("problem too large for one launch (%lld rows)", rows);
-    return AC_EINVAL;
-  }
+  long long groups;
+  if (!row_groups(rows, T_WAVES, &groups)) return AC_EINVAL;
   MixArgs a = {};
   for (int i = 0; i < sources_n; ++i) {
     a.data[i] = src[i].data;

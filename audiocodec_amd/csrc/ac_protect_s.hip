@@ -29,29 +29,10 @@ int launch_protect_stream(const ac_psy_plan* psy, const uint8_t* data, int64_t n
               psy->M, psy->row_bits, red_bits);
     return AC_EUNSUPPORTED;
   }
-  const long long groups = (rows + T_WAVES - 1) / T_WAVES;
-  if (groups > 2147483647ll) {
-    set_error("problem too large for one launch (%lld rows)", rows);
-    return AC_EINVAL;
-  }
-  ProtectArgs a;
-  a.in.data = data;
-  a.in.nbytes = nbytes;
-  a.in.index = index;
-  a.in.band32 = reinterpret_cast<const uint32_t*>(psy->d_qband);
-  a.in.off = psy->d_qoff;
-  a.data = out;
-  a.fits = fits;
-  a.red_fits = red_fits;
-  a.offset = offset;
-  a.red_offset = red_offset;
-  a.rows = rows;
-  a.F = F;
-  a.C = C;
-  a.row_bits = psy->row_bits;
-  a.red_bits = red_bits;
-  a.row_bytes = (int)row_bytes;
-  a.red_bytes = (red_bits + 31) / 32 * 4;
+  long long groups;
+  if (!row_groups(rows, T_WAVES, &groups)) return AC_EINVAL;
+  const ProtectArgs a = protect_args(psy, data, nbytes, index, out, row_bytes, red_bits, fits, red_fits, offset, red_offset, rows,
+                                     F, C);
   ProtectCarry pc;
   pc.row_in = row_in;
   pc.fits_in = fits_in;

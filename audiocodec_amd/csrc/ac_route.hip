@@ -32,11 +32,8 @@ int launch_route(const ac_psy_plan* psy, int sources_n, int outputs_n, const ac_
               psy->row_bits, sources_n, outputs_n);
     return AC_EUNSUPPORTED;
   }
-  const long long groups = (rows + R_WAVES - 1) / R_WAVES;
-  if (groups > 2147483647ll) {
-    set_error("problem too large for one launch (%lld rows)", rows);
-    return AC_EINVAL;
-  }
+  long long groups;
+  if (!row_groups(rows, R_WAVES, &groups)) return AC_EINVAL;
   RouteArgs a = {};
   for (int i = 0; i < sources_n; ++i) {
     a.data[i] = src[i].data;

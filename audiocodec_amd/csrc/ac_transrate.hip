@@ -30,17 +30,10 @@ int launch_transrate(const ac_psy_plan* psy, const uint8_t* data, int64_t nbytes
     set_error("internal: no transrating kernel for filters_n = %d, %d bands, row budget %d", psy->N, psy->M, psy->row_bits);
     return AC_EUNSUPPORTED;
   }
-  const long long groups = (rows + T_WAVES - 1) / T_WAVES;
-  if (groups > 2147483647ll) {
-    set_error("problem too large for one launch (%lld rows)", rows);
-    return AC_EINVAL;
-  }
+  long long groups;
+  if (!row_groups(rows, T_WAVES, &groups)) return AC_EINVAL;
   TransArgs a;
-  a.in.data = data;
-  a.in.nbytes = nbytes;
-  a.in.index = index;
-  a.in.band32 = reinterpret_cast<const uint32_t*>(psy->d_qband);
-  a.in.off = psy->d_qoff;
+  a.in = plan_rows(psy, data, nbytes, index);
   a.out.data = out;
   a.out.fits = fits;
   a.out.row_bytes = (int)row_bytes;
