@@ -61,6 +61,36 @@ def require_float32(compute_dtype, what):
         raise NotImplementedError("%s is implemented for compute_dtype float32 only (got %s)" % (what, compute_dtype))
 
 
+def default_device(device, indexed=False):
+    """``device`` as a ``torch.device``, the current ROCm device for None; ``indexed``: a bare ``"cuda"`` gets the current
+    index too (objects that keep state on the device name it once and for all)."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if indexed and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+def blocks_of(x, filters_n):
+    """K of PCM x [B, K * filters_n, C]."""
+    S = x.shape[1]
+    if S % filters_n != 0:
+        raise ValueError("samples_n (%d) is not a multiple of filters_n (%d)" % (S, filters_n))
+    return S // filters_n
+
+
+def refuse_gradient(x):
+    """The quantising calls take no input that requires a gradient."""
+    if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+        raise ValueError("x requires a gradient: quantisation is not differentiable -- use encode() and "
+                         "psy.add_noise(), its differentiable stand-in")
+
+
+def pcm_out(shape, pcm16, device):
+    """A decoder's PCM result and its (float32, int16) pointer pair for the library: x, px, px16."""
+    x = torch.empty(shape, dtype=torch.int16 if pcm16 else torch.float32, device=device)
+    return (x, None, ptr(x)) if pcm16 else (x, ptr(x), None)
+
+
 def check_device_tensor(t, name, dtype, ndim):
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))

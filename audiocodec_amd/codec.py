@@ -17,36 +17,10 @@ import os
 import numpy as np
 import torch
 
-from . import _host, _lib, placement
+from . import _host, _lib, _rows, placement
 from .mdctransformer import MDCTransformer
 from .psychoacoustic import PsychoacousticModel
-
-
-def _pack_rows_of_spectra(psy, X, thr, index, row_bytes):
-    """The tail of the composition of packed rows, shared by :meth:`AudioCodec.encode_packed_rows` and
-    :meth:`StreamingMDCT.encode_packed_rows_chunk`: ``psy.quantize_to_budget`` at the model's budget on X, thr [B, F, N, C] (on
-    plain allocations: nothing here may wait for the device), rows longer than their slot marked, then the packer at the fixed
-    row starts ``index`` into zero-filled data.  Returns (data uint8 [B*F*C*row_bytes], fits bool [B, F, C]); everything is
-    enqueued on the current stream."""
-    B, F, _, C = X.shape
-    dev = X.device
-    row_bits, min_offset = psy.row_budget
-    codes, sf, _, bits = psy.quantize_to_budget(X, thr, row_bits, min_offset)
-    return _pack_rows_of_codes(psy, codes, sf, bits, index, row_bytes)
-
-
-def _pack_rows_of_codes(psy, codes, sf, bits, index, row_bytes):
-    """The tail of :func:`_pack_rows_of_spectra`, which :meth:`AudioCodec.mix_packed_rows`' composition shares: codes
-    [B, F, N, C], sf (changed in place) and their packed lengths ``bits`` [B, F, C] -> (data, fits)."""
-    B, F, _, C = codes.shape
-    dev = codes.device
-    fits = bits <= 8 * row_bytes
-    sf.masked_fill_(~fits.unsqueeze(2), -128)   # width 31 follows whatever the codes are
-    data = torch.zeros((B * F * C * row_bytes,), dtype=torch.uint8, device=dev)
-    with _host.on_device(dev):
-        _lib.check(_lib.load().ac_pack(psy._plan(dev), _host.ptr(codes), _host.ptr(sf), _host.ptr(index), _host.ptr(data), B, F, C,
-                                       _host.stream_ptr(dev)))
-    return data, fits
+from .stream import ProtectStream, StreamingMDCT   # (their home is stream.py; they stay importable from here)
 
 
 class AudioCodec:
@@ -86,8 +60,14 @@ class AudioCodec:
         """How many kernel launches :meth:`encode` takes for float32 tensors of ``channels_n`` channels on ``device``
         (``ac_encode_launches``): 1 = the fused kernels (filters_n 64 ... 2048 in powers of two, mono / stereo), 2 = transform +
         one masking-model pass, 3 = the generic kernels."""
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        return int(self._lib.ac_encode_launches(self.mdct._plan(dev), self.psy._plan(dev), int(channels_n)))
+        return self._launches(self._lib.ac_encode_launches, device, channels_n)
+
+    def _launches(self, query, device, *counts, mdct=True):
+        """A ``*_launches`` method's answer: ``query`` on the plans of ``device`` (both, or the masking model's alone) and the
+        counts it takes."""
+        dev = _host.default_device(device)
+        plans = (self.mdct._plan(dev), self.psy._plan(dev)) if mdct else (self.psy._plan(dev),)
+        return int(query(*plans, *[int(n) for n in counts]))
 
     def encode(self, x, drown=0.0):
         """x [B, K*N, C] -> (X [B,K+1,N,C], tonality [B,K+1,1,C], threshold [B,K+1,N,C]).
@@ -103,10 +83,7 @@ class AudioCodec:
         pcm16 = isinstance(x, torch.Tensor) and x.dtype == torch.int16
         x = _host.check_device_tensor(x, "x", torch.int16 if pcm16 else self.compute_dtype, 3)
         B, S, C = x.shape
-        N = self.filters_n
-        if S % N != 0:
-            raise ValueError("samples_n (%d) is not a multiple of filters_n (%d)" % (S, N))
-        K = S // N
+        N, K = self.filters_n, _host.blocks_of(x, self.filters_n)
         # the library allocates what it returns, and decides where: spectra and thresholds in different classes of VRAM
         # (audiocodec_amd/placement.py; plain torch.empty for small batches, other dtypes, AC_NO_PLACEMENT=1)
         placement.ensure(self, (B, S, C), x.device)
@@ -134,11 +111,8 @@ class AudioCodec:
             return (X, t, thr, self.psy.add_noise(X, thr, seed=noise_seed) if noise_seed is not None else None,
                     self.psy.amplitude_to_dB_norm(X) if db_norm else None)
         x = _host.check_device_tensor(x, "x", self.compute_dtype, 3)
-        B, S, C = x.shape
-        N = self.filters_n
-        if S % N != 0:
-            raise ValueError("samples_n (%d) is not a multiple of filters_n (%d)" % (S, N))
-        K = S // N
+        B, _, C = x.shape
+        N, K = self.filters_n, _host.blocks_of(x, self.filters_n)
         X = torch.empty((B, K + 1, N, C), dtype=x.dtype, device=x.device)
         t = torch.empty((B, K + 1, 1, C), dtype=x.dtype, device=x.device)
         thr = torch.empty_like(X)
@@ -184,11 +158,8 @@ class AudioCodec:
         if pcm16 and self.compute_dtype != torch.float32:
             raise ValueError("16-bit PCM input needs compute_dtype float32")
         self._check_io(x, "x", None, torch.int16 if pcm16 else self.compute_dtype, None)
-        B, S, C = x.shape
-        N = self.filters_n
-        if S % N != 0:
-            raise ValueError("samples_n (%d) is not a multiple of filters_n (%d)" % (S, N))
-        K = S // N
+        B, _, C = x.shape
+        N, K = self.filters_n, _host.blocks_of(x, self.filters_n)
         self._check_io(X, "X", (B, K + 1, N, C), self.compute_dtype, x.device)
         self._check_io(t, "t", (B, K + 1, 1, C), self.compute_dtype, x.device)
         self._check_io(thr, "thr", (B, K + 1, N, C), self.compute_dtype, x.device)
@@ -235,9 +206,7 @@ class AudioCodec:
     def _encode_for_quantizer(self, x, drown, what):
         """X and the threshold of :meth:`encode` for the quantising method ``what``: float32 only, and no gradient."""
         _host.require_float32(self.compute_dtype, what)
-        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
-            raise ValueError("x requires a gradient: quantisation is not differentiable -- use encode() and "
-                             "psy.add_noise(), its differentiable stand-in")
+        _host.refuse_gradient(x)
         X, _, thr = self.encode(x, drown)
         return X, thr
 
@@ -246,9 +215,8 @@ class AudioCodec:
         (``ac_encode_quantized_launches``): 1 = the fused encode quantises the frame in its registers (filters_n = 1024, mono /
         stereo, spreading ``"f32"`` or ``"bf16x2_mfma"``), 2 = :meth:`encode`, then the quantiser.  ``pcm16=True``: for
         ``torch.int16`` PCM (``ac_encode_quantized_launches_pcm16``)."""
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         query = self._lib.ac_encode_quantized_launches_pcm16 if pcm16 else self._lib.ac_encode_quantized_launches
-        return int(query(self.mdct._plan(dev), self.psy._plan(dev), int(channels_n)))
+        return self._launches(query, device, channels_n)
 
     def encode_quantized(self, x, drown=0.0):
         """:meth:`encode`, then :meth:`PsychoacousticModel.quantize` on its X and threshold: x [B, K*N, C] (float or
@@ -280,8 +248,7 @@ class AudioCodec:
     def decode_quantized_launches(self, channels_n=2, device=None):
         """Launches :meth:`decode_quantized` takes for ``channels_n`` channels (``ac_decode_quantized_launches``): 1 = the
         synthesis dequantises in its loads (filters_n 1024 / 2048, mono / stereo), 2 = dequantise, then :meth:`decode`."""
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        return int(self._lib.ac_decode_quantized_launches(self.mdct._plan(dev), self.psy._plan(dev), int(channels_n)))
+        return self._launches(self._lib.ac_decode_quantized_launches, device, channels_n)
 
     def decode_quantized(self, codes, sf, pcm16=False):
         """codes int16 [B, K', N, C], sf int8 [B, K', M, C] -> x [B, (K'+1)*N, C] (``torch.int16`` with ``pcm16=True``):
@@ -293,14 +260,14 @@ class AudioCodec:
         codes, sf = self.psy._check_codes(codes, sf)
         B, Kp, N, C = codes.shape
         dev = codes.device
-        x = torch.empty((B, (Kp + 1) * N, C), dtype=torch.int16 if pcm16 else torch.float32, device=dev)
+        x, px, px16 = _host.pcm_out((B, (Kp + 1) * N, C), pcm16, dev)
         mdct, psy = self.mdct._plan(dev), self.psy._plan(dev)
         scratch = None
         if self._lib.ac_decode_quantized_launches(mdct, psy, C) != 1:
             scratch = torch.empty((B, Kp, N, C), dtype=torch.float32, device=dev)
         with _host.on_device(dev):
             _lib.check(self._lib.ac_decode_quantized(
-                mdct, psy, _host.ptr(codes), _host.ptr(sf), None if pcm16 else _host.ptr(x), _host.ptr(x) if pcm16 else None,
+                mdct, psy, _host.ptr(codes), _host.ptr(sf), px, px16,
                 _host.ptr(scratch) if scratch is not None else None, B, Kp, C, _host.stream_ptr(dev)))
         return x
 
@@ -350,9 +317,8 @@ class AudioCodec:
         else :meth:`encode_launches` + 2: the encode, the budgeted quantiser and the packer (everywhere while
         ``AC_ENCODE_PACKED_NOFUSE=1`` is set: read per call).  0 on a codec without a row budget.  ``pcm16=True``: for
         ``torch.int16`` PCM (``ac_encode_packed_launches_pcm16``)."""
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         query = self._lib.ac_encode_packed_launches_pcm16 if pcm16 else self._lib.ac_encode_packed_launches
-        return int(query(self.mdct._plan(dev), self.psy._plan(dev), int(channels_n)))
+        return self._launches(query, device, channels_n)
 
     def encode_packed_rows(self, x, drown=0.0):
         """On a codec made by :meth:`with_bitrate` / :meth:`with_row_budget`: x [B, K*N, C] (float32, or ``torch.int16``
@@ -368,28 +334,18 @@ class AudioCodec:
         synchronises with the device, only enqueues on the current stream, and can be captured in a graph.  float32 only,
         not differentiable."""
         _host.require_float32(self.compute_dtype, "encode_packed_rows")
-        if self.row_bits is None:
-            raise ValueError("encode_packed_rows needs a codec with a row budget: make one with with_bitrate() or "
-                             "with_row_budget()")
-        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
-            raise ValueError("x requires a gradient: quantisation is not differentiable -- use encode() and "
-                             "psy.add_noise(), its differentiable stand-in")
+        _rows.need_row_budget(self, "encode_packed_rows")
+        _host.refuse_gradient(x)
         pcm16 = isinstance(x, torch.Tensor) and x.dtype == torch.int16
         x = _host.check_device_tensor(x, "x", torch.int16 if pcm16 else torch.float32, 3)
-        B, S, C = x.shape
-        N = self.filters_n
-        if S % N != 0:
-            raise ValueError("samples_n (%d) is not a multiple of filters_n (%d)" % (S, N))
-        K = S // N
+        B, _, C = x.shape
+        N, K = self.filters_n, _host.blocks_of(x, self.filters_n)
         F, dev, rb = K + 1, x.device, self.row_bytes
-        rows = B * F * C
-        index = (torch.arange(rows, dtype=torch.int64, device=dev) * rb).view(B, F, C)
-        if rows == 0:
-            return (torch.empty((0,), dtype=torch.uint8, device=dev), index, torch.empty((B, F, C), dtype=torch.bool, device=dev))
+        if B * F * C == 0:
+            return _rows.outputs((B, F, C), rb, dev)
         mdct, psy = self.mdct._plan(dev), self.psy._plan(dev)
         if (self._lib.ac_encode_packed_launches_pcm16 if pcm16 else self._lib.ac_encode_packed_launches)(mdct, psy, C) == 1:
-            data = torch.empty((rows * rb,), dtype=torch.uint8, device=dev)
-            fits = torch.empty((B, F, C), dtype=torch.bool, device=dev)
+            data, index, fits = _rows.outputs((B, F, C), rb, dev)
             out = _lib.PackedOut(data.data_ptr(), rb, fits.data_ptr())
             with _host.on_device(dev):
                 _lib.check(self._lib.ac_encode_fused_ex(mdct, psy, _host.ptr(x), None, None, None, float(drown),
@@ -402,7 +358,8 @@ class AudioCodec:
         t = torch.empty((B, F, 1, C), dtype=torch.float32, device=dev)
         thr = torch.empty_like(X)
         self.encode_into(x, X, t, thr, drown)
-        data, fits = _pack_rows_of_spectra(self.psy, X, thr, index, rb)
+        index = _rows.row_starts((B, F, C), rb, dev)
+        data, fits = _rows.pack_rows_of_spectra(self.psy, X, thr, index, rb)
         return data, index, fits
 
     # ---- transrating packed rows (extension) ----------------------------------------------
@@ -412,8 +369,7 @@ class AudioCodec:
         64, a budget of at most ``_lib.AC_PACK_ROWS_MAX_BITS``; any channel count), else 3: :meth:`PsychoacousticModel.unpack`,
         :meth:`PsychoacousticModel.requantize_to_budget` and the packer (everywhere while ``AC_TRANSRATE_NOFUSE=1`` is set:
         read per call).  0 on a codec without a row budget."""
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        return int(self._lib.ac_transrate_launches(self.psy._plan(dev), int(channels_n)))
+        return self._launches(self._lib.ac_transrate_launches, device, channels_n, mdct=False)
 
     def transrate_packed_rows(self, data, index, return_offset=False):
         """On a codec made by :meth:`with_bitrate` / :meth:`with_row_budget`: packed rows at a higher bitrate -> the same
@@ -433,42 +389,16 @@ class AudioCodec:
         same bytes.  The size of ``data'`` is known before the call: it never synchronises with the device, only enqueues on
         the current stream, and can be captured in a graph.  Raising a bitrate is not possible.  float32 only."""
         _host.require_float32(self.compute_dtype, "transrate_packed_rows")
-        if self.row_bits is None:
-            raise ValueError("transrate_packed_rows needs a codec with a row budget: make one with with_bitrate() or "
-                             "with_row_budget()")
-        data = self.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
-        index = self.psy._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
-        B, F, C = index.shape
+        _rows.need_row_budget(self, "transrate_packed_rows")
+        data, index = _rows.check_pair(self.psy, data, index)
         dev, rb = data.device, self.row_bytes
-        rows = B * F * C
-        index_out = (torch.arange(rows, dtype=torch.int64, device=dev) * rb).view(B, F, C)
-        if rows == 0:
-            out = (torch.empty((0,), dtype=torch.uint8, device=dev), index_out, torch.empty((B, F, C), dtype=torch.bool, device=dev))
-            return out + (torch.empty((B, F, C), dtype=torch.int16, device=dev),) if return_offset else out
-        psy = self.psy._plan(dev)
-        if self._lib.ac_transrate_launches(psy, C) == 1:
-            out_data = torch.empty((rows * rb,), dtype=torch.uint8, device=dev)
-            fits = torch.empty((B, F, C), dtype=torch.bool, device=dev)
-            offset = torch.empty((B, F, C), dtype=torch.int16, device=dev) if return_offset else None
-            src = _lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr())
-            dst = _lib.PackedOut(out_data.data_ptr(), rb, fits.data_ptr())
-            with _host.on_device(dev):
-                _lib.check(self._lib.ac_encode_fused_ex(self.mdct._plan(dev), psy, ctypes.addressof(src), None, None, None, 0.0,
-                                                        _lib.AC_IN_PACKED | _lib.AC_EMIT_PACKED, ctypes.addressof(dst),
-                                                        _host.ptr(offset) if return_offset else None, 0, B, F - 1, C,
-                                                        _host.stream_ptr(dev)))
-            return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
+        if index.numel() == 0 or self._lib.ac_transrate_launches(self.psy._plan(dev), index.shape[2]) == 1:
+            out = _rows.outputs(tuple(index.shape), rb, dev, return_offset)
+            return _rows.repack(self, _rows.packed_rows(data, index), 0, out, rb) if index.numel() else out
         # the composition: the rows unpacked, requantised at the budget from offset 0, rows longer than their slot marked, then
         # the packer at the fixed row starts (on plain allocations: nothing here may wait for the device)
         codes, sf = self.psy.unpack(data, index)
-        codes, sf, offset, bits = self.psy.requantize_to_budget(codes, sf, self.row_bits, 0)
-        fits = bits <= 8 * rb
-        sf.masked_fill_(~fits.unsqueeze(2), -128)   # width 31 follows whatever the codes are
-        out_data = torch.zeros((rows * rb,), dtype=torch.uint8, device=dev)
-        with _host.on_device(dev):
-            _lib.check(self._lib.ac_pack(psy, _host.ptr(codes), _host.ptr(sf), _host.ptr(index_out), _host.ptr(out_data), B, F, C,
-                                         _host.stream_ptr(dev)))
-        return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
+        return _rows.pack_quantized(self.psy, self.psy.requantize_to_budget(codes, sf, self.row_bits, 0), rb, return_offset)
 
     # ---- mixing the packed rows of several sources (extension; DESIGN.md section 8h) ----------------------------
     def mix_packed_rows_launches(self, channels_n=2, device=None, *, sources_n):
@@ -477,8 +407,7 @@ class AudioCodec:
         :meth:`transrate_packed_rows_launches` is 1 and ``sources_n`` is at most ``_lib.AC_MIX_MAX_SOURCES``), else
         ``2 * sources_n + 2``: :meth:`PsychoacousticModel.unpack` and ``dequantize`` per source, ``quantize_to_budget`` and the
         packer (everywhere while ``AC_MIX_NOFUSE=1`` is set: read per call).  0 on a codec without a row budget."""
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        return int(self._lib.ac_mix_launches(self.psy._plan(dev), int(channels_n), int(sources_n)))
+        return self._launches(self._lib.ac_mix_launches, device, channels_n, sources_n, mdct=False)
 
     def mix_packed_rows(self, sources, gains=None, active=None, return_offset=False):
         """On a codec made by :meth:`with_bitrate` / :meth:`with_row_budget`: the packed rows of several sources of this
@@ -499,50 +428,26 @@ class AudioCodec:
         packer: the same bytes.  It never synchronises with the device, only enqueues on the current stream, and can be
         captured in a graph.  float32 only."""
         _host.require_float32(self.compute_dtype, "mix_packed_rows")
-        if self.row_bits is None:
-            raise ValueError("mix_packed_rows needs a codec with a row budget: make one with with_bitrate() or with_row_budget()")
+        _rows.need_row_budget(self, "mix_packed_rows")
         sources = list(sources)
         if not sources:
             raise ValueError("mix_packed_rows needs at least one source")
         S = len(sources)
         gains = self.psy._check_gains(gains, S)
-        pairs = []
-        for i, (data, index) in enumerate(sources):
-            data = self.psy._check_quant_tensor(data, "data of source %d" % i, torch.uint8, ndim=1)
-            index = self.psy._check_quant_tensor(index, "index of source %d" % i, torch.int64, device=data.device, ndim=3)
-            if pairs and (index.shape != pairs[0][1].shape or index.device != pairs[0][1].device):
-                raise ValueError("index of source %d has shape %s on %s, that of source 0 shape %s on %s"
-                                 % (i, tuple(index.shape), index.device, tuple(pairs[0][1].shape), pairs[0][1].device))
-            pairs.append((data, index))
-        B, F, C = pairs[0][1].shape
-        dev, rb = pairs[0][1].device, self.row_bytes
-        active = self.psy._check_active(active, S, (B, F, C), dev)
-        rows = B * F * C
-        index_out = (torch.arange(rows, dtype=torch.int64, device=dev) * rb).view(B, F, C)
-        if rows == 0:
-            out = (torch.empty((0,), dtype=torch.uint8, device=dev), index_out, torch.empty((B, F, C), dtype=torch.bool, device=dev))
-            return out + (torch.empty((B, F, C), dtype=torch.int16, device=dev),) if return_offset else out
-        psy = self.psy._plan(dev)
-        if self._lib.ac_mix_launches(psy, C, S) == 1:
-            out_data = torch.empty((rows * rb,), dtype=torch.uint8, device=dev)
-            fits = torch.empty((B, F, C), dtype=torch.bool, device=dev)
-            offset = torch.empty((B, F, C), dtype=torch.int16, device=dev) if return_offset else None
-            src = (_lib.PackedRows * S)(*[_lib.PackedRows(d.data_ptr(), d.numel(), ix.data_ptr()) for d, ix in pairs])
-            gain = (ctypes.c_int32 * S)(*gains)
+        pairs, shape, dev = _rows.check_sources(self.psy, sources)
+        active = self.psy._check_active(active, S, shape, dev)
+        rows, rb = pairs[0][1].numel(), self.row_bytes
+        if rows == 0 or self._lib.ac_mix_launches(self.psy._plan(dev), shape[2], S) == 1:
+            out = _rows.outputs(shape, rb, dev, return_offset)
+            if rows == 0:
+                return out
+            src, gain = _rows.source_rows(pairs), (ctypes.c_int32 * S)(*gains)
             mix = _lib.MixRows(S, src, gain, active.data_ptr() if active is not None else None)
-            dst = _lib.PackedOut(out_data.data_ptr(), rb, fits.data_ptr())
-            with _host.on_device(dev):
-                _lib.check(self._lib.ac_encode_fused_ex(self.mdct._plan(dev), psy, ctypes.addressof(mix), None, None, None, 0.0,
-                                                        _lib.AC_IN_PACKED | _lib.AC_EMIT_PACKED | _lib.AC_IN_MIX,
-                                                        ctypes.addressof(dst), _host.ptr(offset) if return_offset else None, 0,
-                                                        B, F - 1, C, _host.stream_ptr(dev)))
-            return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
+            return _rows.repack(self, mix, _lib.AC_IN_MIX, out, rb)
         # the composition: every source unpacked, the rows mixed at the budget, rows longer than their slot marked, then the
         # packer at the fixed row starts (on plain allocations: nothing here may wait for the device)
         unpacked = [self.psy.unpack(d, ix) for d, ix in pairs]
-        codes, sf, offset, bits = self.psy.mix_to_budget(unpacked, gains, self.row_bits, active)
-        out_data, fits = _pack_rows_of_codes(self.psy, codes, sf, bits, index_out, rb)
-        return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
+        return _rows.pack_quantized(self.psy, self.psy.mix_to_budget(unpacked, gains, self.row_bits, active), rb, return_offset)
 
     # ---- routing the packed rows of several sources to several mixes (extension; DESIGN.md section 8i) --------------
     @staticmethod
@@ -582,8 +487,7 @@ class AudioCodec:
         ``_lib.AC_ROUTE_MAX_OUTPUTS``),
         else ``outputs_n`` times :meth:`mix_packed_rows_launches`, the composition (everywhere while ``AC_ROUTE_NOFUSE=1`` is
         set: read per call).  0 on a codec without a row budget."""
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        return int(self._lib.ac_route_launches(self.psy._plan(dev), int(channels_n), int(sources_n), int(outputs_n)))
+        return self._launches(self._lib.ac_route_launches, device, channels_n, sources_n, outputs_n, mdct=False)
 
     def route_packed_rows(self, sources, routes, active=None, return_offset=False):
         """On a codec made by :meth:`with_bitrate` / :meth:`with_row_budget`: the packed rows of S sources -> O mixes of
@@ -602,45 +506,25 @@ class AudioCodec:
         bytes.  It never synchronises with the device, only enqueues on the current stream, and can be captured in a graph.
         float32 only."""
         _host.require_float32(self.compute_dtype, "route_packed_rows")
-        if self.row_bits is None:
-            raise ValueError("route_packed_rows needs a codec with a row budget: make one with with_bitrate() or with_row_budget()")
+        _rows.need_row_budget(self, "route_packed_rows")
         sources = list(sources)
         if not sources:
             raise ValueError("route_packed_rows needs at least one source")
         S = len(sources)
         routes = self._check_routes(routes, S)
         O = len(routes)
-        pairs = []
-        for i, (data, index) in enumerate(sources):
-            data = self.psy._check_quant_tensor(data, "data of source %d" % i, torch.uint8, ndim=1)
-            index = self.psy._check_quant_tensor(index, "index of source %d" % i, torch.int64, device=data.device, ndim=3)
-            if pairs and (index.shape != pairs[0][1].shape or index.device != pairs[0][1].device):
-                raise ValueError("index of source %d has shape %s on %s, that of source 0 shape %s on %s"
-                                 % (i, tuple(index.shape), index.device, tuple(pairs[0][1].shape), pairs[0][1].device))
-            pairs.append((data, index))
-        B, F, C = pairs[0][1].shape
-        dev, rb = pairs[0][1].device, self.row_bytes
-        active = self.psy._check_active(active, S, (B, F, C), dev)
-        rows = B * F * C
-        index_out = (torch.arange(rows, dtype=torch.int64, device=dev) * rb).view(B, F, C)
-        out_data = torch.empty((O, rows * rb), dtype=torch.uint8, device=dev)
-        fits = torch.empty((O, B, F, C), dtype=torch.bool, device=dev)
-        offset = torch.empty((O, B, F, C), dtype=torch.int16, device=dev) if return_offset else None
-        if rows == 0:
-            return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
-        psy = self.psy._plan(dev)
+        pairs, shape, dev = _rows.check_sources(self.psy, sources)
+        active = self.psy._check_active(active, S, shape, dev)
+        rb = self.row_bytes
+        out = _rows.outputs(shape, rb, dev, return_offset, lead=(O,))
+        if pairs[0][1].numel() == 0:
+            return out
         # (a single output's composition is one launch too: the switch itself decides there)
-        if self._lib.ac_route_launches(psy, C, S, O) == 1 and os.environ.get("AC_ROUTE_NOFUSE") != "1":
-            src = (_lib.PackedRows * S)(*[_lib.PackedRows(d.data_ptr(), d.numel(), ix.data_ptr()) for d, ix in pairs])
+        if self._lib.ac_route_launches(self.psy._plan(dev), shape[2], S, O) == 1 and os.environ.get("AC_ROUTE_NOFUSE") != "1":
+            src = _rows.source_rows(pairs)
             gain = (ctypes.c_int32 * (O * S))(*[_lib.AC_ROUTE_MUTE if g is None else g for row in routes for g in row])
             route = _lib.RouteRows(S, O, src, gain, active.data_ptr() if active is not None else None)
-            dst = _lib.PackedOut(out_data.data_ptr(), rb, fits.data_ptr())
-            with _host.on_device(dev):
-                _lib.check(self._lib.ac_encode_fused_ex(self.mdct._plan(dev), psy, ctypes.addressof(route), None, None, None, 0.0,
-                                                        _lib.AC_IN_PACKED | _lib.AC_EMIT_PACKED | _lib.AC_IN_ROUTE,
-                                                        ctypes.addressof(dst), _host.ptr(offset) if return_offset else None, 0,
-                                                        B, F - 1, C, _host.stream_ptr(dev)))
-            return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
+            return _rows.repack(self, route, _lib.AC_IN_ROUTE, out, rb)
         # the composition: one mix per output on the sources it hears (an output that hears nothing: source 0, never read)
         silent = None
         for o, row in enumerate(routes):
@@ -650,13 +534,11 @@ class AudioCodec:
                 one = self.mix_packed_rows([pairs[i] for i in inc], [row[i] for i in inc], act, return_offset)
             else:
                 if silent is None:
-                    silent = torch.zeros((1, B, F, C), dtype=torch.uint8, device=dev)
+                    silent = torch.zeros((1,) + shape, dtype=torch.uint8, device=dev)
                 one = self.mix_packed_rows(pairs[:1], [0], silent, return_offset)
-            out_data[o].copy_(one[0])
-            fits[o].copy_(one[2])
-            if return_offset:
-                offset[o].copy_(one[3])
-        return (out_data, index_out, fits, offset) if return_offset else (out_data, index_out, fits)
+            for mine, its in zip(out[:1] + out[2:], one[:1] + one[2:]):   # (data, fits and, asked for, offset)
+                mine[o].copy_(its)
+        return out
 
     # ---- the level of packed rows and the loudest sources (extension) ------------------------
     def packed_rows_level_launches(self, channels_n=2, device=None):
@@ -665,8 +547,7 @@ class AudioCodec:
         without a row budget), 0 = the library has no launch of its own and the method runs the composition on
         :meth:`PsychoacousticModel.unpack` and :meth:`PsychoacousticModel.level` (everywhere while ``AC_LEVEL_NOFUSE=1`` is
         set: read per call)."""
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        return int(self._lib.ac_level_launches(self.psy._plan(dev), int(channels_n)))
+        return self._launches(self._lib.ac_level_launches, device, channels_n, mdct=False)
 
     def packed_rows_level(self, data, index, return_bad=False):
         """The energy of packed rows, from the rows themselves, without decoding: data uint8 [nbytes], index int64 [B, F, C]
@@ -681,23 +562,14 @@ class AudioCodec:
         bits.  It never synchronises with the device, only enqueues on the current stream, and can be captured in a graph.
         Works with or without a row budget.  float32 only."""
         _host.require_float32(self.compute_dtype, "packed_rows_level")
-        data = self.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
-        index = self.psy._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
-        B, F, C = index.shape
-        dev = data.device
-        if B * F * C == 0:
-            energy = torch.empty((B, F, C), dtype=torch.float32, device=dev)
-            return (energy, torch.empty((B, F, C), dtype=torch.uint8, device=dev)) if return_bad else energy
-        psy = self.psy._plan(dev)
-        if self._lib.ac_level_launches(psy, C) == 1:
-            energy = torch.empty((B, F, C), dtype=torch.float32, device=dev)
-            bad = torch.empty((B, F, C), dtype=torch.uint8, device=dev) if return_bad else None
-            src = _lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr())
-            with _host.on_device(dev):
-                _lib.check(self._lib.ac_encode_fused_ex(self.mdct._plan(dev), psy, ctypes.addressof(src), None, None, None, 0.0,
-                                                        _lib.AC_IN_PACKED | _lib.AC_EMIT_LEVEL, _host.ptr(energy),
-                                                        _host.ptr(bad) if return_bad else None, 0, B, F - 1, C,
-                                                        _host.stream_ptr(dev)))
+        data, index = _rows.check_pair(self.psy, data, index)
+        shape, dev = tuple(index.shape), data.device
+        if index.numel() == 0 or self._lib.ac_level_launches(self.psy._plan(dev), shape[2]) == 1:
+            energy = torch.empty(shape, dtype=torch.float32, device=dev)
+            bad = torch.empty(shape, dtype=torch.uint8, device=dev) if return_bad else None
+            if index.numel():
+                _rows.fused_ex(self, dev, _rows.packed_rows(data, index), _lib.AC_IN_PACKED | _lib.AC_EMIT_LEVEL, energy, bad,
+                               shape)
             return (energy, bad) if return_bad else energy
         # the composition (the kernel's reference): the rows unpacked, then the band sums and the fold tree as tensor operations
         energy, bad = self.psy.level(*self.psy.unpack(data, index))
@@ -774,10 +646,7 @@ class AudioCodec:
         if S <= _lib.AC_SELECT_MAX_SOURCES:
             sel = _lib.SelectRows(S, energy.data_ptr(), valid.data_ptr() if valid is not None else None, int(n), release, gate,
                                   state.data_ptr() if state is not None else None)
-            with _host.on_device(dev):
-                _lib.check(self._lib.ac_encode_fused_ex(self.mdct._plan(dev), self.psy._plan(dev), ctypes.addressof(sel), None, None,
-                                                        None, 0.0, _lib.AC_SELECT_ACTIVE, _host.ptr(active), None, 0, B, F - 1, C,
-                                                        _host.stream_ptr(dev)))
+            _rows.fused_ex(self, dev, sel, _lib.AC_SELECT_ACTIVE, active, None, (B, F, C))
             return active
         # more sources than a wave has lanes: the rules frame by frame as tensor operations (slow; the same values)
         ok = energy > 0
@@ -802,8 +671,7 @@ class AudioCodec:
 
     # ---- protected rows: a redundant copy of the frame before in every slot (extension) ---
     def _check_red_bits(self, red_bits, what):
-        if self.row_bits is None:
-            raise ValueError("%s needs a codec with a row budget: make one with with_bitrate() or with_row_budget()" % what)
+        _rows.need_row_budget(self, what)
         if isinstance(red_bits, bool) or not isinstance(red_bits, (int, np.integer)):
             raise TypeError("red_bits must be an int, got %s" % type(red_bits).__name__)
         if red_bits < 5 * self.psy.bark_bands_n:
@@ -830,9 +698,10 @@ class AudioCodec:
         and ``red_bits`` is at most ``_lib.AC_PACK_ROWS_MAX_BITS``), else those of the two :meth:`transrate_packed_rows`
         calls of the composition (everywhere while ``AC_PROTECT_NOFUSE=1`` is set: read per call).  0 on a codec without
         a row budget."""
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.row_bits is None:
+        dev = _host.default_device(device)
+        if self.row_bits is None:   # (ahead of the look at red_bits)
             return 0
+        # (not through _launches: channels_n is looked at ahead of red_bits)
         return int(self._lib.ac_protect_launches(self.psy._plan(dev), int(channels_n), self._check_red_bits(red_bits, "")))
 
     def protect_packed_rows(self, data, index, red_bits, return_offset=False):
@@ -851,49 +720,8 @@ class AudioCodec:
         bytes.  Never synchronises with the device, only enqueues on the current stream, and can be captured in a graph."""
         _host.require_float32(self.compute_dtype, "protect_packed_rows")
         red_bits = self._check_red_bits(red_bits, "protect_packed_rows")
-        data = self.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
-        index = self.psy._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
-        B, F, C = index.shape
-        dev, rb = data.device, self.row_bytes
-        sb = self.protected_slot_bytes(red_bits)
-        rows = B * F * C
-        index_out = (torch.arange(rows, dtype=torch.int64, device=dev) * sb).view(B, F, C)
-        if rows == 0:
-            flags = tuple(torch.empty((B, F, C), dtype=torch.bool, device=dev) for _ in range(2))
-            offs = tuple(torch.empty((B, F, C), dtype=torch.int16, device=dev) for _ in range(2)) if return_offset else ()
-            return (torch.empty((0,), dtype=torch.uint8, device=dev), index_out) + flags + offs
-        psy = self.psy._plan(dev)
-        if self._lib.ac_protect_launches(psy, C, red_bits) == 1:
-            out_data = torch.empty((rows * sb,), dtype=torch.uint8, device=dev)
-            fits = torch.empty((B, F, C), dtype=torch.bool, device=dev)
-            red_fits = torch.empty((B, F, C), dtype=torch.bool, device=dev)
-            offset = torch.empty((B, F, C), dtype=torch.int16, device=dev) if return_offset else None
-            red_offset = torch.empty((B, F, C), dtype=torch.int16, device=dev) if return_offset else None
-            src = _lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr())
-            dst = _lib.ProtectedOut(out_data.data_ptr(), rb, fits.data_ptr(), red_bits, red_fits.data_ptr(),
-                                    offset.data_ptr() if return_offset else None,
-                                    red_offset.data_ptr() if return_offset else None)
-            with _host.on_device(dev):
-                _lib.check(self._lib.ac_encode_fused_ex(
-                    self.mdct._plan(dev), psy, ctypes.addressof(src), None, None, None, 0.0,
-                    _lib.AC_IN_PACKED | _lib.AC_EMIT_PACKED | _lib.AC_EMIT_REDUNDANT, ctypes.addressof(dst), None, 0, B, F - 1,
-                    C, _host.stream_ptr(dev)))
-            out = (out_data, index_out, fits, red_fits)
-            return out + (offset, red_offset) if return_offset else out
-        # the composition: the rows transrated at both budgets, then copied into the two parts of every slot
-        prim = self.transrate_packed_rows(data, index, True)
-        red = self._redundant_codec(red_bits).transrate_packed_rows(data, index, True)
-        slots = torch.zeros((B, F, C, sb), dtype=torch.uint8, device=dev)
-        slots[..., :rb] = prim[0].view(B, F, C, rb)
-        slots[:, 1:, :, rb:] = red[0].view(B, F, C, sb - rb)[:, :-1]
-        red_fits = torch.ones((B, F, C), dtype=torch.bool, device=dev)
-        red_fits[:, 1:] = red[2][:, :-1]
-        out = (slots.view(-1), index_out, prim[2], red_fits)
-        if return_offset:
-            red_offset = torch.zeros((B, F, C), dtype=torch.int16, device=dev)
-            red_offset[:, 1:] = red[3][:, :-1]
-            out += (prim[3], red_offset)
-        return out
+        data, index = _rows.check_pair(self.psy, data, index)
+        return _rows.protect(self, data, index, red_bits, return_offset)
 
     def protect_stream(self, batches_n, channels_n, red_bits, device=None):
         """On a codec with a row budget: a :class:`ProtectStream` for ``batches_n`` clips of ``channels_n`` channels --
@@ -935,8 +763,7 @@ class AudioCodec:
         synthesis reads the bitstream itself (filters_n = 1024, bark_bands_n = 64, mono / stereo), else 1 +
         :meth:`decode_quantized_launches`: :meth:`PsychoacousticModel.unpack`, then :meth:`decode_quantized`
         (everywhere while ``AC_DECODE_PACKED_NOFUSE=1`` is set: read per call)."""
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        return int(self._lib.ac_decode_packed_launches(self.mdct._plan(dev), self.psy._plan(dev), int(channels_n)))
+        return self._launches(self._lib.ac_decode_packed_launches, device, channels_n)
 
     def decode_packed(self, data, index, pcm16=False, *, lost=None, max_age=8, redundant_at=None):
         """data uint8 [nbytes], index int64 [B, K', C] -> x [B, (K'+1)*N, C] (``torch.int16`` with ``pcm16=True``);
@@ -964,50 +791,36 @@ class AudioCodec:
             if lost is None:
                 raise ValueError("redundant_at without lost: a row is recovered only where lost marks it")
             redundant_at = self.psy._check_redundant_at(redundant_at)
-        if lost is not None:
-            return self._decode_packed_concealed(data, index, pcm16, lost, max_age, redundant_at)
+        if lost is not None:   # the concealing kernel where packed rows are decoded in one launch, the composition elsewhere
+            max_age = self.psy._check_max_age(max_age)
+            data, index = _rows.check_pair(self.psy, data, index)
+            lost = self.psy._check_lost(lost, index)
+            if index.numel() and self.decode_packed_launches(index.shape[2], data.device) == 1:
+                if redundant_at is None:
+                    conceal = _lib.Conceal(lost.data_ptr(), max_age)
+                else:
+                    conceal = _lib.ConcealRedundant(lost.data_ptr(), max_age | _lib.AC_CONCEAL_REDUNDANT, redundant_at)
+                return self._decode_packed_launch(data, index, pcm16, conceal)
+            src_index, age = self.psy.conceal_plan(index, lost, data.numel(), max_age, redundant_at)
+            codes, sf = self.psy.unpack(data, src_index)
+            return self.decode_quantized(codes, self.psy.conceal_fade(sf, age), pcm16)
         if (isinstance(data, torch.Tensor) and isinstance(index, torch.Tensor) and data.is_cuda and index.dim() == 3
                 and index.shape[1] >= 1 and self.decode_packed_launches(index.shape[2], data.device) == 1):
-            data = self.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
-            index = self.psy._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
-            B, Kp, C = index.shape
-            dev = data.device
-            x = torch.empty((B, (Kp + 1) * self.filters_n, C), dtype=torch.int16 if pcm16 else torch.float32, device=dev)
-            rows = _lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr())
-            with _host.on_device(dev):
-                _lib.check(self._lib.ac_decode_quantized(
-                    self.mdct._plan(dev), self.psy._plan(dev), ctypes.addressof(rows), None,
-                    None if pcm16 else _host.ptr(x), _host.ptr(x) if pcm16 else None, None, B, Kp, C,
-                    _host.stream_ptr(dev)))
-            return x
+            return self._decode_packed_launch(*_rows.check_pair(self.psy, data, index), pcm16)
         codes, sf = self.psy.unpack(data, index)
         return self.decode_quantized(codes, sf, pcm16)
 
-    def _decode_packed_concealed(self, data, index, pcm16, lost, max_age, redundant_at=None):
-        """:meth:`decode_packed` with ``lost`` given: the concealing kernel where packed rows are decoded in one launch, the
-        composition elsewhere."""
-        max_age = self.psy._check_max_age(max_age)
-        data = self.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
-        index = self.psy._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
-        lost = self.psy._check_lost(lost, index)
+    def _decode_packed_launch(self, data, index, pcm16, conceal=None):
+        """:meth:`decode_packed`'s one launch on a checked pair; ``conceal``: the ``ac_conceal`` struct of lost rows."""
         B, Kp, C = index.shape
         dev = data.device
-        if B >= 1 and Kp >= 1 and C >= 1 and self.decode_packed_launches(C, dev) == 1:
-            x = torch.empty((B, (Kp + 1) * self.filters_n, C), dtype=torch.int16 if pcm16 else torch.float32, device=dev)
-            rows = _lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr())
-            if redundant_at is None:
-                conceal = _lib.Conceal(lost.data_ptr(), max_age)
-            else:
-                conceal = _lib.ConcealRedundant(lost.data_ptr(), max_age | _lib.AC_CONCEAL_REDUNDANT, redundant_at)
-            with _host.on_device(dev):
-                _lib.check(self._lib.ac_decode_quantized(
-                    self.mdct._plan(dev), self.psy._plan(dev), ctypes.addressof(rows), None,
-                    None if pcm16 else _host.ptr(x), _host.ptr(x) if pcm16 else None, ctypes.addressof(conceal), B, Kp, C,
-                    _host.stream_ptr(dev)))
-            return x
-        src_index, age = self.psy.conceal_plan(index, lost, data.numel(), max_age, redundant_at)
-        codes, sf = self.psy.unpack(data, src_index)
-        return self.decode_quantized(codes, self.psy.conceal_fade(sf, age), pcm16)
+        x, px, px16 = _host.pcm_out((B, (Kp + 1) * self.filters_n, C), pcm16, dev)
+        rows = _rows.packed_rows(data, index)   # (this frame holds rows and conceal until the call is back)
+        with _host.on_device(dev):
+            _lib.check(self._lib.ac_decode_quantized(
+                self.mdct._plan(dev), self.psy._plan(dev), ctypes.addressof(rows), None, px, px16,
+                ctypes.addressof(conceal) if conceal is not None else None, B, Kp, C, _host.stream_ptr(dev)))
+        return x
 
     def decode_into(self, X, x):
         """:meth:`decode` into a caller-owned PCM tensor ``x [B, (K'+1)*N, C]`` (``torch.int16`` selects 16-bit PCM);
@@ -1031,665 +844,3 @@ class AudioCodec:
         with _host.on_device(X.device):
             _lib.check(fn(self.mdct._plan(X.device), _host.ptr(X), _host.ptr(x), B, Kp, C, _host.stream_ptr(X.device)))
 
-
-class ProtectStream:
-    """:meth:`AudioCodec.protect_packed_rows` chunk by chunk (``AudioCodec.protect_stream``; DESIGN.md section 8g, "Streams").
-
-    :meth:`protect_chunk` returns what ``protect_packed_rows`` returns for the chunk's ``k`` frames, in the same layout, but
-    the redundant part, ``red_fits`` and ``red_offset`` of frame 0 are the copy at ``red_bits`` of the previous chunk's last
-    *input* row -- on a fresh or reset stream the values of f = 0 -- and the copy of the chunk's last input row is kept for
-    the next chunk.  So for any split the chunks' slots, flags and offsets, put together along frames, are those of the
-    one-shot call on all rows, byte for byte.  The carry lives on the device, double buffered; the calls only enqueue, on
-    ``stream`` or the current stream, and calls on one object are ordered by the caller."""
-
-    def __init__(self, codec, batches_n, channels_n, red_bits, device=None):
-        if codec.row_bits is None:
-            raise ValueError("protect_stream needs a codec with a row budget (with_bitrate() / with_row_budget())")
-        self.codec, self.red_bits = codec, red_bits
-        self.B, self.C = int(batches_n), int(channels_n)
-        if self.B < 1 or self.C < 1:
-            raise ValueError("batches_n (%d) and channels_n (%d) must be positive" % (self.B, self.C))
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self._red_bytes = (red_bits + 31) // 32 * 4
-        # two halves of (row, fits, offset); _cur is the half the last chunk wrote, None on a fresh stream
-        self._carry = [(torch.zeros((self.B, self.C, self._red_bytes), dtype=torch.uint8, device=self.device),
-                        torch.ones((self.B, self.C), dtype=torch.bool, device=self.device),
-                        torch.zeros((self.B, self.C), dtype=torch.int16, device=self.device)) for _ in range(2)]
-        self._cur = None
-
-    def reset(self):
-        """The next chunk's frame 0 takes the values of f = 0 again.  No device work."""
-        self._cur = None
-
-    def launches(self):
-        """Library launches of :meth:`protect_chunk` (``ac_protect_chunk_launches``): 1 where
-        ``protect_packed_rows_launches`` is 1, else those of the composition's two transrating calls (everywhere while
-        ``AC_PROTECT_NOFUSE=1`` is set: read per call)."""
-        return int(self.codec._lib.ac_protect_chunk_launches(self.codec.psy._plan(self.device), self.C, self.red_bits))
-
-    def protect_chunk(self, data, index, return_offset=False, stream=None):
-        """data uint8 [nbytes], index int64 [B, k, C] -> (data', index', fits, red_fits) and, with ``return_offset``, offset
-        and red_offset: ``protect_packed_rows``' outputs for the chunk (``index'`` the chunk's own arithmetic index), frame 0
-        taking the carried copy.  ``k = 0`` changes nothing."""
-        codec = self.codec
-        with (torch.cuda.stream(stream) if stream is not None else _host._NO_SWITCH):
-            data = codec.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
-            if data.device != self.device:
-                raise ValueError("data lives on %s but the stream's carry lives on %s" % (data.device, self.device))
-            index = codec.psy._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
-            B, k, C = index.shape
-            if (B, C) != (self.B, self.C):
-                raise ValueError("index must be [%d, k, %d], got %s" % (self.B, self.C, tuple(index.shape)))
-            dev, rb, red_bits = self.device, codec.row_bytes, self.red_bits
-            sb = codec.protected_slot_bytes(red_bits)
-            rows = B * k * C
-            index_out = (torch.arange(rows, dtype=torch.int64, device=dev) * sb).view(B, k, C)
-            if k == 0:
-                flags = tuple(torch.empty((B, k, C), dtype=torch.bool, device=dev) for _ in range(2))
-                offs = tuple(torch.empty((B, k, C), dtype=torch.int16, device=dev) for _ in range(2)) if return_offset else ()
-                return (torch.empty((0,), dtype=torch.uint8, device=dev), index_out) + flags + offs
-            src_half = None if self._cur is None else self._carry[self._cur]
-            nxt = 0 if self._cur is None else self._cur ^ 1
-            dst_half = self._carry[nxt]
-            psy = codec.psy._plan(dev)
-            if codec._lib.ac_protect_chunk_launches(psy, C, red_bits) == 1:
-                out_data = torch.empty((rows * sb,), dtype=torch.uint8, device=dev)
-                fits = torch.empty((B, k, C), dtype=torch.bool, device=dev)
-                red_fits = torch.empty((B, k, C), dtype=torch.bool, device=dev)
-                offset = torch.empty((B, k, C), dtype=torch.int16, device=dev) if return_offset else None
-                red_offset = torch.empty((B, k, C), dtype=torch.int16, device=dev) if return_offset else None
-                src = _lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr())
-                dst = _lib.ProtectedOut(out_data.data_ptr(), rb, fits.data_ptr(), red_bits, red_fits.data_ptr(),
-                                        offset.data_ptr() if return_offset else None,
-                                        red_offset.data_ptr() if return_offset else None)
-                carry = _lib.ProtectCarry(*((None, None, None) if src_half is None else [t.data_ptr() for t in src_half]),
-                                          *[t.data_ptr() for t in dst_half])
-                with _host.on_device(dev):
-                    _lib.check(codec._lib.ac_encode_fused_ex(
-                        codec.mdct._plan(dev), psy, ctypes.addressof(src), None, None, None, 0.0,
-                        _lib.AC_IN_PACKED | _lib.AC_EMIT_PACKED | _lib.AC_EMIT_REDUNDANT | _lib.AC_EMIT_CARRY,
-                        ctypes.addressof(dst), ctypes.addressof(carry), 0, B, k - 1, C,
-                        _host.stream_ptr(dev) if stream is None else ctypes.c_void_p(stream.cuda_stream)))
-                self._cur = nxt
-                out = (out_data, index_out, fits, red_fits)
-                return out + (offset, red_offset) if return_offset else out
-            # the composition: the rows transrated at both budgets, copied into the slots; frame 0 from the carry, the copy of
-            # the last row into the carry's other half
-            prim = codec.transrate_packed_rows(data, index, True)
-            red = codec._redundant_codec(red_bits).transrate_packed_rows(data, index, True)
-            red_rows = red[0].view(B, k, C, sb - rb)
-            slots = torch.zeros((B, k, C, sb), dtype=torch.uint8, device=dev)
-            slots[..., :rb] = prim[0].view(B, k, C, rb)
-            slots[:, 1:, :, rb:] = red_rows[:, :-1]
-            red_fits = torch.ones((B, k, C), dtype=torch.bool, device=dev)
-            red_fits[:, 1:] = red[2][:, :-1]
-            red_offset = torch.zeros((B, k, C), dtype=torch.int16, device=dev)
-            red_offset[:, 1:] = red[3][:, :-1]
-            if src_half is not None:
-                slots[:, 0, :, rb:] = src_half[0]
-                red_fits[:, 0] = src_half[1]
-                red_offset[:, 0] = src_half[2]
-            dst_half[0].copy_(red_rows[:, -1])
-            dst_half[1].copy_(red[2][:, -1])
-            dst_half[2].copy_(red[3][:, -1])
-            self._cur = nxt
-            out = (slots.view(-1), index_out, prim[2], red_fits)
-            return out + (prim[3], red_offset) if return_offset else out
-
-
-class StreamingMDCT:
-    """Chunked analysis / synthesis with device-resident overlap state (BASELINE config 5).
-
-    Feeding consecutive chunks of ``k`` blocks gives, frame for frame, the one-shot ``transform`` /
-    ``inverse_transform`` result: analysis frame ``i`` of a chunk pairs block ``i`` with block ``i-1``
-    (the stored last block of the previous chunk for ``i = 0``); synthesis block ``i`` overlap-adds
-    frame ``i`` with the stored aliased half of the previous frame.  With a masking model (``psy``)
-    :meth:`encode_chunk` also returns tonality and threshold of the chunk's frames -- bit for bit what the one-shot
-    ``AudioCodec.encode`` gives for those frames.  On a stream of a codec at a bitrate (``with_bitrate()``)
-    :meth:`encode_packed_rows_chunk` and :meth:`decode_packed_chunk` go from a chunk of PCM to fixed-stride packed rows and
-    back on the same state, one launch each where :meth:`packed_chunk_launches` is 1.
-
-    Streams: every chunk call only enqueues on its stream -- the current one, or ``stream=`` -- and never touches the
-    default stream or waits for the device.  Creating the object may block the host and leaves the float32 state zeroed;
-    the float64 state is allocated by the first float64 chunk call and zeroed on that call's stream, ahead of its
-    kernels.  Results a chunk call allocates itself (``out=None``) are allocated under the stream the work runs on, so
-    torch's allocator hands their memory on in that stream's order; a caller that consumes them on another stream
-    orders that itself (an event, and ``record_stream``).  The overlap state is carried from call to call: calls on one
-    object are ordered by the caller (one stream, or events between streams).
-    """
-
-    def __init__(self, mdct: MDCTransformer, batches_n, channels_n, device=None, psy: PsychoacousticModel = None):
-        if mdct.compute_dtype not in (torch.float32, torch.float64, torch.bfloat16):
-            raise NotImplementedError("streaming overlap-add serves compute_dtype float32 and float64 (every size) and bfloat16 "
-                                      "(the wave-level kernels: filters_n 1024 / 2048, mono / stereo); got %s" % mdct.compute_dtype)
-        if psy is not None:
-            if psy.compute_dtype != mdct.compute_dtype:
-                raise ValueError("psy.compute_dtype (%s) != mdct.compute_dtype (%s)" % (psy.compute_dtype, mdct.compute_dtype))
-            if psy.filter_bands_n != mdct.filters_n:
-                raise ValueError("psy.filter_bands_n (%d) != mdct.filters_n (%d)" % (psy.filter_bands_n, mdct.filters_n))
-        self.mdct, self.psy = mdct, psy
-        self.B, self.C = int(batches_n), int(channels_n)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self._lib = _lib.load()
-        handle = ctypes.c_void_p()
-        with _host.on_device(self.device):
-            _lib.check(self._lib.ac_stream_create(mdct._plan(self.device), self.B, self.C, ctypes.byref(handle)))
-        self._handle = handle
-        self._graphs = {}       # run(..., graph=True): captured calls by input buffers and arguments
-        self._conceal = None    # decode_packed_chunk(lost=...) where it is composed: (carried codes, sf, gap), None = no source
-        # decode_packed_chunk(redundant_at=...) synthesises one frame behind its rows (DESIGN.md section 8g, "Streams"):
-        # _delayed from the first such chunk, _advanced from the first other call that moved the synthesis, until reset()
-        self._delayed = self._advanced = False
-
-    def close(self):
-        self._graphs = {}       # (the graphs hold launches that address the stream's state)
-        if self._handle is not None:
-            self._lib.ac_stream_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        self._conceal = None
-        self._delayed = self._advanced = False
-        with _host.on_device(self.device):
-            _lib.check(self._lib.ac_stream_reset(self._handle, _host.stream_ptr(self.device)))
-
-    def _check_chunk(self, x, name, ndim, dtype=None):
-        if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
-            raise ValueError("%s requires a gradient: the streaming calls keep state on the device and are not "
-                             "differentiable -- use MDCTransformer.transform / inverse_transform" % name)
-        x = _host.check_device_tensor(x, name, self.mdct.compute_dtype if dtype is None else dtype, ndim)
-        if x.device != self.device:
-            raise ValueError("%s lives on %s but the stream's state lives on %s" % (name, x.device, self.device))
-        return x
-
-    def _out(self, out, name, shape, like, stream=None, dtype=None):
-        """``out``, checked, or a new tensor on ``like``'s device, of ``dtype`` (default: ``like``'s)."""
-        dtype, device = like.dtype if dtype is None else dtype, like.device
-        if out is None:
-            # the allocator's pool (and reuse order) of the stream the work runs on; no test can assert this (only a reuse of
-            # freed memory by another stream's work would show it): the class docstring states the rule
-            if stream is not None:
-                with torch.cuda.stream(stream):
-                    return torch.empty(shape, dtype=dtype, device=device)
-            return torch.empty(shape, dtype=dtype, device=device)
-        if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != dtype \
-                or out.device != device or not out.is_contiguous() or out.data_ptr() % 16 != 0:
-            raise ValueError("%s must be a contiguous, 16-byte aligned %s tensor of shape %s on %s"
-                             % (name, dtype, tuple(shape), device))
-        return out
-
-    def _stream(self, stream):
-        return _host.stream_ptr(self.device) if stream is None else ctypes.c_void_p(stream.cuda_stream)
-
-    def transform_chunk(self, x_chunk, out=None, stream=None):
-        """x_chunk [B, k*N, C] -> X [B, k, N, C].  ``stream``: a ``torch.cuda.Stream`` to enqueue on (default: the
-        current stream)."""
-        x = self._check_chunk(x_chunk, "x_chunk", 3)
-        B, S, C = x.shape
-        N = self.mdct.filters_n
-        if (B, C) != (self.B, self.C) or S % N != 0:
-            raise ValueError("x_chunk must be [%d, k*%d, %d], got %s" % (self.B, N, self.C, tuple(x.shape)))
-        k = S // N
-        X = self._out(out, "out", (B, k, N, C), x, stream)
-        with _host.on_device(x.device):
-            _lib.check(self._lib.ac_stream_encode_typed(self._handle, None, _host.ptr(x), _host.ptr(X), None, None, 0.0,
-                                                        self.mdct._dtype_id, k, self._stream(stream)))
-        return X
-
-    def encode_chunk(self, x_chunk, drown=0.0, out=None, stream=None):
-        """x_chunk [B, k*N, C] -> (X [B, k, N, C], tonality [B, k, 1, C], threshold [B, k, N, C]) of the chunk's frames
-        (``ac_stream_encode``: MDCT, tonality and masking threshold in one launch where the wave-level kernels apply).
-        ``out``: optional tuple of three tensors to write into."""
-        if self.psy is None:
-            raise ValueError("this stream was created without a masking model (psy=...)")
-        x = self._check_chunk(x_chunk, "x_chunk", 3)
-        B, S, C = x.shape
-        N = self.mdct.filters_n
-        if (B, C) != (self.B, self.C) or S % N != 0:
-            raise ValueError("x_chunk must be [%d, k*%d, %d], got %s" % (self.B, N, self.C, tuple(x.shape)))
-        k = S // N
-        o = out if out is not None else (None, None, None)
-        X = self._out(o[0], "out[0]", (B, k, N, C), x, stream)
-        t = self._out(o[1], "out[1]", (B, k, 1, C), x, stream)
-        thr = self._out(o[2], "out[2]", (B, k, N, C), x, stream)
-        with _host.on_device(x.device):
-            _lib.check(self._lib.ac_stream_encode_typed(self._handle, self.psy._plan(x.device), _host.ptr(x), _host.ptr(X),
-                                                        _host.ptr(t), _host.ptr(thr), float(drown), self.mdct._dtype_id, k,
-                                                        self._stream(stream)))
-        return X, t, thr
-
-    def run(self, x, blocks_per_chunk, masking=True, synthesis=True, drown=0.0, graph=False):
-        """A long device-resident signal ``x [1, K*N, C]`` (or a list of chunk tensors ``[B, k*N, C]``) through the stream
-        in chunks of ``blocks_per_chunk`` blocks with one library call (``ac_stream_run``: launches issued from C; with
-        ``synthesis`` and chunks small enough to be latency-bound, the analysis of chunk i + 1 and the synthesis of chunk i
-        share one launch).  Returns ``(X, t, thr, xhat)`` -- tensors ``[1, K, ...]`` for
-        a tensor input, lists of per-chunk tensors for a list input; ``t`` / ``thr`` are None without ``masking``,
-        ``xhat`` is None without ``synthesis``.  The last chunk of a tensor input may be shorter.
-
-        ``graph=True``: the launches of the call are captured into a HIP graph the first time these input buffers (same
-        addresses, shapes and arguments) are seen, and replayed from then on -- the gaps between the dependent launches
-        go (one stereo clip in chunks of 256 blocks: 7.9 us per chunk against 11.9).  A replay reads the CURRENT contents
-        of the same input buffers and overwrites the output tensors of the first call, which are returned again."""
-        _host.require_float32(self.mdct.compute_dtype, "StreamingMDCT.run (use the chunk calls for bfloat16 / float64 streams)")
-        self._not_delayed("run")
-        self._conceal = None    # (the synthesis state moves on without a source for concealment)
-        if graph:
-            out = self._run_graph(x, blocks_per_chunk, masking, synthesis, drown)
-        else:
-            out = self._run(x, blocks_per_chunk, masking, synthesis, drown)
-        self._advanced = self._advanced or bool(synthesis)   # (only once the library call has gone through)
-        return out
-
-    def _run(self, x, blocks_per_chunk, masking, synthesis, drown):
-        k, N = int(blocks_per_chunk), self.mdct.filters_n
-        if masking and self.psy is None:
-            raise ValueError("this stream was created without a masking model (psy=...)")
-        if k < 1:
-            raise ValueError("blocks_per_chunk must be positive")
-        as_list = isinstance(x, (list, tuple))
-        if as_list:
-            xs = [self._check_chunk(c, "x[%d]" % i, 3) for i, c in enumerate(x)]
-            for c in xs:
-                if tuple(c.shape) != (self.B, k * N, self.C):
-                    raise ValueError("every chunk must be [%d, %d, %d], got %s" % (self.B, k * N, self.C, tuple(c.shape)))
-            groups = [(xs, k)]
-            like = xs[0] if xs else None
-        else:
-            xt = self._check_chunk(x, "x", 3)
-            B, S, C = xt.shape
-            if B != 1 or self.B != 1 or C != self.C or S % N != 0:
-                raise ValueError("a tensor input must be [1, K*%d, %d] on a stream of one clip (pass a list of chunks "
-                                 "otherwise), got %s" % (N, self.C, tuple(xt.shape)))
-            K = S // N
-            full, rest = K // k, K % k
-            like = xt
-            if (k * N * C * 4) % 16 != 0 and K > k:
-                # chunk boundaries inside one tensor would not be 16-byte aligned (filters_n * channels_n odd multiples of
-                # 2): per-chunk tensors through the list form, concatenated afterwards
-                parts = [xt[:, i * k * N:(i + 1) * k * N].clone() for i in range(full)]
-                o = self.run(parts, k, masking=masking, synthesis=synthesis, drown=drown) if full else ([], [], [], [])
-                if rest:
-                    r = self.run([xt[:, full * k * N:].clone()], rest, masking=masking, synthesis=synthesis, drown=drown)
-                    o = tuple((a or []) + (b or []) if (a is not None or b is not None) else None for a, b in zip(o, r))
-                cat = lambda ts: torch.cat(ts, dim=1) if ts else None   # noqa: E731
-                return cat(o[0]), cat(o[1]) if masking else None, cat(o[2]) if masking else None, \
-                    cat(o[3]) if synthesis else None
-            Xall = torch.empty((1, K, N, C), dtype=xt.dtype, device=xt.device)
-            tall = torch.empty((1, K, 1, C), dtype=xt.dtype, device=xt.device) if masking else None
-            thrall = torch.empty_like(Xall) if masking else None
-            xhall = torch.empty_like(xt) if synthesis else None
-            groups = []
-            if full:
-                groups.append(([xt[:, i * k * N:(i + 1) * k * N] for i in range(full)], k))
-            if rest:
-                groups.append(([xt[:, full * k * N:]], rest))
-        outs = ([], [], [], [])
-        pos = 0
-        for chunks, kk in groups:
-            n = len(chunks)
-            if n == 0:
-                continue
-            if as_list:
-                Xc = [torch.empty((self.B, kk, N, self.C), dtype=like.dtype, device=like.device) for _ in range(n)]
-                tc = [torch.empty((self.B, kk, 1, self.C), dtype=like.dtype, device=like.device) for _ in range(n)] if masking else None
-                thc = [torch.empty_like(v) for v in Xc] if masking else None
-                xhc = [torch.empty_like(c) for c in chunks] if synthesis else None
-            else:
-                Xc = [Xall[:, pos + i * kk: pos + (i + 1) * kk] for i in range(n)]
-                tc = [tall[:, pos + i * kk: pos + (i + 1) * kk] for i in range(n)] if masking else None
-                thc = [thrall[:, pos + i * kk: pos + (i + 1) * kk] for i in range(n)] if masking else None
-                xhc = [xhall[:, (pos + i * kk) * N: (pos + (i + 1) * kk) * N] for i in range(n)] if synthesis else None
-            arr = lambda ts: (ctypes.c_void_p * n)(*[v.data_ptr() for v in ts]) if ts is not None else None   # noqa: E731
-            with _host.on_device(self.device):
-                _lib.check(self._lib.ac_stream_run(self._handle, self.psy._plan(self.device) if masking else None, n, kk,
-                                                   arr(chunks), arr(Xc), arr(tc), arr(thc), arr(xhc), float(drown),
-                                                   _host.stream_ptr(self.device)))
-            for o, v in zip(outs, (Xc, tc, thc, xhc)):
-                if v is not None:
-                    o.extend(v)
-            pos += n * kk
-        if as_list:
-            return outs[0], (outs[1] if masking else None), (outs[2] if masking else None), (outs[3] if synthesis else None)
-        return Xall, tall, thrall, xhall
-
-    def _run_graph(self, x, blocks_per_chunk, masking, synthesis, drown):
-        chunks = list(x) if isinstance(x, (list, tuple)) else [x]
-        for c in chunks:
-            self._check_chunk(c, "x", 3)
-        key = (tuple((c.data_ptr(), tuple(c.shape)) for c in chunks), isinstance(x, (list, tuple)), int(blocks_per_chunk),
-               bool(masking), bool(synthesis), float(drown))
-        hit = self._graphs.get(key)
-        # a captured call addresses the stream's HOME state buffers; chunk calls (and reset) since the last run() may have
-        # left the current state in the other buffer of the pair: move it home first (no device work when it is there)
-        with _host.on_device(self.device):
-            _lib.check(self._lib.ac_stream_settle(self._handle, _host.stream_ptr(self.device)))
-        if hit is None:
-            with _host.on_device(self.device):
-                self.mdct._plan(self.device)                       # plans are built outside the capture
-                if masking:
-                    if self.psy is None:
-                        raise ValueError("this stream was created without a masking model (psy=...)")
-                    self.psy._plan(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    outs = self.run(x, blocks_per_chunk, masking=masking, synthesis=synthesis, drown=drown)
-            while len(self._graphs) >= 8:                         # a graph keeps its outputs alive: a handful at most
-                self._graphs.pop(next(iter(self._graphs)))
-            hit = self._graphs[key] = (g, outs, chunks)            # (the inputs stay alive with their graph)
-        hit[0].replay()
-        return hit[1]
-
-    def _not_delayed(self, what):
-        if self._delayed:
-            raise ValueError("%s on a stream that decodes recovering chunks (decode_packed_chunk(..., redundant_at=)), which "
-                             "run one frame behind their rows: flush_packed() or reset() first" % what)
-
-    def inverse_chunk(self, X_chunk, out=None, stream=None):
-        """X_chunk [B, k, N, C] -> x [B, k*N, C]."""
-        self._not_delayed("inverse_chunk")
-        x = self._inverse_chunk(X_chunk, out, stream)
-        if x.shape[1]:
-            self._advanced = True
-        return x
-
-    def _inverse_chunk(self, X_chunk, out, stream):
-        """:meth:`inverse_chunk` without the check of the stream's mode: also the last step of the composed recovering chunk."""
-        X = self._check_chunk(X_chunk, "X_chunk", 4)
-        B, k, N, C = X.shape
-        if (B, C, N) != (self.B, self.C, self.mdct.filters_n):
-            raise ValueError("X_chunk must be [%d, k, %d, %d], got %s" % (self.B, self.mdct.filters_n, self.C,
-                                                                         tuple(X.shape)))
-        x = self._out(out, "out", (B, k * N, C), X, stream)
-        self._conceal = None    # (as the library does: a chunk that does not conceal leaves no source)
-        with _host.on_device(X.device):
-            _lib.check(self._lib.ac_stream_inverse_typed(self._handle, _host.ptr(X), _host.ptr(x), self.mdct._dtype_id, k,
-                                                         self._stream(stream)))
-        return x
-
-    # ---- packed rows at a bitrate, chunk by chunk (extension; DESIGN.md section 8b, "Packed rows in a stream") -----
-    def _packed_ready(self, what, budget):
-        _host.require_float32(self.mdct.compute_dtype, "StreamingMDCT.%s" % what)
-        if self.psy is None:
-            raise ValueError("this stream was created without a masking model (psy=...)")
-        if budget and self.psy.row_budget is None:
-            raise ValueError("%s needs a stream with a row budget: make it from a codec of with_bitrate() or "
-                             "with_row_budget() (codec.stream(...))" % what)
-
-    def _on(self, stream):
-        return torch.cuda.stream(stream) if stream is not None else _host._NO_SWITCH
-
-    @property
-    def row_bytes(self):
-        """Bytes of a row's slot in :meth:`encode_packed_rows_chunk`'s data; None without a row budget."""
-        if self.psy is None or self.psy.row_budget is None:
-            return None
-        return (self.psy.row_budget[0] + 31) // 32 * 4
-
-    def packed_chunk_launches(self, decode=False, *, conceal=False, recover=False, pcm16=False):
-        """Library launches of :meth:`encode_packed_rows_chunk` (``decode=True``: of :meth:`decode_packed_chunk`) on this
-        stream (``ac_stream_packed_launches``): 1 = one launch that carries the overlap state -- filters_n = 1024, 64 bands,
-        mono / stereo, a budget of at most ``_lib.AC_PACK_ROWS_MAX_BITS``, and for the encode a kernel instance that passed
-        the register gate (stereo with ``spreading="f32"`` did not) -- else the launches of the composition (everywhere
-        while ``AC_ENCODE_PACKED_NOFUSE=1`` / ``AC_DECODE_PACKED_NOFUSE=1`` is set: read per call).  0 for the encode on a
-        stream without a row budget.  ``pcm16=True``: of the encode on a ``torch.int16`` chunk
-        (``ac_stream_packed_launches_pcm16``; its instances passed the gate with ``spreading="bf16x2_mfma"`` only).
-        ``decode=True, conceal=True``: of :meth:`decode_packed_chunk` with ``lost`` given -- 1 wherever the plain decode is
-        1, else the 3 library launches of its composition.  ``recover=True`` beside them: of the recovering chunk
-        (``redundant_at`` given; ``ac_stream_packed_launches(s, psy, 3)``), 1 and 3 in the same places."""
-        self._packed_ready("packed_chunk_launches", False)
-        if recover and not conceal:
-            raise ValueError("recover=True is a form of the concealing decode: pass decode=True, conceal=True")
-        if conceal:
-            if not decode:
-                raise ValueError("conceal=True is a form of the decode: pass decode=True")
-            return int(self._lib.ac_stream_packed_launches(self._handle, self.psy._plan(self.device), 3 if recover else 2))
-        if pcm16 and not decode:
-            return int(self._lib.ac_stream_packed_launches_pcm16(self._handle, self.psy._plan(self.device)))
-        return int(self._lib.ac_stream_packed_launches(self._handle, self.psy._plan(self.device), 1 if decode else 0))
-
-    def encode_packed_rows_chunk(self, x_chunk, drown=0.0, stream=None):
-        """On a stream of a codec made by ``with_bitrate()`` / ``with_row_budget()``: x_chunk [B, k*N, C] (float32, or
-        ``torch.int16`` PCM read as ``pcm / 32768``: the rows, and the state left, of that float32 chunk) -> (data uint8
-        [B*k*C*row_bytes], index int64 [B, k, C], fits bool [B, k, C]) -- the rows ``AudioCodec.encode_packed_rows`` gives
-        for the chunk's frames of the whole signal, byte for byte: frame ``f`` of the chunk is frame (blocks so far + f),
-        ``index[b, f, c] = ((b*k + f)*C + c) * row_bytes``.  The overlap state advances as under :meth:`encode_chunk`, so
-        the chunk calls of every form may follow each other.  One launch where :meth:`packed_chunk_launches` is 1
-        (``pcm16=True`` for int16; elsewhere an int16 chunk is converted and takes the float32 path), else
-        :meth:`encode_chunk`, ``psy.quantize_to_budget`` and the packer: the same bytes.  Only enqueues, on ``stream`` or
-        the current stream; float32 only, not differentiable."""
-        self._packed_ready("encode_packed_rows_chunk", True)
-        N, rb = self.mdct.filters_n, self.row_bytes
-        with self._on(stream):
-            pcm16 = isinstance(x_chunk, torch.Tensor) and x_chunk.dtype == torch.int16
-            x = self._check_chunk(x_chunk, "x_chunk", 3, torch.int16 if pcm16 else None)
-            B, S, C = x.shape
-            if (B, C) != (self.B, self.C) or S % N != 0:
-                raise ValueError("x_chunk must be [%d, k*%d, %d], got %s" % (self.B, N, self.C, tuple(x.shape)))
-            k = S // N
-            dev, rows = x.device, B * k * C
-            index = (torch.arange(rows, dtype=torch.int64, device=dev) * rb).view(B, k, C)
-            if rows == 0:
-                return (torch.empty((0,), dtype=torch.uint8, device=dev), index,
-                        torch.empty((B, k, C), dtype=torch.bool, device=dev))
-            psy = self.psy._plan(dev)
-            if pcm16 and self._lib.ac_stream_packed_launches_pcm16(self._handle, psy) != 1:
-                x, pcm16 = x.to(torch.float32) / 32768, False
-            if pcm16 or self._lib.ac_stream_packed_launches(self._handle, psy, 0) == 1:
-                data = torch.empty((rows * rb,), dtype=torch.uint8, device=dev)
-                fits = torch.empty((B, k, C), dtype=torch.bool, device=dev)
-                out = _lib.PackedOut(data.data_ptr(), rb, fits.data_ptr())
-                with _host.on_device(dev):
-                    _lib.check(self._lib.ac_stream_encode_typed(self._handle, psy, _host.ptr(x), ctypes.addressof(out), None,
-                                                                None, float(drown),
-                                                                _lib.AC_PACKED | (_lib.AC_IN_PCM16 if pcm16 else 0), k,
-                                                                self._stream(stream)))
-                return data, index, fits
-            X, _, thr = self.encode_chunk(x, drown, stream=stream)
-            data, fits = _pack_rows_of_spectra(self.psy, X, thr, index, rb)
-            return data, index, fits
-
-    def decode_packed_chunk(self, data, index, pcm16=False, out=None, stream=None, *, lost=None, max_age=8, redundant_at=None):
-        """data uint8 [nbytes], index int64 [B, k, C] -> x [B, k*N, C] (``torch.int16`` with ``pcm16=True``): the next k
-        blocks of the signal, bit-equal to ``inverse_chunk(psy.dequantize(*psy.unpack(data, index)))`` -- with ``pcm16``
-        through the store of ``AudioCodec.decode``: ``0 if NaN else clamp(rint(fp32(32768 * x)), -32768, 32767)``.
-        ``index`` may hold any row starts and damaged rows read as ``psy.unpack`` reads them.  One launch where
-        ``packed_chunk_launches(decode=True)`` is 1, else that composition.  Only enqueues, on ``stream`` or the current
-        stream; float32 only.
-
-        ``lost`` uint8 / bool [B, k, C] marks rows that did not arrive, and they are concealed as
-        ``AudioCodec.decode_packed(..., lost=, max_age=)`` conceals them, with the last row that
-        arrived carried from chunk to chunk: however a signal is split into chunks, the outputs are the blocks of that
-        one-shot call on the whole signal, bit for bit; each row takes the ``max_age`` of its own call.  The carried row
-        is the stream's state: :meth:`reset`, and every chunk that is decoded or inverted without ``lost``, leave no
-        source behind.  One launch where ``packed_chunk_launches(decode=True, conceal=True)`` is 1, else the
-        composition with the same state kept in tensors.
-
-        ``redundant_at`` (with ``lost``; an int in [1, 2^31), DESIGN.md section 8g, "Streams") recovers before it conceals,
-        as ``AudioCodec.decode_packed(..., redundant_at=)`` does, and for that the stream is *delayed*: the k blocks
-        returned are the frames of ``D, row 0, ..., row k-2``, where ``D`` is the deferred last row of the chunk before (on
-        a new or reset stream: a lost row with no source before it), and the chunk's last row waits for the next call.
-        So the successor of every frame is in the chunk in hand: a lost frame whose successor arrived is read from
-        ``index[b, successor, c] + redundant_at`` with no fade, every other frame as under ``lost`` alone.  However
-        ``index [B, K', C]`` is split into chunks, the outputs are blocks ``[0, K')`` of the one-shot call on
-        ``cat(index[:, :1], index)`` and ``cat(ones, lost)`` -- one lost frame in front -- bit for bit, and
-        :meth:`flush_packed` returns block ``K'``.  A stream is delayed from its first such chunk until :meth:`reset`: in
-        between :meth:`inverse_chunk`, :meth:`run` and this call without ``redundant_at`` raise ``ValueError`` and leave
-        the state alone, as does a recovering chunk on a stream whose synthesis one of those has advanced since it was
-        made or reset.  One launch where ``packed_chunk_launches(decode=True, conceal=True, recover=True)`` is 1, else
-        the composition."""
-        self._packed_ready("decode_packed_chunk", False)
-        N = self.mdct.filters_n
-        if redundant_at is not None:
-            if lost is None:
-                raise ValueError("redundant_at without lost: a row is recovered only where lost marks it")
-            redundant_at = self.psy._check_redundant_at(redundant_at)
-        with self._on(stream):
-            if lost is not None:
-                max_age = self.psy._check_max_age(max_age)
-            data = self.psy._check_quant_tensor(data, "data", torch.uint8, ndim=1)
-            if data.device != self.device:
-                raise ValueError("data lives on %s but the stream's state lives on %s" % (data.device, self.device))
-            index = self.psy._check_quant_tensor(index, "index", torch.int64, device=data.device, ndim=3)
-            if lost is not None:
-                lost = self.psy._check_lost(lost, index)
-            B, k, C = index.shape
-            if (B, C) != (self.B, self.C):
-                raise ValueError("index must be [%d, k, %d], got %s" % (self.B, self.C, tuple(index.shape)))
-            x = self._out(out, "out", (B, k * N, C), data, stream, dtype=torch.int16 if pcm16 else torch.float32)
-            if k == 0:
-                return x
-            dev = data.device
-            psy = self.psy._plan(dev)
-            if redundant_at is not None:
-                if self._advanced:
-                    raise ValueError("redundant_at on a stream whose synthesis has advanced without it since it was made or "
-                                     "reset: a recovering chunk runs one frame behind its rows -- reset() first")
-                self._decode_packed_chunk_recovered(data, index, lost, max_age, redundant_at, pcm16, x, psy, stream)
-                self._delayed = True   # (the mode changes only once the chunk has gone through)
-                return x
-            self._not_delayed("decode_packed_chunk without redundant_at")
-            if lost is not None:
-                self._decode_packed_chunk_concealed(data, index, lost, max_age, pcm16, x, psy, stream)
-            else:
-                self._conceal = None   # (a chunk that does not conceal leaves no source; the library marks its own state)
-                if self._lib.ac_stream_packed_launches(self._handle, psy, 1) == 1:
-                    rows = _lib.StreamPackedIn(_lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr()), psy.value,
-                                               1 if pcm16 else 0)
-                    with _host.on_device(dev):
-                        _lib.check(self._lib.ac_stream_inverse_typed(self._handle, ctypes.addressof(rows), _host.ptr(x),
-                                                                     _lib.AC_PACKED, k, self._stream(stream)))
-                else:
-                    self._inverse_chunk_into(self.psy.dequantize(*self.psy.unpack(data, index)), x, pcm16, stream)
-            self._advanced = True
-            return x
-
-    def _inverse_chunk_into(self, X, x, pcm16, stream):
-        """:meth:`inverse_chunk` of X into x, through the 16-bit PCM store where x is int16."""
-        if not pcm16:
-            return self._inverse_chunk(X, x, stream)
-        p = torch.nan_to_num(self._inverse_chunk(X, None, stream) * 32768.0, nan=0.0)   # the float32 product
-        x.copy_(p.round_().clamp_(-32768.0, 32767.0).to(torch.int16))                   # round: half to even
-        return x
-
-    def _decode_packed_chunk_concealed(self, data, index, lost, max_age, pcm16, x, psy, stream):
-        """:meth:`decode_packed_chunk` with ``lost`` given (checked; under the stream the work runs on): the one launch where
-        the library has it, else the composition, which keeps the state the kernel keeps -- the carried row as
-        ``psy.unpack`` read it, and the gap (frames since that row at the end of the chunk before; 32: none in reach) -- in
-        ``self._conceal``.  Nothing here waits for the device."""
-        B, k, C = index.shape
-        dev = data.device
-        if self._lib.ac_stream_packed_launches(self._handle, psy, 2) == 1:
-            self._conceal = None   # (the state lives in the library from here on)
-            rows = _lib.StreamPackedLostIn(
-                _lib.StreamPackedIn(_lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr()), psy.value,
-                                    1 if pcm16 else 0), lost.data_ptr(), max_age)
-            with _host.on_device(dev):
-                _lib.check(self._lib.ac_stream_inverse_typed(self._handle, ctypes.addressof(rows), _host.ptr(x),
-                                                             _lib.AC_PACKED | _lib.AC_CONCEAL, k, self._stream(stream)))
-            return x
-        codes, sf = self.psy.unpack(data, index)
-        state = self._conceal
-        if state is None:   # a new stream, after reset(), or after a chunk that did not conceal: no source
-            state = (torch.zeros_like(codes[:, :1]), torch.zeros_like(sf[:, :1]),
-                     torch.full((B, C), 32, dtype=torch.int64, device=dev))
-        row_codes, row_sf, gap = state
-        # the carried row in front as frame -1; sources as DESIGN.md section 8f defines them
-        codes_ext, sf_ext = torch.cat((row_codes, codes), dim=1), torch.cat((row_sf, sf), dim=1)
-        f = torch.arange(k, dtype=torch.int64, device=dev).view(1, k, 1)
-        last = f.expand(B, k, C).masked_fill(lost != 0, -1).cummax(dim=1).values   # the last frame <= f of the chunk that arrived
-        inside = (last >= 0) & (f - last <= max_age)
-        carried_age = gap.view(B, 1, C) + f + 1
-        carried = ~inside & (gap.view(B, 1, C) <= 31) & (carried_age <= max_age)
-        muted = ~inside & ~carried
-        src = torch.where(inside, last + 1, torch.zeros_like(last))               # frame of codes_ext
-        age = torch.where(inside, f - last, carried_age).masked_fill(muted, 0).to(torch.uint8)
-        N, M = codes.shape[2], sf.shape[2]
-        got_codes = codes_ext.gather(1, src.unsqueeze(2).expand(B, k, N, C)).masked_fill(muted.unsqueeze(2), 0)
-        got_sf = sf_ext.gather(1, src.unsqueeze(2).expand(B, k, M, C)).masked_fill(muted.unsqueeze(2), 0)
-        self._inverse_chunk_into(self.psy.dequantize(got_codes, self.psy.conceal_fade(got_sf, age)), x, pcm16, stream)
-        # the state after the chunk, whatever max_age was
-        final = last[:, -1]                                                         # [B, C]: f*, or -1
-        has = final >= 0
-        at = final.clamp(min=0).view(B, 1, 1, C)
-        new_codes = torch.where(has.view(B, 1, 1, C), codes.gather(1, at.expand(B, 1, N, C)), row_codes)
-        new_sf = torch.where(has.view(B, 1, 1, C), sf.gather(1, at.expand(B, 1, M, C)), row_sf)
-        new_gap = torch.where(has, k - 1 - final, gap + k).clamp(max=32)
-        self._conceal = (new_codes, new_sf, new_gap)   # (after inverse_chunk, which leaves no source)
-        return x
-
-    def _decode_packed_chunk_recovered(self, data, index, lost, max_age, redundant_at, pcm16, x, psy, stream):
-        """:meth:`decode_packed_chunk` with ``redundant_at`` given (checked; under the stream the work runs on): the one
-        launch where the library has it, else the composition on the same state as the concealing one keeps
-        (``self._conceal``) -- the deferred row is the carried row where the gap is 0.  Nothing here waits for the device."""
-        B, k, C = index.shape
-        dev = data.device
-        if self._lib.ac_stream_packed_launches(self._handle, psy, 3) == 1:
-            self._conceal = None   # (the state lives in the library from here on)
-            rows = _lib.StreamPackedRecoverIn(
-                _lib.StreamPackedIn(_lib.PackedRows(data.data_ptr(), data.numel(), index.data_ptr()), psy.value,
-                                    1 if pcm16 else 0), lost.data_ptr(), max_age | _lib.AC_CONCEAL_REDUNDANT, redundant_at)
-            with _host.on_device(dev):
-                _lib.check(self._lib.ac_stream_inverse_typed(self._handle, ctypes.addressof(rows), _host.ptr(x),
-                                                             _lib.AC_PACKED | _lib.AC_CONCEAL, k, self._stream(stream)))
-            return x
-        # the chunk's rows and, behind them, the copies their slots carry: the copy in row j's slot is of frame j - 1
-        codes, sf = self.psy.unpack(data, torch.cat((index, index + redundant_at), dim=1))
-        codes, red_codes, sf, red_sf = codes[:, :k], codes[:, k:], sf[:, :k], sf[:, k:]
-        state = self._conceal
-        if state is None:   # a new stream or after reset(): the deferred row did not arrive and has no source
-            state = (torch.zeros_like(codes[:, :1]), torch.zeros_like(sf[:, :1]),
-                     torch.full((B, C), 32, dtype=torch.int64, device=dev))
-        row_codes, row_sf, gap = state
-        # frames j = 0 .. k of the delayed chunk: j = 0 is D, which arrived where the gap is 0, j = f + 1 is row f; the carried
-        # row in front of the chunk's rows is frame 0 where it is D and the row gap frames before it otherwise
-        codes_ext, sf_ext = torch.cat((row_codes, codes), dim=1), torch.cat((row_sf, sf), dim=1)
-        arrived = torch.cat(((gap == 0).view(B, 1, C), lost == 0), dim=1)              # [B, k+1, C]
-        j = torch.arange(k, dtype=torch.int64, device=dev).view(1, k, 1)
-        last = j.expand(B, k, C).masked_fill(~arrived[:, :k], -1).cummax(dim=1).values   # the last frame <= j that arrived
-        recovered = ~arrived[:, :k] & arrived[:, 1:]
-        inside = (last >= 0) & (j - last <= max_age)
-        carried_age = gap.view(B, 1, C) + j
-        carried = ~inside & (gap.view(B, 1, C) <= 31) & (carried_age <= max_age)
-        muted = ~inside & ~carried & ~recovered
-        src = torch.where(inside, last, torch.zeros_like(last))                        # frame of codes_ext
-        age = torch.where(inside, j - last, carried_age).masked_fill(muted | recovered, 0).to(torch.uint8)
-        N, M = codes.shape[2], sf.shape[2]
-        got_codes = codes_ext.gather(1, src.unsqueeze(2).expand(B, k, N, C)).masked_fill(muted.unsqueeze(2), 0)
-        got_sf = sf_ext.gather(1, src.unsqueeze(2).expand(B, k, M, C)).masked_fill(muted.unsqueeze(2), 0)
-        got_codes = torch.where(recovered.unsqueeze(2), red_codes, got_codes)
-        got_sf = torch.where(recovered.unsqueeze(2), red_sf, got_sf)
-        self._inverse_chunk_into(self.psy.dequantize(got_codes, self.psy.conceal_fade(got_sf, age)), x, pcm16, stream)
-        # the state after the chunk, over its rows 0 .. k-1 whatever max_age was: as the concealing chunk leaves it
-        f = torch.arange(k, dtype=torch.int64, device=dev).view(1, k, 1)
-        final = f.expand(B, k, C).masked_fill(lost != 0, -1).max(dim=1).values          # [B, C]: the last row that arrived, or -1
-        has = final >= 0
-        at = final.clamp(min=0).view(B, 1, 1, C)
-        new_codes = torch.where(has.view(B, 1, 1, C), codes.gather(1, at.expand(B, 1, N, C)), row_codes)
-        new_sf = torch.where(has.view(B, 1, 1, C), sf.gather(1, at.expand(B, 1, M, C)), row_sf)
-        new_gap = torch.where(has, k - 1 - final, gap + k).clamp(max=32)
-        self._conceal = (new_codes, new_sf, new_gap)   # (after the synthesis, which leaves no source)
-        return x
-
-    def flush_packed(self, pcm16=False, out=None, stream=None, *, max_age=8):
-        """The last block of a delayed stream, x [B, N, C]: the frame of the deferred row, which no successor can recover
-        any more -- concealed where it was lost.  Exactly ``decode_packed_chunk`` with ``redundant_at`` on one row marked
-        lost, then :meth:`reset`: block ``K'`` of the one-shot call :meth:`decode_packed_chunk` names."""
-        self._packed_ready("flush_packed", False)
-        with self._on(stream):
-            data = torch.zeros((16,), dtype=torch.uint8, device=self.device)
-            index = torch.zeros((self.B, 1, self.C), dtype=torch.int64, device=self.device)
-            lost = torch.ones((self.B, 1, self.C), dtype=torch.uint8, device=self.device)
-        x = self.decode_packed_chunk(data, index, pcm16, out, stream, lost=lost, max_age=max_age, redundant_at=1)
-        with self._on(stream):   # (reset() enqueues on the current stream: behind the chunk)
-            self.reset()
-        return x

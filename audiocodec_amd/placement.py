@@ -172,7 +172,7 @@ def record_stream(tensor, stream):
 
 def report(device=None):
     """What the pool of ``device`` holds and how its placement was found (None: no pool)."""
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    dev = _host.default_device(device)
     p = pool(dev)
     if p is None:
         return None
@@ -182,7 +182,7 @@ def report(device=None):
 def release(device=None):
     """Gives the pool's memory back (at once, or when the last tensor carved out of it dies) and forgets the pool: the next
     large ``encode`` builds a new one."""
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    dev = _host.default_device(device)
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     with _lock:
         p = _pools.pop(idx, None)

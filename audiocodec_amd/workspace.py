@@ -33,7 +33,7 @@ class Workspace:
     def __init__(self, codec, batches_n, blocks_n, channels_n, max_tries=8, span_gib=96.0, tune=True, device=None):
         _host.require_float32(codec.compute_dtype, "Workspace")
         self.codec = codec
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.device = _host.default_device(device)
         B, K, C, N = int(batches_n), int(blocks_n), int(channels_n), codec.filters_n
         lib = self._lib = _lib.load()
         tries = max(1, min(16, int(max_tries))) if tune else 1
